@@ -227,22 +227,29 @@ __global__ __launch_bounds__(256) void emb_silu_bwd_kernel(const bf16* __restric
       }
       stv<NT>((bf16x8*)(dy + off), o);
     }
-    if ((G & (G - 1)) != 0) {                        // (channel groups not a power of two: every lane adds its own)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) atomicAdd(&acc[cg * 8 + i], part[i]);
-    }
   }
+  // the partial sums meet in a FIXED order (no float atomics in LDS): the result does not depend on wave scheduling
   if ((G & (G - 1)) == 0) {
-    // lanes of a wave with the same channel group (cg = lane % G; every thread is a pixel lane then) add up by shuffles:
-    // G lanes per wave reach the LDS accumulators instead of 64 (see gconv_bwd_fused_kernel)
+    // lanes of a wave with the same channel group (cg = lane % G; every thread is a pixel lane then) add up by shuffles,
+    // then the waves add their G lanes' sums one wave after the other (see gconv_bwd_fused_kernel)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = part[i];
-      for (int o = G; o < 64; o <<= 1) v += __shfl_xor(v, o);
-      if ((int)(threadIdx.x & 63) < G) atomicAdd(&acc[cg * 8 + i], v);
+    for (int i = 0; i < 8; ++i)
+      for (int o = G; o < 64; o <<= 1) part[i] += __shfl_xor(part[i], o);
+    for (int q = 0; q < 256 / 64; ++q) {
+      if ((int)(threadIdx.x >> 6) == q && (int)(threadIdx.x & 63) < G)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[cg * 8 + i] += part[i];
+      __syncthreads();
+    }
+  } else {                                           // (channel groups not a power of two: pixel lane after pixel lane)
+    for (int q = 0; q < npl; ++q) {
+      if (pl == q)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[cg * 8 + i] += part[i];
+      __syncthreads();
     }
   }
-  __syncthreads();
+  // at most TWO pixel slices per frame (oniris_emb_silu_bwd) add into the zeroed row: 0 + a + b is the same in either order
   for (int i = threadIdx.x; i < C; i += 256) atomicAdd(dc + (size_t)n * C + i, acc[i]);
 }
 
@@ -265,7 +272,8 @@ extern "C" int oniris_emb_silu_bwd(const void* du, const void* y, const float* c
   // (every block ends with C global atomics: fewer, longer blocks are faster -- see oniris_gconv_bwd_fused)
   static int tgt = -1;                               // (ONIRIS_EMB_SILU_BLOCKS: A/B knob)
   if (tgt < 0) { const char* e = getenv("ONIRIS_EMB_SILU_BLOCKS"); tgt = e ? atoi(e) : 1024; }
-  while (slices < 16 && P / (slices * 2) >= npl * 4 && (long long)N * slices < tgt) slices *= 2;
+  // (<= 2 slices: two float additions into a zeroed value commute, more would make dc depend on the order of the blocks)
+  while (slices < 2 && P / (slices * 2) >= npl * 4 && (long long)N * slices < tgt) slices *= 2;
   const int ppb = cdiv(P, slices);
   const size_t ndc = (size_t)N * C;
   if (!dc_is_zero) ONIRIS_KLAUNCH(zero_f32_kernel, dim3((unsigned)((ndc + 255) / 256)), dim3(256), 0, stream, dc, ndc);

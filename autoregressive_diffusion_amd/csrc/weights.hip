@@ -546,24 +546,33 @@ __global__ __launch_bounds__(1024) void gconv_bwd_fused_kernel(const bf16* g, co
       for (int i = 0; i < 8; ++i) o3[i] = f2bf(acc3[i]);
       stv<NT>((bf16x8*)(dy3 + (size_t)bt * PC + off), o3);
     }
-    if (MODE == 1 && (G8 & (G8 - 1)) != 0) {                      // (channel groups not a power of two: every lane adds its own)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) atomicAdd(&accs[s][cg * 8 + i], part[s][i]);
-    }
   }
+  // the partial sums meet in a FIXED order (no float atomics in LDS): the result does not depend on wave scheduling
   if (MODE == 1 && (G8 & (G8 - 1)) == 0) {
     // the lanes of a wave that hold the same channel group (cg = lane % G8: G8 a power of two <= 64, every thread of the block
-    // is a pixel lane then) add up by shuffles first; G8 lanes per wave reach the LDS accumulators instead of 64
+    // is a pixel lane then) add up by shuffles first; then the waves add their G8 lanes' sums one wave after the other
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float v = part[s][i];
-        for (int o = G8; o < 64; o <<= 1) v += __shfl_xor(v, o);
-        if ((int)(threadIdx.x & 63) < G8) atomicAdd(&accs[s][cg * 8 + i], v);
-      }
+      for (int i = 0; i < 8; ++i)
+        for (int o = G8; o < 64; o <<= 1) part[s][i] += __shfl_xor(part[s][i], o);
+    for (int q = 0; q < NTH / 64; ++q) {
+      if ((int)(threadIdx.x >> 6) == q && (int)(threadIdx.x & 63) < G8)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) accs[s][cg * 8 + i] += part[s][i];
+      __syncthreads();
+    }
+  } else if (MODE == 1) {                                          // (channel groups not a power of two: pixel lane after pixel lane)
+    for (int q = 0; q < npl; ++q) {
+      if (pl == q)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) accs[s][cg * 8 + i] += part[s][i];
+      __syncthreads();
+    }
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -609,7 +618,9 @@ extern "C" int oniris_gconv_bwd_fused(int mode, const void* g, const void* raw, 
   static int tgt1 = -1;                              // (ONIRIS_GCONV_BWD_BLOCKS: A/B knob for mode 1)
   if (tgt1 < 0) { const char* e = getenv("ONIRIS_GCONV_BWD_BLOCKS"); tgt1 = e ? atoi(e) : 512; }
   const int tgt = (mode == 1) ? tgt1 : 2048;
-  while (slices < 32 && P / (slices * 2) >= npl * 2 && (long long)B * T * slices < tgt) slices *= 2;
+  // (<= 2 slices: the slices' sums meet through float atomics in zeroed values, and 0 + a + b is the same in either order;
+  // more slices would make the gradients depend on the order in which the blocks finish)
+  while (slices < 2 && P / (slices * 2) >= npl * 2 && (long long)B * T * slices < tgt) slices *= 2;
   const int ppb = cdiv(P, slices);
   const int csp = cscale_pitch > 0 ? cscale_pitch : C;
   ONIRIS_CHECK_ARG(csp >= C && csp % 4 == 0, "gconv_bwd_fused: cscale_pitch must be a multiple of 4 and >= C");
@@ -632,7 +643,8 @@ extern "C" int oniris_gconv_bwd_prep(const void* dout, const void* out, const vo
   ONIRIS_CHECK_ARG(dout && out && y3 && coef_own && coef_ctx && S1 && S2 && dy3 && B > 0 && T > 0 && (S == 1 || S == 2) &&
                    frame_elems > 0 && frame_elems % 8 == 0, "gconv_bwd_prep: bad arguments");
   int slices = 1;                                    // (d_coef_own / d_coef_ctx are ACCUMULATED: zero on entry)
-  while (slices < 16 && (long long)B * T * slices < 1024 && frame_elems / (slices * 2) >= 256 * 8 * 2) slices *= 2;
+  // (<= 2 slices: two float additions into a zeroed value commute -- S1 / S2 do not depend on the order of the blocks)
+  while (slices < 2 && (long long)B * T * slices < 1024 && frame_elems / (slices * 2) >= 256 * 8 * 2) slices *= 2;
   ONIRIS_KLAUNCH(gconv_bwd_prep_kernel, dim3(B * T, slices), dim3(256), 0, stream, (const bf16*)dout, (const bf16*)out,
                      (const bf16*)y3, coef_own, coef_ctx, S1, S2, (bf16*)dy3, S, T, (size_t)frame_elems);
   ONIRIS_LAUNCH_CHECK();

@@ -2,10 +2,14 @@
 """Denoiser-step throughput of the MI355X-native Oniris implementation (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR               (+ what the last timed step computed, as DIR/<name>.npy)
+  python bench.py ... --full                           (+ per-mode step times, rooflines, extra records, CPU baseline)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; everything else it can measure is behind --full.
 
 Workload (config.workload): the Lunar-Lander net of gym_train.py:37-47 (46.2 M parameters), 64-frame sequences of
 8x64x64 latents, B sequences per GPU -- by default the reference's own micro-batch, 8 (gym_train.py:55; rounds 1-3 quoted
-B = 2, which the default run still reports as extra.gym_t64_b2) -- synthetic N(0,1) latents and random-init weights.  One step = the reference
+B = 2, which --full still reports as extra.gym_t64_b2) -- synthetic N(0,1) latents and random-init weights.  One step = the reference
 training micro-step: EDM2Loss forward (Precond -> UNet over clean|noised frame slots), backward, gradient
 all-reduce (N > 1), fused AdamW, with the reference's 3:1 mix of 3-D and 2-D steps (gym_train.py:96).
 value = latent frames / s over the whole job = N * B * T * K / wall time of the K timed steps (max over ranks).
@@ -68,10 +72,45 @@ def _pmc_traffic(key):
     return None, source
 
 
-MFMA_BF16_PEAK = 2.5e15          # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_BF16_PEAK = 2.5e15          # dense bf16, MI355X (CDNA4) peak
 HBM_ACHIEVABLE = 6.3e12          # B/s, the figure SURVEY 8d / BASELINE.md section 3 price memory-bound layers with
 # algorithmic forward FLOPs per sample of the 3-D step; x3 forward + backward
 ALGO_FWD_FLOPS = {("gym", 64): 1.82e12, ("cs", 32): 2.58e12, ("cs", 64): 5.16e12}
+
+
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: elements kept of each parameter-sized array (8 MB of float32)
+DUMP_SEED = 0                    # ... chosen once, without replacement, by numpy.random.default_rng(DUMP_SEED)
+
+
+def _write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _step_outputs(named, loss, grad_of, emas):
+    """What one training step hands its caller: the loss and, over the trainable parameters in module order (independent of
+    how the flat buffer lays them out), the updated parameters, their gradients (grad_of(p); None: not kept) and the EMA
+    profiles (emas: one function p -> tensor per profile).  The parameter-sized arrays are a fixed seeded sample of
+    DUMP_SAMPLE elements, the same indices for all of them.  Host float32 arrays by name."""
+    import numpy as np
+    import torch
+    params = [p for _, p in named]
+    n = sum(p.numel() for p in params)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(params[0].device)
+
+    def pick(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts])[idx].cpu().numpy()
+
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "params": pick(params)}
+    if grad_of is not None:
+        out["grads"] = pick([grad_of(p) for p in params])
+    for k, view in enumerate(emas):
+        out[f"ema{k}"] = pick([view(p) for p in params])
+    return out
 
 
 C1_CFG = dict(img_resolution=64, img_channels=8, label_dim=4, model_channels=16, channel_mult=[1, 2, 4, 8], num_blocks=1,
@@ -147,6 +186,8 @@ def rollout(args, quiet=False):
                                                   sigma_max=80, rho=2)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", None):
+        _write_outputs(args.dump_outputs, {"frame": x.float().cpu().numpy()})
     evals = 31 * args.gen_frames
     out = {"metric": "rollout generated frames/s (config 5, KV-cached sampler)", "value": B * args.gen_frames / dt,
            "unit": "frames/s", "n_gpus": 1, "ms_per_unet_eval": dt / evals * 1e3, "frames_generated": args.gen_frames,
@@ -163,7 +204,7 @@ def rollout(args, quiet=False):
 # (profiles/r06_rollout_gaps.txt: 19 % of a frame idle; profiles/r06_rollout_stream_ab*.txt: 27.2 -> 32.3 frames/s with one queue,
 # nothing else changed).  One hardware queue is right for a single-stream inference process and WRONG for data-parallel training
 # (RCCL's stream must overlap the backward kernels), so it is set for rollout-only processes -- `--mode rollout`, and the child process
-# in which the default training run measures its `extra.rollout_*` records -- never for a training process.  setdefault: an explicit
+# in which a --full training run measures its `extra.rollout_*` records -- never for a training process.  setdefault: an explicit
 # setting in the caller's environment wins.  The training step does not notice it (profiles/r06_hwq_train_ab.txt: 8551 vs 8554 frames/s).
 ROLLOUT_ENV = {"GPU_MAX_HW_QUEUES": "1"}
 
@@ -471,6 +512,16 @@ def train(args, netname, steps, warmup, rank, world, dev, wd, light=False, light
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     loss_val = float(last.item())
+    if not light and rank == 0 and getattr(args, "dump_outputs", None):
+        # what the LAST timed step computed, read back before anything else runs a step
+        named = [(n, p) for n, p in unet.named_parameters() if p.requires_grad]
+        if torch_loop:
+            ids = [id(p) for p in net.parameters()]
+            outs = _step_outputs(named, last, None, [(lambda p, d=dict(zip(ids, cp.parameters())): d[id(p)]) for cp in ema_copies])
+        else:
+            outs = _step_outputs(named, last, lambda p: flat.slice_of(flat.grad, p),
+                                 [(lambda p, k=k: ema.view(k, p)) for k in range(len(ema.emas))])
+        _write_outputs(args.dump_outputs, outs)
     exposed = (sum(a.elapsed_time(b) for a, b in comm_events) / max(1, steps)) if (multi and comm_events) else None
     exposed_stage = ({k: round(sum(a.elapsed_time(b) for a, b in v) / max(1, steps), 4) for k, v in sorted(comm_stage.items())}
                      if (multi and comm_stage) else None)
@@ -491,7 +542,7 @@ def train(args, netname, steps, warmup, rank, world, dev, wd, light=False, light
 
     # per-mode step times (one 3-D and one 2-D step, timed separately, not part of `value`; median of 3)
     per_mode = {}
-    for name, i in (("ms_3d_step", 1), ("ms_2d_step", 0)):
+    for name, i in ((("ms_3d_step", 1), ("ms_2d_step", 0)) if args.full else ()):
         ts = []
         for _ in range(3):
             wd.beat(f"{tag}per-mode step ({name})")
@@ -500,7 +551,7 @@ def train(args, netname, steps, warmup, rank, world, dev, wd, light=False, light
         per_mode[name] = sorted(ts)[1]
 
     roof, kernels, roof_attn, roof_attn_bwd, roof_step, roof_step_2d = None, None, None, None, None, None
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # one full 3:1 cycle (eager), every MFMA launch bracketed by HIP events on its own stream; the 2-D step and the three
         # 3-D steps are aggregated separately (roofline_step is the 3-D step's)
         agg, agg3, agg2 = {}, {}, {}
@@ -594,7 +645,7 @@ def train(args, netname, steps, warmup, rank, world, dev, wd, light=False, light
                                                  frac=round(v["flops"] / (v["ms"] * 1e-3) / MFMA_BF16_PEAK, 3),
                                                  roof=round(v["t_min"] / (v["ms"] * 1e-3), 3))
                                          for k, v in sorted(agg2.items(), key=lambda kv: -kv[1]["ms"])[:8]})
-    elif world > 1:
+    elif args.full and world > 1:
         for i in range(4):
             wd.beat(f"{tag}unprofiled cycle step {i} (collectives matched across ranks)")
             step(i)                                               # keep collectives matched across ranks
@@ -652,11 +703,19 @@ def main():
     ap.add_argument("--extra-rollout-frames", type=int, default=256,
                     help="generated frames of the `extra.rollout_<n>` record (BASELINE configs[4]: 256)")
     ap.add_argument("--cpu-frames", type=int, default=64,
-                    help="frames of the CPU-baseline sample: 64 = BASELINE configs[1] at B = 1 (BASELINE.md section 3: about two "
+                    help="--full: frames of the CPU-baseline sample: 64 = BASELINE configs[1] at B = 1 (BASELINE.md section 3: about two "
                          "minutes of host time); smaller = a shorter sample; 0 = skip")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-mode step times, the profiled cycle and its "
+                         "rooflines, the `extra` records and the CPU baseline (--no-profile, --no-extra, --cpu-frames 0 drop "
+                         "parts of it).  Off: set up, warm up, time the K steps, print the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the loss and a "
+                         "fixed seeded sample of the updated parameters, their gradients and the EMA profiles (rollout: the "
+                         "last generated frame)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the profiled cycle (rooflines, kernels)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the `extra` records (Counter-Strike T = 32 training steps, a KV-cached rollout) the default "
+                    help="--full: skip the `extra` records (Counter-Strike T = 32 training steps, a KV-cached rollout) the "
                          "1-GPU gym run appends to its JSON line")
     ap.add_argument("--mode", choices=["train", "rollout"], default="train",
                     help="train = the BASELINE headline metric (default); rollout = config 5 (KV-cached sampler), extra line")
@@ -691,9 +750,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force_dist = bool(os.environ.get("ONIRIS_FORCE_DIST"))          # debug: run the RCCL/DDP path with a single rank
-    # the rollout records of the default run are measured FIRST, each in a child process of its own (ROLLOUT_ENV), while this process
+    # the rollout records of a --full run are measured FIRST, each in a child process of its own (ROLLOUT_ENV), while this process
     # has not touched the GPU yet: a child is started (fork + exec) only from a process without HIP state
-    want_extra = (rank == 0 and world == 1 and not force_dist and args.net == "gym" and not args.no_extra and args.accum == 1
+    want_extra = (args.full and rank == 0 and world == 1 and not force_dist and args.net == "gym" and not args.no_extra and args.accum == 1
                   and not os.environ.get("ONIRIS_ONLY_MODE") and not args.dry_run and args.gpus == 1)
     pre_extra = {}
     if want_extra:
@@ -735,7 +794,7 @@ def main():
 
     out = train(args, args.net, args.steps, args.warmup, rank, world, dev, wd)
     single = rank == 0 and world == 1 and not force_dist
-    if single and args.net == "gym" and not args.no_extra and args.accum == 1 and not os.environ.get("ONIRIS_ONLY_MODE"):
+    if single and args.full and args.net == "gym" and not args.no_extra and args.accum == 1 and not os.environ.get("ONIRIS_ONLY_MODE"):
         # BASELINE configs[2] and [4] next to the headline, so that their figures are witnessed by the same run:
         # the Counter-Strike net at its own 32 frames (8 timed steps, ~1 s) and a 32-frame KV-cached rollout (~2 s)
         import types
@@ -753,7 +812,7 @@ def main():
         except Exception as e:                                   # (never lose the headline to an extra)
             extra["error"] = f"{type(e).__name__}: {e}"
         out["extra"] = extra
-    if single and args.cpu_frames > 0 and args.net == "gym":
+    if single and args.full and args.cpu_frames > 0 and args.net == "gym":
         out["cpu_baseline"] = cpu_baseline(args.cpu_frames)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -3,7 +3,7 @@
 O=gpurun_out
 name=$1; shift
 for v in "$@"; do
-  env $name=$v python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab_${name}_$v.json 2> $O/ab_${name}_$v.err
+  env $name=$v python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab_${name}_$v.json 2> $O/ab_${name}_$v.err
 done
 python - "$name" "$@" <<'PY'
 import json, sys

@@ -4,7 +4,7 @@ O=gpurun_out
 python -m pytest tests -m gpu -q -x 2>&1 | tail -4
 for rep in 1 2; do
 for v in 16 32; do
-  ONIRIS_IN_PAD=$v python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab6_${v}_$rep.json 2>/dev/null
+  ONIRIS_IN_PAD=$v python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab6_${v}_$rep.json 2>/dev/null
   ONIRIS_IN_PAD=$v python bench.py --mode rollout --gen-frames 48 --batch 1 > $O/ab6_ro_${v}_$rep.json 2>/dev/null
   python - $v $rep <<'PY'
 import json, sys

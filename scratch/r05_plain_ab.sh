@@ -4,7 +4,7 @@ O=gpurun_out
 python -m pytest tests/test_ops_gpu.py -m gpu -q -x -k "test_conv_plain or test_conv_epilogues or clip_flags" 2>&1 | tail -15
 for rep in 1 2; do
 for bt in 132 4; do
-  ONIRIS_BIG_TILE=$bt python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab5_${bt}_$rep.json 2>/dev/null
+  ONIRIS_BIG_TILE=$bt python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab5_${bt}_$rep.json 2>/dev/null
   python - $bt $rep <<'PY'
 import json, sys
 bt, rep = sys.argv[1:]

@@ -5,11 +5,11 @@ O=gpurun_out
 python -m pytest tests/test_model_gpu.py -m gpu -q -x -s -k "cs_shaped_unet_vs_oracle or g6 or ddp" > $O/r05_scalar_grads.log 2>&1; echo rc=$? >> $O/r05_scalar_grads.log
 grep -E "scalar gradients|passed|failed|rc=" $O/r05_scalar_grads.log
 python -m pytest tests/test_ops_gpu.py tests/test_abi.py -m gpu -q -x > $O/r05_ops.log 2>&1; echo rc=$? >> $O/r05_ops.log; tail -3 $O/r05_ops.log
-python bench.py --steps 12 --warmup 4 --cpu-frames 0 > $O/r05_bench_2.json 2> $O/r05_bench_2.err; tail -c 600 $O/r05_bench_2.err
+python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 > $O/r05_bench_2.json 2> $O/r05_bench_2.err; tail -c 600 $O/r05_bench_2.err
 for k in 8 16 32; do
-ONIRIS_COMM_CUS_ALWAYS=$k python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra --no-profile > $O/r05_bench_cus$k.json 2> $O/r05_bench_cus$k.err
+ONIRIS_COMM_CUS_ALWAYS=$k python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra --no-profile > $O/r05_bench_cus$k.json 2> $O/r05_bench_cus$k.err
 done
-python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra --no-profile > $O/r05_bench_cus0.json 2> $O/r05_bench_cus0.err
+python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra --no-profile > $O/r05_bench_cus0.json 2> $O/r05_bench_cus0.err
 python - <<'PY'
 import json
 for k in (0, 8, 16, 32):

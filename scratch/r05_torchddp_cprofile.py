@@ -6,7 +6,7 @@ wrapper = sys.argv[1] if len(sys.argv) > 1 else "torch"
 dist_ = len(sys.argv) > 2 and sys.argv[2] == "dist"
 if dist_:
     os.environ["ONIRIS_FORCE_DIST"] = "1"
-sys.argv = ["bench.py", "--wrapper", wrapper, "--steps", "8", "--warmup", "4", "--cpu-frames", "0", "--no-extra", "--no-profile"]
+sys.argv = ["bench.py", "--full", "--wrapper", wrapper, "--steps", "8", "--warmup", "4", "--cpu-frames", "0", "--no-extra", "--no-profile"]
 import bench
 pr = cProfile.Profile()
 pr.enable()

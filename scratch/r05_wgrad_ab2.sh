@@ -5,7 +5,7 @@ ONIRIS_LIB_NAME=liboniris_hip_wng1c.so ONIRIS_WGRAD_CAP_MUL=2 python -m pytest t
 for rep in 1 2; do
 for cfg in "liboniris_hip_wng1b.so 2" "liboniris_hip_wng1c.so 2"; do
   set -- $cfg
-  ONIRIS_LIB_NAME=$1 ONIRIS_WGRAD_CAP_MUL=$2 python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab_wng_$1_$rep.json 2> $O/ab_wng_$1_$rep.err
+  ONIRIS_LIB_NAME=$1 ONIRIS_WGRAD_CAP_MUL=$2 python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab_wng_$1_$rep.json 2> $O/ab_wng_$1_$rep.err
   python - $1 $rep <<'PY'
 import json, sys
 lib, rep = sys.argv[1:]

@@ -3,9 +3,9 @@
 O=gpurun_out
 for rep in 1 2; do
 for lib in liboniris_hip_wng2.so liboniris_hip.so; do
-  ONIRIS_LIB_NAME=$lib python bench.py --batch 2 --steps 20 --warmup 5 --cpu-frames 0 --no-extra --no-profile > $O/ab3_b2_${lib}_$rep.json 2>/dev/null
-  ONIRIS_LIB_NAME=$lib python bench.py --net cs --steps 8 --warmup 4 --no-profile --cpu-frames 0 > $O/ab3_cs_${lib}_$rep.json 2>/dev/null
-  ONIRIS_LIB_NAME=$lib python bench.py --net cs --frames 64 --steps 8 --warmup 4 --no-profile --cpu-frames 0 > $O/ab3_cs64_${lib}_$rep.json 2>/dev/null
+  ONIRIS_LIB_NAME=$lib python bench.py --full --batch 2 --steps 20 --warmup 5 --cpu-frames 0 --no-extra --no-profile > $O/ab3_b2_${lib}_$rep.json 2>/dev/null
+  ONIRIS_LIB_NAME=$lib python bench.py --full --net cs --steps 8 --warmup 4 --no-profile --cpu-frames 0 > $O/ab3_cs_${lib}_$rep.json 2>/dev/null
+  ONIRIS_LIB_NAME=$lib python bench.py --full --net cs --frames 64 --steps 8 --warmup 4 --no-profile --cpu-frames 0 > $O/ab3_cs64_${lib}_$rep.json 2>/dev/null
   python - $lib $rep <<'PY'
 import json, sys
 lib, rep = sys.argv[1:]

@@ -4,7 +4,7 @@ O=gpurun_out
 python -m pytest tests -m gpu -q -x -k "wgrad or gated_conv_train or g8_ or g3_" 2>&1 | tail -3
 for rep in 1 2; do
 for lib in liboniris_hip_wsold.so liboniris_hip_wsph8.so liboniris_hip.so; do
-  ONIRIS_LIB_NAME=$lib python bench.py --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab4_${lib}_$rep.json 2>/dev/null
+  ONIRIS_LIB_NAME=$lib python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --no-extra > $O/ab4_${lib}_$rep.json 2>/dev/null
   python - $lib $rep <<'PY'
 import json, sys
 lib, rep = sys.argv[1:]

@@ -1,5 +1,5 @@
 #!/bin/bash
-run() { echo -n "$1: "; env $1 python bench.py --steps 16 --warmup 4 --cpu-frames 0 --no-extra --no-profile 2>/dev/null | python -c "
+run() { echo -n "$1: "; env $1 python bench.py --full --steps 16 --warmup 4 --cpu-frames 0 --no-extra --no-profile 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('frames/s', round(d['value'],1), 'ms/step', round(d['ms_per_step'],3))"; }
 run "X=1"

@@ -3,6 +3,8 @@ networks_edm2.py:96-110,238-258 / test.py:28): only its module tree and state_di
 `emb_gain, conv_res0.weight, emb_linear.weight, conv_res1.weight [, conv_skip.weight] [, attn_qkv.weight,
 attn_proj.weight]`, at the top `emb_fourier.{freqs,phases}, emb_noise.weight, emb_label.weight, out_conv.weight,
 out_gain`, enc/dec ModuleDicts in the same order as the 3-D net.  Built from a paramgen parameter set (3-D key names)."""
+import math
+
 import torch
 from torch import nn
 
@@ -52,6 +54,8 @@ class Net2D(nn.Module):
 
 
 def state_sums(sd):
-    """(sorted keys, float64 sums, float64 abs-sums) of a state dict: the fixture content."""
+    """(sorted keys, float64 sums, float64 abs-sums) of a state dict: the fixture content.  The sums are math.fsum's, exactly
+    rounded and so independent of summation order: a threaded / vectorised tensor sum depends on the host's thread count."""
     keys = sorted(k for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point())
-    return keys, [float(sd[k].double().sum()) for k in keys], [float(sd[k].double().abs().sum()) for k in keys]
+    vals = {k: sd[k].double().reshape(-1).tolist() for k in keys}
+    return keys, [math.fsum(vals[k]) for k in keys], [math.fsum(map(abs, vals[k])) for k in keys]

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -46,3 +48,61 @@ def test_watchdog_names_the_stage_of_a_hung_collective():
     assert r.returncode != 0
     assert "watchdog: rank 0 made no progress" in r.stderr and "all_reduce(MAX)" in r.stderr, r.stderr[-2000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_are_float32_and_the_same_sample_every_run(tmp_path):
+    # --dump-outputs: the last timed step's loss and a fixed seeded sample of parameter-sized arrays, float32 .npy files
+    # (run in a child: importing bench.py sets process environment this test process must not carry into later tests)
+    code = (
+        "import sys, numpy as np, torch\n"
+        "import bench\n"
+        "torch.manual_seed(0)\n"
+        "m = torch.nn.Sequential(torch.nn.Linear(300, 400), torch.nn.Linear(400, 7))\n"
+        "named = list(m.named_parameters())\n"
+        "out = bench._step_outputs(named, torch.tensor(2.5, dtype=torch.float64), lambda p: 2 * p, [lambda p: 3 * p])\n"
+        "bench._write_outputs(sys.argv[1], out)\n")
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "-c", code, str(tmp_path / d)], cwd=ROOT, capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-2000:]
+    import numpy as np
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["ema0.npy", "grads.npy", "loss.npy", "params.npy"]
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    b = {n: np.load(tmp_path / "b" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].tolist() == [2.5]
+    n = 300 * 400 + 400 + 400 * 7 + 7
+    assert a["params.npy"].shape == (n,)                       # fewer elements than the sample size: all of them
+    assert np.array_equal(a["grads.npy"], 2 * a["params.npy"]) and np.array_equal(a["ema0.npy"], 3 * a["params.npy"])
+    assert all(np.array_equal(a[k], b[k]) for k in names)
+
+
+def test_plain_run_options():
+    # a plain run leaves the extra measurements to --full; --dump-outputs DIR writes the last timed step's outputs
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_reproducibly(tmp_path):
+    """A plain run on the GPU at a small shape, twice: the result line holds the headline fields and none of what --full
+    adds, and --dump-outputs writes the same float32 arrays both times (same inputs, reproducible step)."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--frames", "8",
+                  "--dump-outputs", str(tmp_path / d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    out = lines[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "latent-frames/s"
+    assert "extra" not in out and out["cpu_baseline"] is None and out["roofline_step"] is None and out["kernels"] is None
+    assert not any(k.startswith("ms_") for k in out["config"])
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["ema0.npy", "ema1.npy", "grads.npy", "loss.npy", "params.npy"]
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    b = {n: np.load(tmp_path / "b" / n) for n in names}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["params.npy"].shape == (1 << 21,) and np.abs(a["grads.npy"]).max() > 0
+    assert not np.array_equal(a["ema0.npy"], a["params.npy"])       # the EMA profiles trail the parameters
+    assert all(np.array_equal(a[n], b[n]) for n in names)

@@ -1306,3 +1306,41 @@ def test_ddp_with_torch_optimizer_on_the_unet():
         moved = max(rel(pp[k], build_precond(SMALL_CFG, 67, 1.0).state_dict()[k].float().cpu()) for k in list(pp)[:40] if pp[k].numel() > 64)
         print(what, "+ torch.optim.AdamW vs the un-wrapped loop: worst parameter rel L2", worst, "(the loop moved them by", moved, ")")
         assert worst < 1e-4 and moved > 1e-3
+
+
+@pytest.mark.selfcheck
+def test_training_gradients_are_bitwise_reproducible():
+    """Two backward passes of the same 3-D and 2-D training step from the same state give bit-identical gradients: the
+    gate / emb-scale gradient sums meet in a fixed order (no float atomics in LDS, at most two pixel slices per frame)."""
+    B, T, mc = 2, 8, 32
+    from edm2.networks_edm2 import UNet, Precond
+    from edm2.loss import EDM2Loss
+    from autoregressive_diffusion_amd.parallel import FlatParams
+    torch.manual_seed(0)
+    unet = UNet(img_resolution=64, img_channels=8, label_dim=4, model_channels=mc, channel_mult=[1, 2, 4, 8], num_blocks=1,
+                video_attn_resolutions=[8], frame_attn_resolutions=[16]).to(DEV)
+    for m in unet.modules():
+        if hasattr(m, "emb_gain"):
+            torch.nn.init.constant_(m.emb_gain, 0.3)
+    torch.nn.init.constant_(unet.out_gain, 1.0)
+    flat = FlatParams(unet, lazy_small=True)
+    net = Precond(unet, use_fp16=True, sigma_data=1.0).to(DEV).train()
+    g = torch.Generator(device=DEV).manual_seed(1)
+    lat = torch.randn(B, T, 8, 64, 64, device=DEV, generator=g)
+    act = torch.randint(0, 4, (B, T), device=DEV, generator=g)
+    loss_fn = EDM2Loss(P_mean=1.2, P_std=1.0, sigma_data=1.0, context_noise_reduction=0.5)
+    named = [(n, p) for n, p in unet.named_parameters() if p.requires_grad]
+    for just_2d in (False, True):
+        S = 1 if just_2d else 2
+        sig = torch.randn(B, S * T, device=DEV, generator=g).exp()
+        noise = torch.randn(B, S * T, 8, 64, 64, device=DEV, generator=g)
+        res = []
+        for rep in range(3):                 # (rep 0: the forced weight normalisation settles the weights first)
+            flat.zero_grad()
+            loss, _ = loss_fn(net, lat, act, sigma=sig, just_2d=just_2d, noise=noise, sync=False)
+            loss.backward()
+            flat.gather()
+            res.append((loss.detach().clone(), {n: flat.slice_of(flat.grad, p).clone() for n, p in named}))
+        assert torch.equal(res[1][0], res[2][0])
+        differ = [n for n, _ in named if not torch.equal(res[1][1][n], res[2][1][n])]
+        assert not differ, f"2d={just_2d}: gradients not reproducible: {differ[:8]}"

@@ -1182,3 +1182,48 @@ def test_prelude_kernels_and_adjoints_match_torch_autograd():
         assert rel(emb, want) < 4e-3
         (want * re_.float()).sum().backward()
         assert rel(g1, e1.grad) < 6e-3 and (not with_e2 or rel(g2, e2.grad) < 6e-3)
+
+
+@pytest.mark.parametrize("C,P", [(24, 4096), (32, 4096), (48, 1024), (256, 256)])
+def test_emb_scale_gradient_sums_are_exact_and_reproducible(C, P):
+    """The emb-scale gradient dc[n][co] = sum_pixels dz * y of oniris_emb_silu_bwd and of oniris_gconv_bwd_fused mode 1 against
+    an fp64 restatement, and bit-identical over repeated launches: the partial sums meet in a fixed order, channel groups
+    that are not a power of two (C = 24, 48) included."""
+    from autoregressive_diffusion_amd import ops
+    from autoregressive_diffusion_amd._lib import lib, check
+    torch.manual_seed(C + P)
+    B, T = 1, 4
+    N = B * 2 * T
+    g = torch.randn(N, P, C, device="cuda").to(torch.bfloat16)
+    raw = torch.randn(N, P, C, device="cuda").to(torch.bfloat16)
+    cs = (torch.rand(N, C, device="cuda") + 0.5).contiguous()
+    z = raw.double() * cs.double()[:, None, :]
+    dz = g.double() * torch.sigmoid(z) * (1 + z * (1 - torch.sigmoid(z))) / 0.596
+    want = (dz * raw.double()).sum(1)
+
+    def emb_silu():
+        dy, dc = torch.empty_like(g), torch.zeros(N, C, device="cuda")
+        check(lib.oniris_emb_silu_bwd(ops._p(g), ops._p(raw), ops._p(cs), ops._p(dy), ops._p(dc), N, P, C, C, 1, ops._stream()),
+              "emb_silu_bwd")
+        return [dy, dc]
+
+    def fused():
+        y3 = torch.randn(B * T, P, C, device="cuda", generator=torch.Generator("cuda").manual_seed(3)).to(torch.bfloat16)
+        ca = torch.linspace(0.5, 1.0, N, device="cuda")
+        cb = torch.linspace(0.1, 0.4, N, device="cuda")
+        dout, dy3 = torch.empty_like(g), torch.empty_like(y3)
+        acc = torch.zeros(N * (2 + C), device="cuda")
+        dca, dcb, dcs = acc[:N], acc[N:2 * N], acc[2 * N:].view(N, C)
+        check(lib.oniris_gconv_bwd_fused(1, ops._p(g), ops._p(raw), ops._p(y3), ops._p(ca), ops._p(cb), ops._p(cs), None,
+                                         ops._p(dout), None, ops._p(dy3), ops._p(dca), ops._p(dcb), ops._p(dcs), B, T, P, C,
+                                         1.0, 1.0, 0.0, C, None, None, ops._stream()), "gconv_bwd_fused")
+        return [dout, dy3, dca, dcb, dcs]
+
+    for fn, k in ((emb_silu, 1), (fused, 4)):
+        runs = [fn() for _ in range(3)]
+        torch.cuda.synchronize()
+        got = runs[0][k].double()
+        err = ((got - want).norm() / want.norm()).item()
+        assert err < 1e-3, (fn.__name__, err)
+        for r in runs[1:]:
+            assert all(torch.equal(a, b) for a, b in zip(runs[0], r)), fn.__name__
