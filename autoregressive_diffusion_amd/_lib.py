@@ -40,7 +40,7 @@ class ConvArgs(C.Structure):
                 ("big_tile", c_int32), ("escale_pitch", c_int32),
                 ("splitk_ws", c_void_p), ("splitk_ws_bytes", C.c_size_t), ("clip_flag", c_void_p),
                 ("ctx_prod", c_void_p), ("ctx_prod_mode", c_int32), ("x_split", c_int32), ("x2", c_void_p), ("act_out", c_void_p),
-                ("cat_w1", c_float), ("cat_w2", c_float)]
+                ("cat_w1", c_float), ("cat_w2", c_float), ("ctx_rows", c_int32)]
 
 
 class WgradArgs(C.Structure):
@@ -148,6 +148,13 @@ _SIGS = {
                                 c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "oniris_precond_out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                    c_void_p]),
+    "oniris_qkv_eval_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "oniris_dart_input_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,
+                                       c_void_p]),
+    "oniris_precond_out_guided": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                          c_float, c_void_p]),
     "oniris_sampler_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float,
                                       c_void_p, c_int, c_float, c_void_p]),
     "oniris_embed_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -965,7 +965,8 @@ __global__ __launch_bounds__(256) void qkv_eval_kernel(const bf16* __restrict__ 
                                                        bf16* __restrict__ kr, const float* __restrict__ cos_t,
                                                        const float* __restrict__ sin_t, const float* __restrict__ scale_t,
                                                        long long M, int C, int CinP, long long kv_tpb, long long kv_bstride,
-                                                       long long kv_off, int pos) {
+                                                       long long kv_off, int pos, long long split, bf16* __restrict__ q2,
+                                                       bf16* __restrict__ k2, bf16* __restrict__ v2) {
   // K is staged KC input channels at a time (the whole K for C <= 256: every load of the tile is in flight at once -- the
   // launch is pure latency, ~10 us with four 64-channel rounds of load / barrier / multiply, half of that in one round)
   constexpr int ROWB = KC * 2 + 16;                          // + 16 bytes: conflict-free 16-byte fragment reads
@@ -1038,9 +1039,16 @@ __global__ __launch_bounds__(256) void qkv_eval_kernel(const bf16* __restrict__ 
   ss += __shfl_xor(ss, 32);
   const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
   if (tok >= M) return;
-  const long long dense = tok * C + hd * 64;
+  // tokens >= split: the 2-D rows of a guided pair launch (oniris_qkv_eval_pair) -- normalised, un-rotated q | k | v, dense
+  // [token - split][C] in the side buffers (what the frame form of this launch writes)
+  const bool side = tok >= split;
+  bf16* const qo = side ? q2 : q;
+  bf16* const ko = side ? k2 : k;
+  bf16* const vo = side ? v2 : v;
+  const bool rot_on = rope && !side;
+  const long long dense = (side ? tok - split : tok) * C + hd * 64;
   long long ring = dense;
-  if (kv_tpb > 0) {                                          // (one sequence: tok < kv_tpb, no 64-bit division on the way to the stores)
+  if (kv_tpb > 0 && !side) {                                          // (one sequence: tok < kv_tpb, no 64-bit division on the way to the stores)
     const long long sq = (tok < kv_tpb) ? 0 : tok / kv_tpb;
     ring = sq * kv_bstride + (kv_off + tok - sq * kv_tpb) * C + hd * 64;
   }
@@ -1054,7 +1062,7 @@ __global__ __launch_bounds__(256) void qkv_eval_kernel(const bf16* __restrict__ 
       const float u0 = bf2f(f2bf(f[0][i] * inv)), u1 = bf2f(f2bf(f[1][i] * inv));
       plain[0][kk] = f2bf(u0); plain[1][kk] = f2bf(u1);
       float v0 = u0, v1 = u1;
-      if (rope) {
+      if (rot_on) {
         v0 = u0 * tc0[i] - u1 * ts0[i];                       // rotate_half: [-x2, x1]
         v1 = u1 * tc1[i] + u0 * ts1[i];
         const float s0 = tq0[i], s1 = tq1[i];
@@ -1065,12 +1073,12 @@ __global__ __launch_bounds__(256) void qkv_eval_kernel(const bf16* __restrict__ 
     }
     const int co = 8 * g + 4 * h;
     if (s == 0) {
-      *(bf16x4*)(q + dense + co) = rot[0]; *(bf16x4*)(q + dense + co + 32) = rot[1];
+      *(bf16x4*)(qo + dense + co) = rot[0]; *(bf16x4*)(qo + dense + co + 32) = rot[1];
     } else if (s == 1) {
-      *(bf16x4*)(k + ring + co) = plain[0]; *(bf16x4*)(k + ring + co + 32) = plain[1];
-      if (kr) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
+      *(bf16x4*)(ko + ring + co) = plain[0]; *(bf16x4*)(ko + ring + co + 32) = plain[1];
+      if (kr && !side) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
     } else {
-      *(bf16x4*)(v + ring + co) = plain[0]; *(bf16x4*)(v + ring + co + 32) = plain[1];
+      *(bf16x4*)(vo + ring + co) = plain[0]; *(bf16x4*)(vo + ring + co + 32) = plain[1];
     }
   }
 }
@@ -1084,7 +1092,8 @@ __global__ __launch_bounds__(256) void qkv_eval_few_kernel(const bf16* __restric
                                                            bf16* __restrict__ kr, const float* __restrict__ cos_t,
                                                            const float* __restrict__ sin_t, const float* __restrict__ scale_t,
                                                            long long M, int C, int CinP, long long kv_tpb, long long kv_bstride,
-                                                           long long kv_off, int pos) {
+                                                           long long kv_off, int pos, long long split, bf16* __restrict__ q2,
+                                                           bf16* __restrict__ k2, bf16* __restrict__ v2) {
   __shared__ float red[3 * 2 * 16 * 64];           // waves 1..3 -> wave 0: [wave - 1][n-tile][accumulator register][lane]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
   const long long tok = (long long)blockIdx.x * 32 + r;
@@ -1158,9 +1167,16 @@ __global__ __launch_bounds__(256) void qkv_eval_few_kernel(const bf16* __restric
   ss += __shfl_xor(ss, 32);
   const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
   if (!tvalid) return;
-  const long long dense = tok * C + hd * 64;
+  // tokens >= split: the 2-D rows of a guided pair launch (oniris_qkv_eval_pair) -- normalised, un-rotated q | k | v, dense
+  // [token - split][C] in the side buffers (what the frame form of this launch writes)
+  const bool side = tok >= split;
+  bf16* const qo = side ? q2 : q;
+  bf16* const ko = side ? k2 : k;
+  bf16* const vo = side ? v2 : v;
+  const bool rot_on = rope && !side;
+  const long long dense = (side ? tok - split : tok) * C + hd * 64;
   long long ring = dense;
-  if (kv_tpb > 0) {
+  if (kv_tpb > 0 && !side) {
     const long long sq = (tok < kv_tpb) ? 0 : tok / kv_tpb;
     ring = sq * kv_bstride + (kv_off + tok - sq * kv_tpb) * C + hd * 64;
   }
@@ -1173,7 +1189,7 @@ __global__ __launch_bounds__(256) void qkv_eval_few_kernel(const bf16* __restric
       const float u0 = bf2f(f2bf(f[0][i] * inv)), u1 = bf2f(f2bf(f[1][i] * inv));
       plain[0][kk] = f2bf(u0); plain[1][kk] = f2bf(u1);
       float v0 = u0, v1 = u1;
-      if (rope) {
+      if (rot_on) {
         v0 = u0 * tc0[i] - u1 * ts0[i];
         v1 = u1 * tc1[i] + u0 * ts1[i];
         const float s0 = tq0[i], s1 = tq1[i];
@@ -1184,12 +1200,12 @@ __global__ __launch_bounds__(256) void qkv_eval_few_kernel(const bf16* __restric
     }
     const int co = 8 * g + 4 * h;
     if (s == 0) {
-      *(bf16x4*)(q + dense + co) = rot[0]; *(bf16x4*)(q + dense + co + 32) = rot[1];
+      *(bf16x4*)(qo + dense + co) = rot[0]; *(bf16x4*)(qo + dense + co + 32) = rot[1];
     } else if (s == 1) {
-      *(bf16x4*)(k + ring + co) = plain[0]; *(bf16x4*)(k + ring + co + 32) = plain[1];
-      if (kr) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
+      *(bf16x4*)(ko + ring + co) = plain[0]; *(bf16x4*)(ko + ring + co + 32) = plain[1];
+      if (kr && !side) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
     } else {
-      *(bf16x4*)(v + ring + co) = plain[0]; *(bf16x4*)(v + ring + co + 32) = plain[1];
+      *(bf16x4*)(vo + ring + co) = plain[0]; *(bf16x4*)(vo + ring + co + 32) = plain[1];
     }
   }
 }
@@ -1632,39 +1648,61 @@ extern "C" int oniris_qkv_norm_rope_eval(const void* qkv, void* q, void* k, void
   return ONIRIS_OK;
 }
 
-extern "C" int oniris_qkv_eval(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t,
-                               const float* sin_t, const float* scale_t, int64_t n_tokens, int C, int CinP,
-                               int64_t kv_tokens_per_batch, int64_t kv_batch_stride, int64_t kv_token_offset, int pos,
-                               oniris_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+static int qkv_eval_impl(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t, const float* sin_t,
+                         const float* scale_t, int64_t n_tokens, int C, int CinP, int64_t kv_tokens_per_batch,
+                         int64_t kv_batch_stride, int64_t kv_token_offset, int pos, int64_t split, void* q2, void* k2, void* v2,
+                         hipStream_t stream) {
   ONIRIS_CHECK_ARG(x && w && q && k && v && n_tokens > 0 && C > 0 && C % 64 == 0 && CinP >= C && CinP % 8 == 0 && pos >= 0,
                    "qkv_eval: bad arguments");
   ONIRIS_CHECK_ARG((cos_t && sin_t && scale_t) || (!cos_t && !sin_t && !scale_t && !kr), "qkv_eval: all rotary tables or none");
-  ONIRIS_CHECK_ARG(kv_tokens_per_batch == 0 || (kv_tokens_per_batch > 0 && n_tokens % kv_tokens_per_batch == 0 &&
+  ONIRIS_CHECK_ARG(kv_tokens_per_batch == 0 || (kv_tokens_per_batch > 0 && split % kv_tokens_per_batch == 0 &&
                                                 kv_batch_stride >= (kv_token_offset + kv_tokens_per_batch) * C),
                    "qkv_eval: bad KV ring geometry");
+  const char* tag = split < n_tokens ? "pair-rows" : nullptr;
   // a few tiles (one frame per sequence; at most one workgroup per CU): 32-token tiles, the four waves of a workgroup split the K
   // (qkv_eval_few_kernel; ONIRIS_QKV_EVAL_FEW=0 in the environment: off, A/B)
   static const int qkv_few = getenv("ONIRIS_QKV_EVAL_FEW") ? atoi(getenv("ONIRIS_QKV_EVAL_FEW")) : 1;
   if (qkv_few && ((n_tokens + 31) / 32) * (3LL * C / 64) <= 256) {
     const dim3 gf((unsigned)((n_tokens + 31) / 32), (unsigned)(C / 64), 3u);
-    ONIRIS_KLAUNCH(qkv_eval_few_kernel, gf, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (bf16*)q, (bf16*)k, (bf16*)v, (bf16*)kr,
-                   cos_t, sin_t, scale_t, (long long)n_tokens, C, CinP, (long long)kv_tokens_per_batch, (long long)kv_batch_stride,
-                   (long long)kv_token_offset, pos);
+    if (oniris_census_on) oniris_census_note((const void*)qkv_eval_few_kernel, tag);
+    hipLaunchKernelGGL(qkv_eval_few_kernel, gf, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (bf16*)q, (bf16*)k, (bf16*)v,
+                       (bf16*)kr, cos_t, sin_t, scale_t, (long long)n_tokens, C, CinP, (long long)kv_tokens_per_batch,
+                       (long long)kv_batch_stride, (long long)kv_token_offset, pos, (long long)split, (bf16*)q2, (bf16*)k2, (bf16*)v2);
     ONIRIS_LAUNCH_CHECK();
     return ONIRIS_OK;
   }
   const dim3 grid((unsigned)((n_tokens + 127) / 128), (unsigned)(C / 64), 3u);        // (x: token tile, y: head, z: q | k | v)
 #define QKV_EVAL_LAUNCH(KC_)                                                                                              \
-  ONIRIS_KLAUNCH(qkv_eval_kernel<KC_>, grid, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (bf16*)q, (bf16*)k,  \
-                     (bf16*)v, (bf16*)kr, cos_t, sin_t, scale_t, (long long)n_tokens, C, CinP,                             \
-                     (long long)kv_tokens_per_batch, (long long)kv_batch_stride, (long long)kv_token_offset, pos)
+  do {                                                                                                                    \
+    if (oniris_census_on) oniris_census_note((const void*)qkv_eval_kernel<KC_>, tag);                                     \
+    hipLaunchKernelGGL(qkv_eval_kernel<KC_>, grid, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (bf16*)q, (bf16*)k, \
+                       (bf16*)v, (bf16*)kr, cos_t, sin_t, scale_t, (long long)n_tokens, C, CinP,                          \
+                       (long long)kv_tokens_per_batch, (long long)kv_batch_stride, (long long)kv_token_offset, pos,       \
+                       (long long)split, (bf16*)q2, (bf16*)k2, (bf16*)v2);                                               \
+  } while (0)
   if (C % 256 == 0) QKV_EVAL_LAUNCH(256);
   else if (C % 128 == 0) QKV_EVAL_LAUNCH(128);
   else QKV_EVAL_LAUNCH(64);
 #undef QKV_EVAL_LAUNCH
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
+}
+
+extern "C" int oniris_qkv_eval(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t,
+                               const float* sin_t, const float* scale_t, int64_t n_tokens, int C, int CinP,
+                               int64_t kv_tokens_per_batch, int64_t kv_batch_stride, int64_t kv_token_offset, int pos,
+                               oniris_stream_t stream_) {
+  return qkv_eval_impl(x, w, q, k, v, kr, cos_t, sin_t, scale_t, n_tokens, C, CinP, kv_tokens_per_batch, kv_batch_stride,
+                       kv_token_offset, pos, n_tokens, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int oniris_qkv_eval_pair(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t,
+                                    const float* sin_t, const float* scale_t, int64_t n_tokens, int64_t split, int C, int CinP,
+                                    int64_t kv_tokens_per_batch, int64_t kv_batch_stride, int64_t kv_token_offset, int pos,
+                                    void* q2, void* k2, void* v2, oniris_stream_t stream_) {
+  ONIRIS_CHECK_ARG(split > 0 && split < n_tokens && q2 && k2 && v2, "qkv_eval_pair: need 0 < split < n_tokens and the side buffers");
+  return qkv_eval_impl(x, w, q, k, v, kr, cos_t, sin_t, scale_t, n_tokens, C, CinP, kv_tokens_per_batch, kv_batch_stride,
+                       kv_token_offset, pos, split, q2, k2, v2, (hipStream_t)stream_);
 }
 
 extern "C" int oniris_qkv_norm_rope_bwd(const void* qkv, const void* dq, const void* dk, const void* dv, void* dqkv,

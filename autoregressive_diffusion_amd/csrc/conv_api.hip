@@ -9,6 +9,13 @@ extern "C" int oniris_conv_fwd(const OnirisConvArgs* args, oniris_stream_t strea
     oniris_set_error("conv_fwd: ctx_prod_mode %d is for the one-frame cached evaluation (S == 1, context path, ctx_prod given)", a.ctx_prod_mode);
     return ONIRIS_EUNSUPPORTED;
   }
+  // (B == 2 * ctx_rows: every 2-D row b reads the emb-scale row b - ctx_rows of its 3-D twin, so escale holds ctx_rows rows)
+  if (a.ctx_rows != 0 && !(a.S == 1 && a.T == 1 && a.ctx && a.taps == 9 && a.ctx_rows > 0 && a.B == 2 * a.ctx_rows &&
+                           a.ctx_out == nullptr && a.ctx_prod_mode != 3)) {
+    oniris_set_error("conv_fwd: ctx_rows %d is for the one-frame cached evaluation of a guided pair (S = T = 1, context path, "
+                     "B = 2 * ctx_rows (got B = %d), no ctx_out, ctx_prod_mode != 3)", a.ctx_rows, a.B);
+    return ONIRIS_EUNSUPPORTED;
+  }
   ONIRIS_CHECK_ARG(a.taps == 9 || a.taps == 1, "conv_fwd: taps must be 1 or 9 (got %d)", a.taps);
   ONIRIS_CHECK_ARG(a.B > 0 && a.T > 0 && a.H > 0 && a.W > 0 && (a.S == 1 || a.S == 2), "conv_fwd: bad sizes");
   ONIRIS_CHECK_ARG(a.Cin % 8 == 0 && a.Cout % 8 == 0, "conv_fwd: Cin, Cout must be multiples of 8 (%d,%d)", a.Cin, a.Cout);

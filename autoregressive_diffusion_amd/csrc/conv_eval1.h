@@ -23,6 +23,8 @@
 // changes.  Mode 3 computes the product once per frame (context phases only, fp32 store), mode 2 reads it back and walks the
 // own phases only: a third of the phases and of the weight stream per evaluation.  The stored value is the fp32 sum the
 // epilogue would have formed itself, so mode 2 is bit-identical to the all-phases launch.
+// Guided pair (OnirisConvArgs.ctx_rows): a launch over 2B rows whose rows >= B are the 2-D evaluation of rows < B -- those
+// workgroups walk the own phases only (mode 4 above) and never touch the context pair, the kept product or the gate coefficients.
 // Requirements (conv_eval1_ok): S == 1, T == 1, context = the cached pair (ctx_T == 2, coff = 0 / 1), taps == 9,
 // Cin % 32 == 0, H % 8 == 0, W % 8 == 0.  Same results as the split-K path up to fp32 summation order.
 #pragma once
@@ -64,9 +66,12 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
   const int co0 = (int)blockIdx.x * CO, x0 = (int)blockIdx.y * 8;
   const int b = (int)blockIdx.z / d.nty, y0 = ((int)blockIdx.z - b * d.nty) * 8;
   // phases per 32-channel chunk: own | cached frame 0 | cached frame 1, or (ctx_prod_mode 2) the own one only, or (3) the two
-  // context ones only
-  const int mode = a.ctx_prod_mode;
-  const int phs = (mode == 2) ? 1 : (mode == 3) ? 2 : 3, ph0 = (mode == 3) ? 1 : 0;
+  // context ones only, or (mode 4: a 2-D row of a guided pair launch, OnirisConvArgs.ctx_rows) the own one only with no context
+  // at all -- y2 goes through the epilogue as it is (edm2/conv.py:60); uniform per workgroup (b comes from the grid)
+  const bool own_only = a.ctx_rows > 0 && b >= a.ctx_rows;
+  const int mode = own_only ? 4 : a.ctx_prod_mode;
+  const int eb = own_only ? b - a.ctx_rows : b;    // emb-scale row: the 2-D rows read the one of their 3-D twin
+  const int phs = (mode == 2 || mode == 4) ? 1 : (mode == 3) ? 2 : 3, ph0 = (mode == 3) ? 1 : 0;
   const int NP = (Cin / 32) * phs;
   // (mode 2) this thread's four context sums, requested now: nothing else of this wave is in flight yet, and the loader waves'
   // counted waits only ever leave YOUNGER requests outstanding
@@ -98,13 +103,13 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
           const uint2 t2_ = *(const uint2*)((const bf16*)a.res + o_);                                                           \
           epre0 = t2_.x; epre1 = t2_.y;                                                                                         \
         } else if (a.epi == ONIRIS_EPI_EMB_SILU) {                                                                              \
-          const float4 t4_ = *(const float4*)((const float*)a.escale + (size_t)b * (a.escale_pitch ? a.escale_pitch : a.Cout) + co0 + cq_); \
+          const float4 t4_ = *(const float4*)((const float*)a.escale + (size_t)eb * (a.escale_pitch ? a.escale_pitch : a.Cout) + co0 + cq_); \
           epre0 = __builtin_bit_cast(unsigned, t4_.x); epre1 = __builtin_bit_cast(unsigned, t4_.y);                             \
           epre2 = __builtin_bit_cast(unsigned, t4_.z); epre3 = __builtin_bit_cast(unsigned, t4_.w);                             \
         }                                                                                                                       \
       }                                                                                                                         \
-      if (a.coef_own) cown_pre = a.coef_own[b];                                                                                 \
-      if (a.coef_ctx) cctx_pre = a.coef_ctx[b];                                                                                 \
+      if (a.coef_own && mode != 4) cown_pre = a.coef_own[b];                                                                    \
+      if (a.coef_ctx && mode != 4) cctx_pre = a.coef_ctx[b];                                                                    \
     }                                                                                                                           \
   } while (0)
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
     const int frame_bytes = HWp * Cin * 2;
     const int wbytes = 9 * a.CoutP * a.CinP * 2;
     const i32x4 rs_x = make_rsrc((const bf16*)a.x + (size_t)b * HWp * Cin, frame_bytes);
-    const i32x4 rs_c = make_rsrc((const bf16*)a.ctx + (size_t)b * a.ctx_bstride * HWp * Cin, 2 * frame_bytes);
+    const i32x4 rs_c = make_rsrc((const bf16*)a.ctx + (size_t)(own_only ? 0 : b) * a.ctx_bstride * HWp * Cin, 2 * frame_bytes);
     const i32x4 rs_wo = make_rsrc(a.w_own, wbytes), rs_wc = make_rsrc(a.w_ctx, 2 * wbytes);
     auto issue = [&](int p) __attribute__((always_inline)) {
       const int ch = p / phs, ph = ph0 + p - phs * ch, c0 = ch * 32;
@@ -314,7 +319,7 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
       const int n = b;                             // frame-slot index (S == 1, T == 1)
       const size_t o = ((size_t)n * HWp + (size_t)(y0 + py) * W + (x0 + px)) * a.Cout + co;
       if (mode == 2) { ctx[0] = y3v.x; ctx[1] = y3v.y; ctx[2] = y3v.z; ctx[3] = y3v.w; }
-      else if (mode != 0) *(float4*)(a.ctx_prod + o) = make_float4(ctx[0], ctx[1], ctx[2], ctx[3]);
+      else if (mode == 1 || mode == 3) *(float4*)(a.ctx_prod + o) = make_float4(ctx[0], ctx[1], ctx[2], ctx[3]);
       if (mode == 3) return;
       const float cown = cown_pre, cctx = cctx_pre;
       float v[4];
@@ -384,7 +389,8 @@ static int launch_conv_eval1_co(const OnirisConvArgs& a, hipStream_t stream) {
   d.ntx = a.W / 8; d.nty = a.H / 8; d.ntt = 1;
   const long long nz = (long long)d.nty * a.B;
   if (d.ncob <= 0 || d.ntx <= 0 || d.ntx > 65535 || nz <= 0 || nz > 65535) { oniris_set_error("conv_fwd: bad grid %d x %d x %lld", d.ncob, d.ntx, nz); return ONIRIS_EINVAL; }
-  oniris_launch(conv_eval1_kernel<CO>, dim3((unsigned)d.ncob, (unsigned)d.ntx, (unsigned)nz), dim3(512), stream, d);
+  oniris_launch_tagged(a.ctx_rows > 0 ? "pair-rows" : nullptr, conv_eval1_kernel<CO>, dim3((unsigned)d.ncob, (unsigned)d.ntx, (unsigned)nz),
+                       dim3(512), stream, d);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }

@@ -515,10 +515,12 @@ extern "C" int oniris_resample_filter(const void* in, void* out, const void* add
 //   dart_loss_bwd: dF (bf16, zero for the clean slots) and per-frame partial sums of d out_gain
 __global__ __launch_bounds__(256) void dart_input_kernel(const float* __restrict__ img, const float* __restrict__ noise,
                                                          const float* __restrict__ sigma, bf16* __restrict__ xcl, int S,
-                                                         int T, int C, int HW, float sd, float* __restrict__ c_noise_out, int cpad) {
-  const int n = blockIdx.y, b = n / (S * T), st = n % (S * T), t = st % T;
+                                                         int T, int C, int HW, float sd, float* __restrict__ c_noise_out, int cpad,
+                                                         int nsrc) {
+  // (nsrc < gridDim.y: oniris_dart_input_pair -- output slot n packs source slot n % nsrc, c_noise is written once per source slot)
+  const int n = blockIdx.y, m = n % nsrc, b = m / (S * T), st = m % (S * T), t = st % T;
   const float sg = sigma[b * S * T + st];
-  if (c_noise_out && blockIdx.x == 0 && threadIdx.x == 0) c_noise_out[n] = logf(sg) / 4.f;     // c_noise (networks_edm2.py:291)
+  if (c_noise_out && n < nsrc && blockIdx.x == 0 && threadIdx.x == 0) c_noise_out[n] = logf(sg) / 4.f;     // c_noise (networks_edm2.py:291)
   const float cin = 1.f / sqrtf(sd * sd + sg * sg);
   const float* ip = img + (size_t)(b * T + t) * C * HW;
   const bool has_noise = noise != nullptr;        // NULL: no noise term (Precond's input side in eval)
@@ -601,7 +603,22 @@ extern "C" int oniris_dart_input(const float* images, const float* noise, const 
   int gx = cdiv(HW, 256);
   if (gx > 64) gx = 64;
   ONIRIS_KLAUNCH(dart_input_kernel, dim3(gx, B * S * T), dim3(256), 0, stream, images, noise, sigma, (bf16*)xcl, S, T, C,
-                     HW, sigma_data, c_noise_out, cpad);
+                     HW, sigma_data, c_noise_out, cpad, B * S * T);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+extern "C" int oniris_dart_input_pair(const float* x, const float* sigma, void* xcl, int B, int T, int C, int H, int W,
+                                      float sigma_data, float* c_noise_out, int cpad, oniris_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ONIRIS_CHECK_ARG(x && sigma && xcl && B > 0 && T > 0 && C > 0 && C < 16 && H > 0 && W > 0, "dart_input_pair: bad arguments");
+  ONIRIS_CHECK_ARG(cpad >= 16 && cpad % 8 == 0 && cpad <= 64, "dart_input_pair: cpad must be 16 ... 64 and a multiple of 8 (got %d)", cpad);
+  const int HW = H * W;
+  int gx = cdiv(HW, 256);
+  if (gx > 64) gx = 64;
+  if (oniris_census_on) oniris_census_note((const void*)dart_input_kernel, "pair-rows");
+  hipLaunchKernelGGL(dart_input_kernel, dim3(gx, 2 * B * T), dim3(256), 0, stream, x, (const float*)nullptr, sigma, (bf16*)xcl, 1, T,
+                     C, HW, sigma_data, c_noise_out, cpad, B * T);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }
@@ -707,6 +724,43 @@ __global__ __launch_bounds__(256) void precond_out_kernel(const bf16* __restrict
         D[o] = cskip * x[o] + cout * bf2f(f[c]);
       }
   }
+}
+
+// ... of a guided pair evaluation (edm2/sampler.py:25-32 of the reference): F holds 2N frames, [0, N) the cached 3-D evaluation and
+// [N, 2N) the 2-D one of the same x; D = lerp(D_2d, D_3d, guidance) in torch.lerp's form (ATen Lerp.h: weight below 0.5 in magnitude
+// from the start point, else from the end point)
+__global__ __launch_bounds__(256) void precond_out_guided_kernel(const bf16* __restrict__ F, const float* __restrict__ x,
+                                                                 const float* __restrict__ sigma, const float* __restrict__ out_gain,
+                                                                 float* __restrict__ D, int N, int C, int HW, float sd, float g) {
+  const int n = blockIdx.y;
+  const float sg = sigma[n], og = out_gain[0];
+  const float den = sg * sg + sd * sd;
+  const float cskip = sd * sd / den, cout = sg * sd / sqrtf(den) * og;
+  const bool small = fabsf(g) < 0.5f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+    const bf16x8 f3 = *(const bf16x8*)(F + ((size_t)n * HW + p) * 8);
+    const bf16x8 f2 = *(const bf16x8*)(F + ((size_t)(N + n) * HW + p) * 8);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < C) {
+        const size_t o = ((size_t)n * C + c) * HW + p;
+        const float xs = cskip * x[o];
+        const float d3 = xs + cout * bf2f(f3[c]), d2 = xs + cout * bf2f(f2[c]);
+        D[o] = small ? d2 + g * (d3 - d2) : d3 - (d3 - d2) * (1.f - g);
+      }
+  }
+}
+
+extern "C" int oniris_precond_out_guided(const void* F, const float* x, const float* sigma, const float* out_gain, float* D, int N,
+                                         int C, int H, int W, float sigma_data, float guidance, oniris_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ONIRIS_CHECK_ARG(F && x && sigma && out_gain && D && N > 0 && C > 0 && C <= 8 && H > 0 && W > 0, "precond_out_guided: bad arguments");
+  int gx = cdiv(H * W, 256);
+  if (gx > 64) gx = 64;
+  ONIRIS_KLAUNCH(precond_out_guided_kernel, dim3(gx, N), dim3(256), 0, stream, (const bf16*)F, x, sigma, out_gain, D, N, C, H * W,
+                 sigma_data, guidance);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
 }
 
 extern "C" int oniris_precond_out(const void* F, const float* x, const float* sigma, const float* out_gain, float* D,

@@ -57,8 +57,9 @@ class VideoAttention(_AttentionBase):
         self.rope = RotaryEmbedding(channels // num_heads)
         self.train_mask = None
 
-    def _cl(self, x, batch_size, cache=None, update_cache=False, just_2d=False, clip=0.0):
-        """x (B*t, H, W, C) bf16 -> (mp_sum(x, attention(x)) [clipped], cache)."""
+    def _cl(self, x, batch_size, cache=None, update_cache=False, just_2d=False, clip=0.0, pair=False):
+        """x (B*t, H, W, C) bf16 -> (mp_sum(x, attention(x)) [clipped], cache).  pair (guided pair evaluation, eval): x is
+        (2B, H, W, C), rows >= B the 2-D evaluation of rows < B; the KV ring receives the rows < B only."""
         if self.num_heads == 0:
             return (x.clamp(-clip, clip) if clip > 0 else x), None
         if just_2d:
@@ -67,6 +68,11 @@ class VideoAttention(_AttentionBase):
         P = H * W
         self.__dict__["_tokens_per_frame"] = P               # (UNet.prewarm_eval sizes the next RoPE table from it)
         rope_bufs = (self.rope.inv_freq, self.rope.scale)
+        if pair:
+            assert not self.training and not torch.is_grad_enabled() and x.is_cuda
+            o, cache = ops.attention_eval_x_pair(x, self.attn_qkv.weight.pw, batch_size, self.num_heads, rope_bufs, cache,
+                                                 update_cache, P)
+            return self._proj(x, o.reshape(N, H, W, C), clip), cache
         if not self.training and not torch.is_grad_enabled() and x.is_cuda:
             o, cache = ops.attention_eval_x(x, self.attn_qkv.weight.pw, batch_size, self.num_heads, rope_bufs, cache,
                                             update_cache, P)

@@ -235,9 +235,14 @@ class MPCausal3DGatedConv(nn.Module):
     def _cl(self, x, batch_size, c_noise, cache=None, update_cache=False, just_2d=False, **epi):
         """x (B*t, H, W, C) bf16 -> (y, cache).  cache['activations'] is (B, 2, H, W, C) bf16.
         **epi: fused epilogue, either cscale=(N,Cout) fp32 [silu(y*cscale)/0.596] or res/ta/tb/clip [mp_sum+clip];
-        grad_private (training, see ops.ConvCfg): the output's gradient will be a tensor only this op's backward reads."""
+        grad_private (training, see ops.ConvCfg): the output's gradient will be a tensor only this op's backward reads;
+        pair (guided pair evaluation, UNet._forward(_pair=True), eval, one generated frame): x is (2B, H, W, C), rows [0, B) the
+        cached evaluation, rows [B, 2B) the 2-D evaluation of the same input (own-frame product, no gate, no context: conv.py:60;
+        OnirisConvArgs.ctx_rows) -- gates, cscale and the cache entry belong to rows < B, which leave exactly what the B-row
+        cached evaluation leaves."""
         grad_private = epi.pop("grad_private", False)
         slot_kw = dict(res_slot=epi.pop("res_slot", None), res_alias=epi.pop("res_alias", False))
+        pair = epi.pop("pair", False)
         if just_2d:
             self.__dict__.pop("_gate_pre", None)
             train_kw = dict(grad_private=grad_private, **slot_kw) if self.training else {}
@@ -255,9 +260,12 @@ class MPCausal3DGatedConv(nn.Module):
         N, H, W, C = x.shape
         pw2, pw3 = self.last_frame_conv.weight.pw, self.weight.pw
         if self.training:
+            assert not pair
             T = N // (2 * batch_size)
             return ops.gated_conv_train(x, gate, pw2, pw3, batch_size, T, coefs, grad_private=grad_private, **slot_kw, **epi), cache
-        t = N // batch_size
+        xc = x[:batch_size] if pair else x                    # the rows the cache entry is built from
+        t = xc.shape[0] // batch_size
+        assert not pair or (N == 2 * batch_size and t == 1), (N, batch_size)
         pad = cache.get("activations")
         had_pair = pad is not None
         if pad is None:
@@ -267,9 +275,9 @@ class MPCausal3DGatedConv(nn.Module):
                 # captured evaluation of the sampler's frame graph: the shifted pair is built once, after the frame's last
                 # replay (sampler.finish_cache), from the old pair and this layer's input -- not by every replay
                 cache["activations"] = pad
-                cache["_pending_frame"] = x.reshape(batch_size, 1, H, W, C)
+                cache["_pending_frame"] = xc.reshape(batch_size, 1, H, W, C)
             elif update_cache:
-                cache["activations"] = torch.cat([pad[:, 1:], x.reshape(batch_size, 1, H, W, C)], dim=1)
+                cache["activations"] = torch.cat([pad[:, 1:], xc.reshape(batch_size, 1, H, W, C)], dim=1)
             # The context product of the cached pair is the same in every evaluation against that pair (the sampler runs 31
             # per generated frame, sampler.py:50-76; the reference's F.conv3d recomputes it each time, conv.py:84-86): kept
             # in the cache entry beside the pair it belongs to -- computed by UNet.prewarm_eval or by the first evaluation,
@@ -285,7 +293,9 @@ class MPCausal3DGatedConv(nn.Module):
                 y3 = torch.empty((batch_size, H, W, ops.roundup(pw2.cout, 8)), dtype=torch.float32, device=x.device)
                 cache["_ctx_product"] = (y3, pad, wsig)
                 epi = dict(epi, ctx_prod=y3, ctx_prod_mode=1)
-            return ops.gated_conv_eval(x, gate, pw2, pw3, batch_size, 1, pad.contiguous(), coefs, ctx_T=2, **epi), cache
+            if pair:            # one launch over both halves where the one-frame kernel serves the shape (ops.pair_conv_ok)
+                epi = dict(epi, ctx_rows=batch_size)
+            return ops.gated_conv_eval(x, gate, pw2, pw3, N, 1, pad.contiguous(), coefs, ctx_T=2, **epi), cache
         ctx = torch.cat([pad, x.reshape(batch_size, t, H, W, C)], dim=1).contiguous()
         if update_cache:
             cache["activations"] = ctx[:, -2:].clone()

@@ -47,7 +47,7 @@ class Block(nn.Module):
     __getstate__ = strip_runtime_state
 
     def _cl(self, x, emb, batch_size, c_noise, cache=None, update_cache=False, just_2d=False, skip=None, cat_w=None,
-            c=None, in_slot=None, skip_slot=None, private_out=False):
+            c=None, in_slot=None, skip_slot=None, private_out=False, pair=False):
         """x (N,H,W,C) bf16, emb (N,1,1,cemb) bf16; skip/cat_w: the decoder's mp_cat operand, fused into the first
         activation kernel.  private_out: the caller consumes the block's output through ops of this package that join all of
         its gradients in one kernel (UNet.forward with GradSlots) -- see ops.ConvCfg.grad_private.  Elementwise chains of the reference's Block.forward (:62-94) run as fused HIP kernels:
@@ -88,8 +88,9 @@ class Block(nn.Module):
         N = x.shape[0]
         if c is None:          # (the UNet hands in all of its blocks' scales from one grouped GEMM: ops.emb_scales)
             c = (self.emb_linear._cl(emb).reshape(N, -1).float() * self.emb_gain + 1)      # (N, Cout) fp32
+        pk = dict(pair=True) if pair else {}       # (guided pair evaluation: UNet._forward(_pair=True))
         y, cache["conv_res0"] = self.conv_res0._cl(a, batch_size, c_noise, cache.get("conv_res0"), update_cache,
-                                                   just_2d, cscale=c)    # y = mp_silu(conv(a) * c)
+                                                   just_2d, cscale=c, **pk)    # y = mp_silu(conv(a) * c)
         if self.training and self.dropout != 0:
             y = F.dropout(y, p=self.dropout)
         if self.flavor == "dec" and self.conv_skip is not None and not skip_conv_done:
@@ -100,10 +101,13 @@ class Block(nn.Module):
         x, cache["conv_res1"] = self.conv_res1._cl(y, batch_size, c_noise, cache.get("conv_res1"), update_cache, just_2d,
                                                    res=x, ta=(1 - t) * den, tb=t * den,
                                                    clip=clip if self.num_heads == 0 else 0.0,
-                                                   grad_private=private_out,
+                                                   grad_private=private_out, **pk,
                                                    **(dict(res_slot=xs, res_alias=True) if xs is not None else {}))
         if self.num_heads > 0:
-            x, cache["attn"] = self.attn._cl(x, batch_size, cache.get("attn"), update_cache, just_2d, clip=clip)
+            if pair and isinstance(self.attn, VideoAttention):
+                x, cache["attn"] = self.attn._cl(x, batch_size, cache.get("attn"), update_cache, just_2d, clip=clip, pair=True)
+            else:
+                x, cache["attn"] = self.attn._cl(x, batch_size, cache.get("attn"), update_cache, just_2d, clip=clip)
         else:
             cache["attn"] = None
         return x, cache
@@ -187,19 +191,25 @@ class UNet(BetterModule):
 
     _oniris_cl_io = True        # forward(..., _cl_io=(B, tt)) takes / returns channels-last bf16 (edm2/loss.py fast path)
 
-    def forward(self, x, c_noise, conditioning=None, cache=None, update_cache=False, just_2d=False, _cl_io=None):
+    def forward(self, x, c_noise, conditioning=None, cache=None, update_cache=False, just_2d=False, _cl_io=None, _pair=False):
         inner = self._ddp_inner()          # torch DistributedDataParallel around this net (utils.BetterModule)
         if inner is None:
-            return self._forward(x, c_noise, conditioning, cache, update_cache, just_2d, _cl_io)
+            return self._forward(x, c_noise, conditioning, cache, update_cache, just_2d, _cl_io, _pair)
         inner.inner_pre_forward()
-        out = self._forward(x, c_noise, conditioning, cache, update_cache, just_2d, _cl_io)
+        out = self._forward(x, c_noise, conditioning, cache, update_cache, just_2d, _cl_io, _pair)
         inner.inner_post_forward(out)
         return out
 
-    def _forward(self, x, c_noise, conditioning=None, cache=None, update_cache=False, just_2d=False, _cl_io=None):
+    def _forward(self, x, c_noise, conditioning=None, cache=None, update_cache=False, just_2d=False, _cl_io=None, _pair=False):
         """_cl_io = (B, tt): `x` is already the packed UNet input (B*tt, H, W, ops.IN_PAD) bf16 with the ones channel
         (ops.dart_input) and the raw channels-last output (B*tt, H, W, 8k) bf16 is returned WITHOUT out_gain -- the
-        fused DART loss applies it (ops.dart_loss).  Default: the reference signature (:191)."""
+        fused DART loss applies it (ops.dart_loss).  Default: the reference signature (:191).
+        _pair (with _cl_io = (B, 1), eval, see pair_ok): `x` holds 2B rows (ops.dart_input_pair) -- ONE evaluation whose rows
+        [0, B) are the cached evaluation against `cache` and rows [B, 2B) the just_2d evaluation of the same input (the two
+        calls of the reference's guided sampler, edm2/sampler.py:25-32); embedding, gates and the cache come from / go to the
+        B cached rows only, the raw output has 2B rows."""
+        if _pair:
+            assert _cl_io is not None and _cl_io[1] == 1 and not just_2d and not self.training and not torch.is_grad_enabled()
         if _fp32.active():
             if _cl_io is not None:
                 raise RuntimeError("the packed bf16 input / output form of UNet.forward does not exist in the fp32 path")
@@ -249,6 +259,7 @@ class UNet(BetterModule):
                 gains = eb[1][:] = [b.emb_gain for b in blocks]
             cs = dict(zip(map(id, blocks), ops.emb_scales(emb, self.__dict__["_oniris_groups"][0], gains)))
             skips = []
+            pk = dict(pair=True) if _pair else {}
             # one GradSlot per encoder output (training): it is read by the next block AND by a decoder block (skip)
             use_slots = torch.is_grad_enabled() and self.training and ops.GRAD_SLOTS
             slot = None
@@ -256,9 +267,9 @@ class UNet(BetterModule):
             for name, block in self.enc.items():
                 if isinstance(block, Block):
                     xcl, cache["enc", name] = block._cl(xcl, emb, B, c_noise, cache.get(("enc", name)), update_cache, just_2d,
-                                                        c=cs[id(block)], in_slot=slot, private_out=bool(use_slots))
+                                                        c=cs[id(block)], in_slot=slot, private_out=bool(use_slots), **pk)
                 else:
-                    xcl, cache["enc", name] = block._cl(xcl, B, c_noise, cache.get(("enc", name)), update_cache, just_2d)
+                    xcl, cache["enc", name] = block._cl(xcl, B, c_noise, cache.get(("enc", name)), update_cache, just_2d, **pk)
                 # (an output of a frozen encoder prefix carries no gradient: nobody would take what the decoder parks for it)
                 slot = ops.GradSlot() if (use_slots and xcl.requires_grad) else None
                 skips.append((xcl, slot))
@@ -275,17 +286,24 @@ class UNet(BetterModule):
                 # (the last encoder output enters the decoder as its main input: `slot` is still that tensor's slot)
                 xcl, cache["dec", name] = block._cl(xcl, emb, B, c_noise, cache.get(("dec", name)), update_cache, just_2d,
                                                     skip=skip, cat_w=cat_w, c=cs[id(block)], in_slot=slot, skip_slot=skip_slot,
-                                                    private_out=bool(use_slots))
+                                                    private_out=bool(use_slots), **pk)
                 slot = None
                 cb = stage_hooks.get(("dec", name))
                 if cb is not None and xcl.requires_grad:
                     xcl.register_hook(cb)
-            xcl, cache["out_conv"] = self.out_conv._cl(xcl, B, c_noise, cache.get("out_conv"), update_cache, just_2d)
+            xcl, cache["out_conv"] = self.out_conv._cl(xcl, B, c_noise, cache.get("out_conv"), update_cache, just_2d, **pk)
             if _cl_io is not None:
                 return xcl, cache
             out = from_cl(xcl[..., :self.img_channels], torch.float32)
             out = out.reshape(B, tt, *out.shape[1:]) * self.out_gain
             return out, cache
+
+    def pair_ok(self):
+        """Does the guided pair evaluation (_forward(_pair=True)) serve this net?  The bf16 path with every VideoAttention layer on
+        64-channel heads (the KV-ring path); padded / wider heads and the fp32 mode keep the two-call formulation."""
+        if _fp32.active():
+            return False
+        return all(m.num_heads == 0 or m.channels == 64 * m.num_heads for m in self.modules() if isinstance(m, VideoAttention))
 
     def _emb_blocks(self):
         return [b for b in list(self.enc.values()) + list(self.dec.values()) if isinstance(b, Block)]
@@ -481,16 +499,43 @@ class Precond(BetterModule):
         core = getattr(self.unet, "module", self.unet)
         return core._ddp_fused_parameters() if hasattr(core, "_ddp_fused_parameters") else []
 
-    def forward(self, x, sigma, conditioning=None, force_fp32=False, cache=None, update_cache=False, just_2d=False):
+    def forward(self, x, sigma, conditioning=None, force_fp32=False, cache=None, update_cache=False, just_2d=False, _guidance=None):
         inner = self._ddp_inner()          # torch DistributedDataParallel around the Precond itself
         if inner is None:
-            return self._forward(x, sigma, conditioning, force_fp32, cache, update_cache, just_2d)
+            return self._forward(x, sigma, conditioning, force_fp32, cache, update_cache, just_2d, _guidance)
         inner.inner_pre_forward()
-        out = self._forward(x, sigma, conditioning, force_fp32, cache, update_cache, just_2d)
+        out = self._forward(x, sigma, conditioning, force_fp32, cache, update_cache, just_2d, _guidance)
         inner.inner_post_forward(out)
         return out
 
-    def _forward(self, x, sigma, conditioning=None, force_fp32=False, cache=None, update_cache=False, just_2d=False):
+    def pair_served(self, x=None, force_fp32=False):
+        """True when a guided evaluation (_guidance) of this net runs as ONE pair evaluation (UNet.pair_ok, bf16 eval path)."""
+        core = unwrap_ddp(self.unet)
+        if force_fp32 or not self.use_fp16 or not getattr(core, "_oniris_cl_io", False):
+            return False
+        if not (hasattr(core, "pair_ok") and hasattr(core, "prewarm_eval") and core.pair_ok()):
+            return False
+        return x is None or (x.is_cuda and x.is_contiguous() and x.shape[1] == 1 and x.shape[2] <= 8
+                             and getattr(core, "img_channels", -1) == x.shape[2])
+
+    def _forward(self, x, sigma, conditioning=None, force_fp32=False, cache=None, update_cache=False, just_2d=False, _guidance=None):
+        if _guidance is not None and not just_2d:
+            # guided evaluation (reference edm2/sampler.py:25-32): lerp(net(x, just_2d=True), net(x, cache), guidance) -- ONE
+            # evaluation over 2B rows where pair_served, else the reference's two calls
+            if cache is None:
+                cache = {}
+            if not torch.is_grad_enabled() and self.pair_served(x, force_fp32) and sigma.shape == x.shape[:2]:
+                cache["shape"] = x.shape
+                core = unwrap_ddp(self.unet)
+                x = x.to(torch.float32)
+                sg = sigma.to(torch.float32).contiguous()
+                xcl, c_noise = ops.dart_input_pair(x, sg, self.sigma_data)
+                Fcl, cache = self.unet.forward(xcl, c_noise, conditioning, cache, update_cache, False, _cl_io=tuple(x.shape[:2]),
+                                               _pair=True)
+                return ops.precond_out_guided(Fcl, x, sg, core.out_gain, self.sigma_data, _guidance), cache
+            D, cache = self._forward(x, sigma, conditioning, force_fp32, cache, update_cache, False)
+            ref, _ = self._forward(x, sigma, conditioning, force_fp32, None, False, True)
+            return ref.lerp(D, _guidance), cache
         if cache is None:
             cache = {}
         cache["shape"] = x.shape

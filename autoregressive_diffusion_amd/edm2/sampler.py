@@ -22,8 +22,11 @@ class _GraphedDenoiser:
     evaluation without their host cost.  The last evaluation of the frame updates the cache and stays eager.  A new graph per
     frame: the KV length and the cache tensors change with every frame."""
 
-    def __init__(self, net, cache, conditioning, B, dtype, device):
+    def __init__(self, net, cache, conditioning, B, dtype, device, guidance=1):
         self.net, self.cache, self.cond = net, cache, conditioning
+        # guidance != 1: every evaluation is the guided PAIR (Precond(_guidance=): the cached and the 2-D evaluation of x as
+        # one evaluation over 2B rows, lerp in the output pass) -- captured and replayed like the unguided one
+        self.kw = {} if guidance == 1 else {"_guidance": guidance}
         self.t = torch.ones(B, 1, device=device, dtype=dtype)
         self.x, self.out, self.graph, self.calls = None, None, None, 0
 
@@ -35,7 +38,7 @@ class _GraphedDenoiser:
             if hasattr(unet, "prewarm_eval"):                      # tables for this frame count, built outside the capture
                 unet.prewarm_eval(self.cache)
             else:                                                  # unknown net: one eager evaluation builds them
-                Dx, _ = self.net(x, self.t * t, self.cond, cache=self.cache, update_cache=False, just_2d=False)
+                Dx, _ = self.net(x, self.t * t, self.cond, cache=self.cache, update_cache=False, just_2d=False, **self.kw)
                 return Dx
         self.t.fill_(1.0).mul_(t)
         if self.graph is None:
@@ -47,7 +50,7 @@ class _GraphedDenoiser:
             side.wait_stream(cur)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, stream=side):
-                self.out, _ = self.net(self.x, self.t, self.cond, cache=self.cache, update_cache=False, just_2d=False)
+                self.out, _ = self.net(self.x, self.t, self.cond, cache=self.cache, update_cache=False, just_2d=False, **self.kw)
             self.graph, self.side = g, side
         else:
             self.x.copy_(x)
@@ -109,7 +112,7 @@ class _GraphedDenoiser:
                     g.capture_begin(pool=pool)
                     try:
                         self.out, self.new_cache = self.net(self.x, self.t, self.cond, cache=shadow, update_cache=True,
-                                                            just_2d=False)
+                                                            just_2d=False, **self.kw)
                     finally:
                         g.capture_end()
             finally:
@@ -158,7 +161,8 @@ def _t_steps(num_steps, sigma_min, sigma_max, rho, dtype, device):
 
 
 def _fused_frame(net, graphed, cache, conditioning, t_steps, x0, B, num_steps):
-    """The frame loop of edm_sampler_with_mse for the common case (no churn, no guidance, no target, fp32, CUDA): same
+    """The frame loop of edm_sampler_with_mse for the common case (no churn, no target, fp32, CUDA; guidance through the pair
+    evaluation): same
     arithmetic in the same order (reference sampler.py:56-76), but every evaluation is a graph replay whose x / sigma inputs
     were written in place by the previous update kernel -- per evaluation ONE replay + ONE small launch instead of ~10 torch
     launches (fill, mul, copy, clone, sub, div, mul, add ... on a 128 KB tensor, each ~5 us of a 1.6 ms evaluation)."""
@@ -200,15 +204,20 @@ def edm_sampler_with_mse(net, cache, target=None, gnet=None, conditioning=None, 
     if hasattr(unet, "prewarm_eval") and torch.device(device).type == "cuda":
         unet.prewarm_eval(cache)
 
+    # guidance != 1 on a net that evaluates the guided PAIR (Precond.pair_served: the cached and the 2-D evaluation of x as
+    # one evaluation over 2B rows): the same graphed / fused paths as guidance == 1, one net call per evaluation
+    pair = (guidance != 1 and torch.device(device).type == "cuda" and hasattr(net, "pair_served") and net.pair_served())
     graphed = None
-    if (SAMPLER_GRAPH and guidance == 1 and torch.device(device).type == "cuda" and dtype == torch.float32
+    if (SAMPLER_GRAPH and (guidance == 1 or pair) and torch.device(device).type == "cuda" and dtype == torch.float32
             and num_steps >= 4):
-        graphed = _GraphedDenoiser(net, cache, conditioning, B, dtype, device)
+        graphed = _GraphedDenoiser(net, cache, conditioning, B, dtype, device, guidance)
 
     def denoise(x, t, cache, update_cache):
         if graphed is not None and not update_cache:
             return graphed(x, t), cache
         t = torch.ones(B, 1, device=device, dtype=dtype) * t
+        if pair:
+            return net(x, t, conditioning, cache=cache, update_cache=update_cache, just_2d=False, _guidance=guidance)
         Dx, cache = net(x, t, conditioning, cache=cache, update_cache=update_cache, just_2d=False)
         if guidance == 1:
             return Dx, cache

@@ -624,7 +624,7 @@ CLIP_FLAG = int(_os.environ.get("ONIRIS_CLIP_FLAG", "1"))    # 0: the mp_sum bac
 def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, Cin, CinP, Cout, CoutP, taps,
                  ctx_bstride=0, ctx_T=0, coff=(0, 0), ctx_fill=0.0, epi=0, res=None, escale=None, emb_gain=None,
                  out2=None, ta=0.0, tb=0.0, clip=0.0, ctx_out=None, clip_flag=None, ctx_prod=None, ctx_prod_mode=0,
-                 x2=None, act_out=None, x_split=0, cat_w=(1.0, 1.0)):
+                 x2=None, act_out=None, x_split=0, cat_w=(1.0, 1.0), ctx_rows=0):
     if KernelProfile.enabled:
         flops = 2.0 * B * S * T * H * W * Cout * Cin * taps
         if ctx is not None:
@@ -657,7 +657,8 @@ def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, C
         try:
             e0, e1 = _timed_launch(lambda: _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, Cin, CinP,
                                                         Cout, CoutP, taps, ctx_bstride, ctx_T, coff, ctx_fill, epi, res, escale,
-                                                        emb_gain, out2, ta, tb, clip, ctx_out, clip_flag, ctx_prod, ctx_prod_mode))
+                                                        emb_gain, out2, ta, tb, clip, ctx_out, clip_flag, ctx_prod, ctx_prod_mode,
+                                                        ctx_rows=ctx_rows))
         finally:
             KernelProfile.enabled = True
         # algorithmic HBM bytes of the launch (every operand read once, every result written once; the context
@@ -685,7 +686,8 @@ def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, C
     if x2 is not None:
         a.x2, a.act_out, a.x_split, a.cat_w1, a.cat_w2 = _p(x2), _p(act_out), x_split, cat_w[0], cat_w[1]
     a.big_tile = BIG_TILE
-    if SPLITK and B * S * T * H * W <= 64 * 256 and ctx_prod_mode == 0:      # few tiles (one rollout frame): lend the split-K workspace
+    a.ctx_rows = ctx_rows
+    if SPLITK and B * S * T * H * W <= 64 * 256 and ctx_prod_mode == 0 and ctx_rows == 0:      # few tiles (one rollout frame): lend the split-K workspace
         ws = _splitk_workspace(x.device)
         a.splitk_ws, a.splitk_ws_bytes = _p(ws), ws.numel() * 4
     check(lib.oniris_conv_fwd(ctypes.byref(a), _stream()), "conv_fwd")
@@ -1093,12 +1095,27 @@ def gated_conv_ctx_product(pair, pw2, pw3, B, out=None):
     return y3
 
 
+def pair_conv_ok(x, pw2):
+    """True when the one-frame kernel (csrc/conv_eval1.h) serves a guided pair launch over the rows of x (OnirisConvArgs.ctx_rows;
+    mirrors conv_dispatch_s1ctx / conv_eval1_ok); otherwise gated_conv_eval issues the two halves as two launches."""
+    N, H, W, Cin = x.shape
+    Co = roundup(pw2.cout, 8)
+    return bool(BIG_TILE >= 3 and not (BIG_TILE & 16) and Cin % 32 == 0 and Cin >= 32 and H % 8 == 0 and W % 8 == 0
+                and Co % 8 == 0 and 2 * H * W * Cin * 2 < (1 << 31) and (H // 8) * N <= 65535 and W // 8 <= 65535)
+
+
 @torch.no_grad()
 def gated_conv_eval(x, gate, pw2, pw3, B, t, ctx_frames, coefs=None, res=None, ta=0.0, tb=0.0, clip=0.0, cscale=None,
-                    ctx_T=None, ctx_prod=None, ctx_prod_mode=0):
+                    ctx_T=None, ctx_prod=None, ctx_prod_mode=0, ctx_rows=0):
     """Eval-mode gated conv: x (B*t,H,W,C); ctx_frames (B, ctx_T, H, W, C) = [2 cached frames, x frames] (ctx_T = t+2),
     or just the 2 cached frames when t == 1 (output frame 0 reads context frames 0 and 1 only).  ctx_prod (t == 1 only):
-    the kept context product of that pair, written (mode 1) or read instead of being recomputed (mode 2)."""
+    the kept context product of that pair, written (mode 1) or read instead of being recomputed (mode 2).
+    ctx_rows (guided pair, t == 1): x holds B = 2 * ctx_rows rows, rows >= ctx_rows are the 2-D evaluation of rows < ctx_rows
+    (own-frame taps, no gate, no context: edm2/conv.py:60); ctx_frames, the gate coefficients, cscale and ctx_prod hold the
+    ctx_rows rows of the cached half.  One launch where the one-frame kernel serves the shape (pair_conv_ok), else two."""
+    if ctx_rows:
+        return _gated_conv_eval_pair(x, gate, pw2, pw3, B, ctx_frames, coefs, res, ta, tb, clip, cscale, ctx_T, ctx_prod,
+                                     ctx_prod_mode, ctx_rows)
     ctx_T = t + 2 if ctx_T is None else ctx_T
     assert ctx_frames.shape[1] == ctx_T and (ctx_T == t + 2 or t == 1)
     N, H, W, Cin = x.shape
@@ -1117,6 +1134,44 @@ def gated_conv_eval(x, gate, pw2, pw3, B, t, ctx_frames, coefs=None, res=None, t
         kw.update(ctx_prod=ctx_prod, ctx_prod_mode=ctx_prod_mode)
     _conv_launch(x, ctx_frames, pw2.wf, pw3.wf, out, ca, cb, B, 1, t, H, W, Cin, pw2.CinP, Co, pw2.CoutP, 9,
                  ctx_bstride=ctx_T, ctx_T=ctx_T, coff=(0, 1), ctx_fill=0.0, **kw)
+    return ret
+
+
+def _gated_conv_eval_pair(x, gate, pw2, pw3, B, ctx_frames, coefs, res, ta, tb, clip, cscale, ctx_T, ctx_prod, ctx_prod_mode,
+                          ctx_rows):
+    ctx_T = 2 if ctx_T is None else ctx_T
+    N, H, W, Cin = x.shape
+    R = ctx_rows
+    assert N == B == 2 * R and ctx_T == 2 and ctx_frames.shape[:2] == (R, 2), (x.shape, B, R, ctx_frames.shape)
+    Co = roundup(pw2.cout, 8)
+    out = torch.empty((N, H, W, Co), dtype=BF16, device=x.device)
+    ca, cb = coefs if coefs is not None else gate_coefs(gate)
+    ca, cb = ca.float().contiguous(), cb.float().contiguous()
+    assert ca.numel() == R and cb.numel() == R
+    ret, cs = out, None
+    if res is None and cscale is not None:
+        ret = torch.empty_like(out)
+        cs = _rows_f32(cscale)
+        assert tuple(cs.shape) == (R, Co), (cs.shape, R, Co)
+    if ctx_prod_mode:
+        assert ctx_prod.dtype == torch.float32 and tuple(ctx_prod.shape) == (R, H, W, Co) and ctx_prod.is_contiguous()
+
+    def epi(rows):
+        if res is not None:
+            return dict(epi=_lib.EPI_MPSUM, res=res[rows], ta=ta, tb=tb, clip=clip)
+        if cscale is not None:
+            return dict(epi=_lib.EPI_EMB_SILU, escale=cs, out2=ret[rows])
+        return {}
+    pk = dict(ctx_prod=ctx_prod, ctx_prod_mode=ctx_prod_mode) if ctx_prod_mode else {}
+    if pair_conv_ok(x, pw2):
+        _conv_launch(x, ctx_frames, pw2.wf, pw3.wf, out, ca, cb, N, 1, 1, H, W, Cin, pw2.CinP, Co, pw2.CoutP, 9,
+                     ctx_bstride=2, ctx_T=2, coff=(0, 1), ctx_fill=0.0, ctx_rows=R, **epi(slice(None)), **pk)
+        return ret
+    # shapes the one-frame kernel does not take (e.g. 16-channel levels): the cached half, then the 2-D half as the plain
+    # own-frame conv just_2d runs (MPCausal3DGatedConv._cl)
+    _conv_launch(x[:R], ctx_frames, pw2.wf, pw3.wf, out[:R], ca, cb, R, 1, 1, H, W, Cin, pw2.CinP, Co, pw2.CoutP, 9,
+                 ctx_bstride=2, ctx_T=2, coff=(0, 1), ctx_fill=0.0, **epi(slice(0, R)), **pk)
+    _conv_launch(x[R:], None, pw2.wf, None, out[R:], None, None, 1, 1, R, H, W, Cin, pw2.CinP, Co, pw2.CoutP, 9, **epi(slice(R, N)))
     return ret
 
 
@@ -2091,6 +2146,46 @@ def attention_eval_x(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P):
 
 
 @torch.no_grad()
+def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P):
+    """attention_eval_x of a guided pair evaluation: x (2B, H, W, C), rows [0, B) the cached 3-D evaluation of one new frame
+    per sequence, rows [B, 2B) the 2-D evaluation of the same input (attention_modules.py:36-45: dense attention inside the
+    frame on normalised q | k | v, no RoPE, no KV cache).  -> (out (2B, P, C), cache of the 3-D rows).  With a prepared KV ring:
+    ONE qkv launch for both halves (oniris_qkv_eval_pair), the decode over the ring for rows < B and the frame attention of
+    frame_attention_eval for rows >= B -- three launches.  Otherwise the two halves as attention_eval_x and
+    frame_attention_eval."""
+    N, C = x.shape[0], x.shape[-1]
+    assert N == 2 * B, (N, B)
+    dev = x.device
+    ring = KVRing.of(kv_cache, B, P, C, 1, dev) if (FUSED_QKV_EVAL and C == 64 * heads and pw.cout == 3 * C) else None
+    if ring is None or ring.kr_state != (ring.n, ring.n + 1):
+        o3, new_cache = attention_eval_x(x[:B], pw, B, heads, rope_bufs, kv_cache, update_cache, P)
+        o2 = frame_attention_eval(x[B:], pw, heads)
+        return torch.cat([o3.reshape(B, P, C), o2.reshape(B, P, C)]), new_cache
+    n, nk = ring.n, ring.n + 1
+    bstride = ring.cap * P * C
+    q = torch.empty((B, P, C), dtype=BF16, device=dev)
+    q2, k2, v2 = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    cs_, sn_, sc_ = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
+    xc = x.contiguous()
+    check(lib.oniris_qkv_eval_pair(_p(xc), _p(pw.wf), _p(q), _p(ring.K), _p(ring.V), _p(ring.KR), _p(cs_), _p(sn_), _p(sc_), N * P,
+                                   B * P, C, pw.CinP, P, bstride, n * P, n, _p(q2), _p(k2), _p(v2), _stream()), "qkv_eval_pair")
+    if update_cache:
+        ring.n = nk
+        new_cache = ring.views()
+    else:
+        new_cache = kv_cache
+    out = torch.empty((N, P, C), dtype=BF16, device=dev)
+    a = _attn_args(q, ring.KR, ring.V, None, None, None, out[:B], None, None, B, heads, P, nk * P, C, 0, P, 0)
+    a.v_bstride = a.k_bstride = bstride
+    _decode_splits(a, B, heads, P, nk * P, dev)
+    check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
+    lse = torch.empty((B, heads, P), dtype=torch.float32, device=dev)
+    a2 = _attn_args(q2, k2, v2, None, None, None, out[B:], lse, None, B, heads, P, P, C, 0, P, 1)
+    check(lib.oniris_attn_fwd(ctypes.byref(a2), _stream()), "attn_fwd")
+    return out, new_cache
+
+
+@torch.no_grad()
 def frame_attention_eval(x, pw, heads):
     """FrameAttention without autograd (attention_modules.py:105-119) from the layer input: qkv convolution + normalisation
     in one launch, dense attention inside every frame."""
@@ -2236,6 +2331,34 @@ def dart_input(images, noise, sigma, S, sigma_data, want_c_noise=False):
     check(lib.oniris_dart_input(_p(images), _p(noise), _p(sigma), _p(xcl), B, S, T, C, H, W, float(sigma_data), _p(cn), IN_PAD,
                                 _stream()), "dart_input")
     return (xcl, cn) if want_c_noise else xcl
+
+
+def dart_input_pair(x, sigma, sigma_data):
+    """Packed UNet input of a guided pair evaluation (oniris_dart_input_pair): x (B,t,C,H,W) fp32, sigma (B,t) -> ((2*B*t, H, W,
+    IN_PAD) bf16 = c_in * x with the ones channel, rows [B*t, 2*B*t) a copy of rows [0, B*t) for the 2-D half; c_noise (B,t))."""
+    _need_gpu(x, sigma)
+    B, T, C, H, W = x.shape
+    xcl = torch.empty((2 * B * T, H, W, IN_PAD), dtype=BF16, device=x.device)
+    cn = torch.empty((B, T), dtype=torch.float32, device=x.device)
+    check(lib.oniris_dart_input_pair(_p(x), _p(sigma), _p(xcl), B, T, C, H, W, float(sigma_data), _p(cn), IN_PAD, _stream()),
+          "dart_input_pair")
+    return xcl, cn
+
+
+@torch.no_grad()
+def precond_out_guided(F, x, sigma, out_gain, sigma_data, guidance):
+    """D = lerp(D_2d, D_3d, guidance) from the raw output F (2*B*t, H, W, 8) bf16 of a guided pair evaluation (rows [0, B*t) the
+    cached 3-D half, the rest the 2-D half), each D_i = c_skip * x + c_out * out_gain * F_i as precond_out forms it; torch.lerp's
+    formula (reference edm2/sampler.py:32).  x (B,t,C,H,W) fp32, sigma (B,t) -> D like x.  One launch."""
+    _need_gpu(F, x, sigma)
+    B, t, C, H, W = x.shape
+    assert (F.dtype == BF16 and F.shape == (2 * B * t, H, W, 8) and F.is_contiguous() and x.dtype == torch.float32
+            and x.is_contiguous())
+    D = torch.empty_like(x)
+    og = out_gain.detach().float().reshape(1)
+    check(lib.oniris_precond_out_guided(_p(F), _p(x), _p(sigma.float().contiguous()), _p(og), _p(D), B * t, C, H, W,
+                                        float(sigma_data), float(guidance), _stream()), "precond_out_guided")
+    return D
 
 
 @torch.no_grad()

@@ -25,7 +25,8 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
+int oniris_abi_version(void);   /* 14.  Added within 14 (guided sampling, nothing existing changed): OnirisConvArgs.ctx_rows (appended field),
+                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
 /* Measurement aid: arm a pair of HIP events (hipEvent_t created with timing); the next MFMA conv / weight-gradient /
@@ -145,6 +146,15 @@ int oniris_loss_tail(const float* mse, const float* sigma, const float* coef, fl
  *   outputs the gate coefficients ca, cb [L][N] of mp_sum(y2, y3, g) (utils.py:118-123).                              */
 int oniris_precond_out(const void* F, const float* x, const float* sigma, const float* out_gain, float* D, int N, int C,
                        int H, int W, float sigma_data, oniris_stream_t stream);
+/* Guided pair evaluation (reference edm2/sampler.py:25-32: D = lerp(net(x, just_2d=True), net(x, cache), guidance)) as ONE UNet
+ * evaluation over 2N frames, [0, N) the cached 3-D rows, [N, 2N) the 2-D rows of the same input:
+ * oniris_dart_input_pair: xcl [2N][H][W][cpad] = both halves packed from x [N][C][H][W] (N = B*T), c_noise_out [N] (may be NULL);
+ * oniris_precond_out_guided: D [N][C][H][W] = lerp(D_2d, D_3d, guidance) with D_i = c_skip * x + c_out * out_gain * F_i, F the raw
+ *   output [2N][H][W][8] of the pair; torch.lerp's formula in fp32.                                                  */
+int oniris_dart_input_pair(const float* x, const float* sigma, void* xcl, int B, int T, int C, int H, int W, float sigma_data,
+                           float* c_noise_out, int cpad, oniris_stream_t stream);
+int oniris_precond_out_guided(const void* F, const float* x, const float* sigma, const float* out_gain, float* D, int N, int C,
+                              int H, int W, float sigma_data, float guidance, oniris_stream_t stream);
 /* oniris_sampler_update: the Euler / Heun update between two UNet evaluations of edm_sampler_with_mse (reference
  *   edm2/sampler.py:66-76), one fp32 launch over n elements:
  *   mode 0: d = (x_hat - x_pred) / t_a; x_out = x_hat + dt * d; d_io <- d
@@ -284,6 +294,13 @@ typedef struct OnirisConvArgs {
   const void* x2;
   void* act_out;
   float cat_w1, cat_w2;
+  /* Optional (guided sampling; the one-frame cached evaluation only, csrc/conv_eval1.h): a launch over B == 2 * ctx_rows rows
+   * (S == T == 1) whose rows b >= ctx_rows are the 2-D evaluation of row b - ctx_rows's input (edm2/conv.py:60 just_2d): they
+   * run the own-frame taps only, read neither ctx nor ctx_prod nor coef_own / coef_ctx, write no ctx_prod, and their epilogue is
+   * applied to y2 itself, with the emb-scale row b - ctx_rows.  ctx, ctx_prod, coef_own, coef_ctx and escale hold ctx_rows rows;
+   * x, out, out2 and res hold B.  0: off (every row is a cached row).  Any other B, and a launch with ctx_rows > 0 that the
+   * one-frame kernel cannot serve, fail with ONIRIS_EUNSUPPORTED.                                                          */
+  int32_t ctx_rows;
 } OnirisConvArgs;
 
 int oniris_conv_fwd(const OnirisConvArgs* args /* [host] */, oniris_stream_t stream);
@@ -450,6 +467,13 @@ int oniris_qkv_norm_rope_eval(const void* qkv, void* q, void* k, void* v, void* 
 int oniris_qkv_eval(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t, const float* sin_t,
                     const float* scale_t, int64_t n_tokens, int C, int CinP, int64_t kv_tokens_per_batch,
                     int64_t kv_batch_stride, int64_t kv_token_offset, int pos, oniris_stream_t stream);
+/* oniris_qkv_eval_pair: oniris_qkv_eval over the tokens of a guided pair evaluation in ONE launch -- tokens [0, split) as
+ * oniris_qkv_eval writes them (ring geometry relative to token 0), tokens [split, n_tokens) (the 2-D rows) normalised and
+ * un-rotated into the dense side buffers q2 / k2 / v2 [n_tokens - split][C] (the frame form: tables off, kr untouched).   */
+int oniris_qkv_eval_pair(const void* x, const void* w, void* q, void* k, void* v, void* kr, const float* cos_t, const float* sin_t,
+                         const float* scale_t, int64_t n_tokens, int64_t split, int C, int CinP, int64_t kv_tokens_per_batch,
+                         int64_t kv_batch_stride, int64_t kv_token_offset, int pos, void* q2, void* k2, void* v2,
+                         oniris_stream_t stream);
 
 /* Block-sparse flash attention forward (replaces compiled_flex_attention / F.scaled_dot_product_attention,
  * attention_modules.py:41,66,70,75,115).  q [B][Lq][C], k,v [B][Lk][C] bf16 (head h = channels 64h..64h+63),
