@@ -176,6 +176,15 @@ _SIGS = {
                                      c_void_p]),
     "oniris_attn_bwd_dq": (c_int, [C.POINTER(AttnArgs), c_void_p]),
     "oniris_attn_bwd_dkv": (c_int, [C.POINTER(AttnArgs), c_void_p]),
+    "oniris_vae_temb": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "oniris_vae_up": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "oniris_vae_res_a": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_void_p]),
+    "oniris_vae_res_b": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p]),
+    "oniris_vae_out": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
 }
 EXPORTED = sorted(_SIGS)
 

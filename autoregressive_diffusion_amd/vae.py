@@ -1,0 +1,297 @@
+"""VAE decoder on HIP kernels: generated latents -> RGB frames on the GPU (reference: edm2/vae/vae.py).
+
+`VAE` has the reference's constructor, `kwargs` and state_dict keys (encoder and decoder), so a checkpoint of the reference's
+VAE loads here unchanged and round-trips.  Only the decoder runs, for inference, in fp32 like the reference: `decode`,
+`latents_to_frames` and the streaming form `decode_frames`.  The decoder is causal in time -- every group-causal conv keeps
+the last g activated frames of its input as a cache (vae.py:18-53) -- so decoding one latent frame at a time through the
+cache gives exactly what decoding the whole sequence gives (bit-identical here: csrc/vae.hip sums every output in a fixed
+order).  Activations are channels-last fp32 [B][T][H][W][C]; per decoder block one `up` launch, two per ResBlock, one `out`
+launch, plus one t-embedding launch per decode (include/oniris.h: oniris_vae_*).
+
+The encoder, `forward` and `frames_to_latents` are not implemented here: use the reference's `edm2.vae`.
+"""
+import ctypes
+import inspect
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from .edm2.utils import BetterModule, MPFourier
+
+MAX_WIDTH = 64
+_REF = "the reference's edm2.vae (this package implements the decoder only)"
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _nch(c):
+    """Channel capacity of the res-conv kernel instantiation that serves c channels: 8, 16, 32 or 64."""
+    return next(n for n in (8, 16, 32, 64) if c <= n)
+
+
+def _gpt(c, g):
+    """Output frames per thread of res A: the largest power of two that divides g with nch * gpt <= 32 (csrc/vae.hip)."""
+    gpt = 1
+    while gpt * 2 <= 4 and g % (gpt * 2) == 0 and _nch(c) * gpt * 2 <= 32:
+        gpt *= 2
+    return gpt
+
+
+class GroupCausal3DConvVAE(nn.Module):
+    """Parameter holder with the reference's layout (vae.py:18-34): conv3d (C g, C, 2g, 3, 3), stride g in time."""
+
+    def __init__(self, in_channels, out_channels, kernel, group_size):
+        super().__init__()
+        self.out_channels, self.group_size = out_channels, group_size
+        self.conv3d = nn.Conv3d(in_channels, out_channels * group_size, kernel, stride=(group_size, 1, 1), bias=True)
+        with torch.no_grad():
+            w = self.conv3d.weight
+            w[:, :, :-group_size] = 0
+            self.conv3d.weight.copy_(w * 32 ** -.25)
+        self.register_buffer("group_size_tensor", torch.tensor(group_size), persistent=False)
+
+
+class ResBlock(nn.Module):
+    """vae.py:56-93 (parameters only; the computation is oniris_vae_res_a / oniris_vae_res_b)."""
+
+    def __init__(self, channels, kernel, group_size=1, t_cond=False):
+        super().__init__()
+        self.conv3d0 = GroupCausal3DConvVAE(channels, channels, kernel, group_size)
+        self.conv3d1 = nn.Conv3d(channels, channels, kernel_size=(1, 3, 3), padding=(0, 1, 1))
+        nn.init.zeros_(self.conv3d1.weight)
+        nn.init.zeros_(self.conv3d1.bias)
+        if t_cond:
+            self.fourier_cond = MPFourier(channels * 2)
+            self.t_cond = nn.Linear(channels * 2, channels * 2)
+            nn.init.zeros_(self.t_cond.weight)
+            nn.init.zeros_(self.t_cond.bias)
+
+
+class EncoderDecoderBlock(nn.Module):
+    """vae.py:96-133 (parameters only)."""
+
+    def __init__(self, in_channels, out_channels, time_compression, spatial_compression, kernel, group_size, n_res_blocks,
+                 type="encoder"):
+        super().__init__()
+        self.time_compression, self.spatial_compression = int(time_compression), int(spatial_compression)
+        total = self.time_compression * self.spatial_compression ** 2
+        dec = type == "decoder"
+        self.decompression_block = nn.Conv3d(in_channels, in_channels * total, kernel_size=(1, 1, 1)) if dec else None
+        self.compression_block = None if dec else nn.Conv3d(in_channels * total, out_channels, kernel_size=(1, 1, 1))
+        self.res_blocks = nn.ModuleList([ResBlock(in_channels if dec else out_channels, kernel, group_size, t_cond=dec)
+                                         for _ in range(n_res_blocks)])
+        self.final_conv = nn.Conv3d(in_channels, out_channels, kernel_size=(1, 1, 1)) if dec else None
+
+
+class EncoderDecoder(nn.Module):
+    """vae.py:167-204 (parameters only): the decoder reverses `channels`, doubles its last entry (mean | logvar) and keeps the
+    group sizes cumprod(time_compressions) in order."""
+
+    def __init__(self, channels, n_res_blocks, time_compressions, spatial_compressions, type):
+        super().__init__()
+        assert type in ["encoder", "decoder"], "Invalid type, expected encoder or decoder"
+        assert len(channels) - 1 == len(time_compressions) == len(spatial_compressions)
+        self.time_compressions, self.spatial_compressions, self.encoding_type = time_compressions, spatial_compressions, type
+        channels = list(channels)
+        group_sizes = np.cumprod(time_compressions)
+        if type == "encoder":
+            group_sizes = group_sizes[::-1]
+        else:
+            channels = channels[::-1]
+            self.logvar_multiplier = nn.Parameter(torch.tensor(-2.))
+            channels[-1] = channels[-1] * 2
+        self.in_channels, self.out_channels = channels[:-1], channels[1:]
+        self.group_sizes = [int(g) for g in group_sizes]
+        self.encoder_blocks = nn.ModuleList([
+            EncoderDecoderBlock(self.in_channels[i], self.out_channels[i], time_compressions[i], spatial_compressions[i],
+                                (self.group_sizes[i] * 2, 3, 3), self.group_sizes[i], n_res_blocks, type)
+            for i in range(len(group_sizes))])
+
+
+class VAE(BetterModule):
+    """The reference's VAE (vae.py:207-318) with its decoder on HIP kernels.  Supported: every decoder width <= 64, time and
+    spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises NotImplementedError
+    here (the Counter-Strike VAE, 512 channels, is out of scope)."""
+
+    def __init__(self, channels, n_res_blocks, time_compressions=[1, 2, 2], spatial_compressions=[1, 2, 2], mean=None, std=None):
+        super().__init__()
+        if len(channels) - 1 != len(time_compressions) or len(channels) - 1 != len(spatial_compressions) or len(channels) < 2:
+            raise ValueError("VAE: len(channels) - 1 must equal the number of time and spatial compressions")
+        widths = list(channels[::-1][:-1])
+        if max(widths) > MAX_WIDTH or min(widths) < 1:
+            raise NotImplementedError(f"VAE decoder: block widths {widths}: the HIP kernels take 1..{MAX_WIDTH} channels")
+        if any(int(c) not in (1, 2) for c in list(time_compressions) + list(spatial_compressions)):
+            raise NotImplementedError(f"VAE decoder: compressions {list(time_compressions)} / {list(spatial_compressions)}: "
+                                      "the HIP kernels take 1 or 2")
+        self.latent_channels = channels[-1]
+        self.encoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="encoder")
+        self.decoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="decoder")
+        self.time_compression = np.prod(time_compressions)
+        self.spatial_compression = np.prod(spatial_compressions)
+        if mean is not None:
+            self.register_buffer("mean", torch.tensor(mean), persistent=False)
+            self.register_buffer("std", torch.tensor(std), persistent=False)
+        frame = inspect.currentframe()
+        args, _, _, values = inspect.getargvalues(frame)
+        self.kwargs = {arg: values[arg] for arg in args if arg != "self"}
+
+    # ---- not implemented here
+    def forward(self, x, t=0.1, cache=None):
+        raise NotImplementedError(f"VAE.forward (encode + decode, training): use {_REF}")
+
+    def encode(self, x, cache=None):
+        raise NotImplementedError(f"VAE.encode: use {_REF}")
+
+    def encode_long_sequence(self, frames, cache=None, split_size=256):
+        raise NotImplementedError(f"VAE.encode_long_sequence: use {_REF}")
+
+    def frames_to_latents(self, frames):
+        raise NotImplementedError(f"VAE.frames_to_latents: use {_REF}")
+
+    # ---- packed device weights
+    def _pack(self, device):
+        """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip, rebuilt when a parameter changed."""
+        params = list(self.decoder.parameters()) + list(self.decoder.buffers())
+        sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        pk = self.__dict__.get("_oniris_vae_pack")
+        if pk is not None and pk["sig"] == sig:
+            return pk
+        f32 = dict(device=device, dtype=torch.float32)
+        blocks, tparams, table, eoff = [], [], [], 0
+        with torch.no_grad():
+            for i, blk in enumerate(self.decoder.encoder_blocks):
+                C, Cout, g = self.decoder.in_channels[i], self.decoder.out_channels[i], self.decoder.group_sizes[i]
+                nch, gpt = _nch(C), _gpt(C, g)
+                res = []
+                for rb in blk.res_blocks:
+                    w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gq gpt + gl
+                    w = w.reshape(C, g // gpt, gpt, C, 2 * g, 3, 3).permute(1, 4, 5, 6, 3, 0, 2)   # gq, kt, ky, kx, ci, c, gl
+                    wa = torch.zeros(g // gpt, 2 * g, 3, 3, C, nch, gpt, **f32)
+                    wa[:, :, :, :, :, :C] = w
+                    ba = torch.zeros(g // gpt, nch, gpt, **f32)
+                    ba[:, :C] = rb.conv3d0.conv3d.bias.detach().to(**f32).reshape(C, g // gpt, gpt).permute(1, 0, 2)
+                    wb = torch.zeros(3, 3, C, nch, **f32)
+                    wb[..., :C] = rb.conv3d1.weight.detach().to(**f32)[:, :, 0].permute(2, 3, 1, 0)   # ky, kx, ci, co
+                    bb = torch.zeros(nch, **f32)
+                    bb[:C] = rb.conv3d1.bias.detach().to(**f32)
+                    res.append(dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb, emb_off=eoff))
+                    off = sum(x.numel() for x in tparams)
+                    tparams += [rb.fourier_cond.freqs.detach().to(**f32), rb.fourier_cond.phases.detach().to(**f32),
+                                rb.t_cond.weight.detach().to(**f32).reshape(-1), rb.t_cond.bias.detach().to(**f32)]
+                    table += [off, 2 * C, eoff]
+                    eoff += 2 * C
+                blocks.append(dict(C=C, Cout=Cout, g=g, nch=nch, gpt=gpt, tc=blk.time_compression, sc=blk.spatial_compression,
+                                   wu=blk.decompression_block.weight.detach().to(**f32).reshape(-1, C).contiguous(),
+                                   bu=blk.decompression_block.bias.detach().to(**f32).contiguous(),
+                                   wo=blk.final_conv.weight.detach().to(**f32).reshape(Cout, C).contiguous(),
+                                   bo=blk.final_conv.bias.detach().to(**f32).contiguous(), res=res))
+            pk = dict(sig=sig, blocks=blocks, tparams=torch.cat(tparams).contiguous(),
+                      table=torch.tensor(table, dtype=torch.int32, device=device), n_rb=len(table) // 3, emb_per_row=eoff,
+                      lvm=self.decoder.logvar_multiplier.detach().to(**f32).reshape(1).contiguous())
+        self.__dict__["_oniris_vae_pack"] = pk
+        return pk
+
+    # ---- the decoder
+    def _run(self, x, strides, t, cache, in_affine=False, want="moments"):
+        """x: latents addressed by element strides (b, t, h, w, c); returns ((mean, logvar) | frames, cache)."""
+        B, T, h, w_ = x.shape[0], x.shape[1 if want == "frames" else 2], x.shape[-2], x.shape[-1]
+        dev = x.device
+        if dev.type != "cuda":
+            raise RuntimeError("VAE decoder: the latents must be on the GPU (the decoder runs on HIP kernels only)")
+        pk = self._pack(dev)
+        s = _stream()
+        t = torch.as_tensor(t, dtype=torch.float32, device=dev)
+        t = (t.expand(B) if t.dim() == 0 else t.reshape(B)).contiguous()
+        emb = torch.empty(B * pk["emb_per_row"], dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), B, _p(emb), s), "vae_temb")
+        cache = {} if cache is None else cache
+        new_cache = {}
+        scale = shift = None
+        if in_affine:
+            if not hasattr(self, "mean"):
+                raise RuntimeError("VAE: latents_to_frames needs the `mean` / `std` constructor arguments (as in the reference)")
+            scale = self.std.to(device=dev, dtype=torch.float32).contiguous()
+            shift = self.mean.to(device=dev, dtype=torch.float32).contiguous()
+        H, W = h, w_
+        nblk = len(pk["blocks"])
+        for i, bk in enumerate(pk["blocks"]):
+            C, g, tc, sc = bk["C"], bk["g"], bk["tc"], bk["sc"]
+            up = torch.empty(B, T * tc, H * sc, W * sc, C, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]),
+                                              tc, sc, _p(up), s), "vae_up")
+            x, T, H, W = up, T * tc, H * sc, W * sc
+            scale = shift = None
+            bc = cache.get(f"encoder_block_{i}", {})
+            nbc = new_cache[f"encoder_block_{i}"] = {}
+            for j, rb in enumerate(bk["res"]):
+                cin = bc.get(f"res_block_{j}", {}).get("conv3d_res0")
+                if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != dev or cin.dtype != torch.float32):
+                    raise ValueError(f"VAE decoder cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
+                                     f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
+                cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=dev)
+                u = torch.empty_like(x)
+                _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb.data_ptr() + 4 * B * rb["emb_off"],
+                                                     _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g, bk["nch"], bk["gpt"], _p(u), s),
+                           "vae_res_a")
+                xn = torch.empty_like(x)
+                _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
+                           "vae_res_b")
+                x = xn
+                nbc[f"res_block_{j}"] = {"conv3d_res0": cout}
+            Cout = bk["Cout"]
+            if i < nblk - 1:
+                y = torch.empty(B, T, H, W, Cout, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, 0, None, _p(y), None,
+                                                   *y.stride()[:4], 1, None, s), "vae_out")
+                x = y
+                strides = y.stride()[:4] + (1,)
+                continue
+            half = Cout // 2
+            if want == "frames":
+                frames = torch.empty(B, T, H, W, half, dtype=torch.uint8, device=dev)
+                _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]),
+                                                   None, None, 0, 0, 0, 0, 0, _p(frames), s), "vae_out")
+                return frames, new_cache
+            mean = torch.empty(B, half, T, H, W, dtype=torch.float32, device=dev)
+            logvar = torch.empty_like(mean)
+            sb, scc, st, sh, sw = mean.stride()
+            _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]),
+                                               _p(mean), _p(logvar), sb, st, sh, sw, scc, None, s), "vae_out")
+            return (mean, logvar), new_cache
+
+    @torch.no_grad()
+    def decode(self, z, t, cache=None):
+        """z (B, C, T, h, w) -> (mean, logvar, cache), mean / logvar (B, 3, 4T, 4h, 4w) (vae.py:253-255).  The cache holds, under
+        the reference's keys cache['encoder_block_{i}']['res_block_{j}']['conv3d_res0'], the last g activated input frames of
+        every group-causal conv as opaque channels-last (B, g, H, W, C) fp32 tensors; pass it back to continue the sequence."""
+        if z.dim() != 5 or z.shape[1] != self.latent_channels:
+            raise ValueError(f"VAE.decode: z must be (B, {self.latent_channels}, T, h, w), got {tuple(z.shape)}")
+        z = z.float()
+        sb, sc, st, sh, sw = z.stride()
+        (mean, logvar), cache = self._run(z, (sb, st, sh, sw, sc), t, cache)
+        return mean, logvar, cache
+
+    @torch.no_grad()
+    def decode_frames(self, latents, t=0.1, cache=None):
+        """Streaming latents_to_frames: latents (B, t, C, h, w) (normalised, as the sampler returns them) -> (frames (B, 4t, H, W, 3)
+        uint8 on the device, cache).  Feed the returned cache to the next call: frame by frame, the result equals
+        latents_to_frames over the whole sequence."""
+        if latents.dim() != 5 or latents.shape[2] != self.latent_channels:
+            raise ValueError(f"VAE.decode_frames: latents must be (B, t, {self.latent_channels}, h, w), got {tuple(latents.shape)}")
+        latents = latents.float()
+        sb, st, sc, sh, sw = latents.stride()
+        return self._run(latents, (sb, st, sh, sw, sc), t, cache, in_affine=True, want="frames")
+
+    @torch.no_grad()
+    def latents_to_frames(self, latents, t=0.1):
+        """latents (B, T, C, h, w) -> numpy int array (B, 4T, H, W, 3) = clip((mean + 1) 127.5, 0, 255) truncated (vae.py:288-318)."""
+        frames, _ = self.decode_frames(latents, t)
+        return frames.cpu().numpy().astype(int)

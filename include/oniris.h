@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (guided sampling, nothing existing changed): OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
@@ -598,6 +598,40 @@ typedef struct OnirisAttnF32Args {
 } OnirisAttnF32Args;
 int oniris_attn_f32_fwd(const OnirisAttnF32Args* args, oniris_stream_t stream);
 int oniris_attn_f32_bwd(const OnirisAttnF32Args* args, oniris_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * VAE decoder (reference: edm2/vae/vae.py EncoderDecoder(type='decoder') :167-204 and VAE.decode / latents_to_frames
+ * :253-318), inference, fp32 throughout.  Activations channels-last fp32 [B][T][H][W][C], C <= 64.  csrc/vae.hip.
+ * oniris_vae_temb: the FiLM scale | shift of every ResBlock for one decode, emb[r][b][2 C_r] = t_cond(MPFourier(t_b))
+ * (vae.py:76-80); table [3 n_res_blocks] int32 = {offset of block r's freqs[2C] | phases[2C] | W[2C][2C] | bias[2C] in params,
+ * 2 C_r, offset of block r in emb divided by B}.
+ * oniris_vae_up: decompression 1x1 conv C -> C tc sc^2 (w [C tc sc^2][C], bias) written to the 'up' positions
+ * out [B][T tc][H sc][W sc][C] (vae.py:96-133, :148-164); x addressed through element strides sb / st / sh / sw / sc;
+ * in_scale / in_shift (or both NULL): x * scale + shift per input channel first (latents * std + mean, vae.py:305).
+ * oniris_vae_res_a: the first half of a ResBlock (vae.py:70-87): SiLU(RMS(x) (1 + scale) + shift), the group-causal
+ * (2g, 3, 3) conv C -> C g of [prefix ++ input] with stride g in time (vae.py:18-53), '(c g) t -> c (t g)', SiLU(RMS(.)).
+ * prefix = cache_in [B][g][H][W][C] (activated frames of the previous chunk) or, when NULL, the first g activated input
+ * frames; cache_out (a different buffer) receives the last g activated input frames.  T % g == 0.  emb = this block's
+ * [B][2C].  w packed [g / gpt][2g][9][C][nch gpt], output j = c gpt + gl <-> conv channel c g + gq gpt + gl (zero for c >= C),
+ * bias [g / gpt][nch gpt]; (nch, gpt) in {(8,1), (8,2), (8,4), (16,1), (16,2), (32,1), (64,1)}, C <= nch.
+ * oniris_vae_res_b: the second half: out = res + bias + conv3x3(u) (w packed [9][C][nch], bias [nch]).
+ * oniris_vae_out: final 1x1 conv Cin -> Cout (w [Cout][Cin], bias) + the channel-area residual (vae.py:128-141).  split = 0:
+ * out (element strides) receives all Cout channels; split > 0: channels < split to out, the rest to out2 times
+ * exp(*logvar_mult) (vae.py:199-203); frames (or NULL) receives uint8 clip((mean + 1) 127.5, 0, 255) [B][T][H][W][split]
+ * (vae.py:316-317); out may be NULL when frames is given.  The summation order of every output is fixed (time tap, row,
+ * column, channel, bias): a decode in chunks through the cache is bit-identical to the whole sequence.                     */
+int oniris_vae_temb(const float* params, const int32_t* table, int n_res_blocks, const float* t, int B, float* emb,
+                    oniris_stream_t stream);
+int oniris_vae_up(const float* x, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B, int T, int H, int W, int C,
+                  const float* in_scale, const float* in_shift, const float* w, const float* bias, int tcomp, int scomp, float* out,
+                  oniris_stream_t stream);
+int oniris_vae_res_a(const float* x, const float* cache_in, float* cache_out, const float* emb, const float* w, const float* bias,
+                     int B, int T, int H, int W, int C, int g, int nch, int gpt, float* out, oniris_stream_t stream);
+int oniris_vae_res_b(const float* u, const float* res, const float* w, const float* bias, int B, int T, int H, int W, int C,
+                     int nch, float* out, oniris_stream_t stream);
+int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout, int split,
+                   const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc,
+                   uint8_t* frames, oniris_stream_t stream);
 
 #ifdef __cplusplus
 }
