@@ -185,6 +185,10 @@ _SIGS = {
                                  c_void_p]),
     "oniris_vae_out": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "oniris_vae_down": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "oniris_vae_latents": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                   c_int64, c_int64, c_int64, c_void_p]),
 }
 EXPORTED = sorted(_SIGS)
 

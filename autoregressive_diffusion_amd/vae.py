@@ -1,14 +1,17 @@
-"""VAE decoder on HIP kernels: generated latents -> RGB frames on the GPU (reference: edm2/vae/vae.py).
+"""VAE on HIP kernels, both directions: RGB frames -> latents and generated latents -> RGB frames on the GPU (reference:
+edm2/vae/vae.py).
 
 `VAE` has the reference's constructor, `kwargs` and state_dict keys (encoder and decoder), so a checkpoint of the reference's
-VAE loads here unchanged and round-trips.  Only the decoder runs, for inference, in fp32 like the reference: `decode`,
-`latents_to_frames` and the streaming form `decode_frames`.  The decoder is causal in time -- every group-causal conv keeps
-the last g activated frames of its input as a cache (vae.py:18-53) -- so decoding one latent frame at a time through the
-cache gives exactly what decoding the whole sequence gives (bit-identical here: csrc/vae.hip sums every output in a fixed
-order).  Activations are channels-last fp32 [B][T][H][W][C]; per decoder block one `up` launch, two per ResBlock, one `out`
-launch, plus one t-embedding launch per decode (include/oniris.h: oniris_vae_*).
+VAE loads here unchanged and round-trips.  Encoder and decoder run for inference, in fp32 like the reference: `encode`,
+`encode_long_sequence`, `frames_to_latents` and the streaming form `encode_frames`; `decode`, `latents_to_frames` and the
+streaming form `decode_frames`.  Both are causal in time -- every group-causal conv keeps the last g activated frames of its
+input as a cache (vae.py:18-53) -- so encoding or decoding a sequence chunk by chunk through the cache gives exactly what the
+whole sequence gives (bit-identical here: csrc/vae.hip and csrc/vae_encoder.hip sum every output in a fixed order).
+Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up` launch, two per ResBlock, one `out` launch,
+plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
+ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
 
-The encoder, `forward` and `frames_to_latents` are not implemented here: use the reference's `edm2.vae`.
+`forward` (VAE training) is not implemented here, and the encoder has no CPU path: use the reference's `edm2.vae` for those.
 """
 import ctypes
 import inspect
@@ -21,7 +24,7 @@ from . import _lib
 from .edm2.utils import BetterModule, MPFourier
 
 MAX_WIDTH = 64
-_REF = "the reference's edm2.vae (this package implements the decoder only)"
+_REF = "the reference's edm2.vae (this package runs the VAE on HIP kernels only, for inference)"
 
 
 def _stream():
@@ -43,6 +46,22 @@ def _gpt(c, g):
     while gpt * 2 <= 4 and g % (gpt * 2) == 0 and _nch(c) * gpt * 2 <= 32:
         gpt *= 2
     return gpt
+
+
+def _pack_res(rb, C, g, f32):
+    """The two convolutions of a ResBlock in the layouts of vae_conv3_kernel (csrc/vae.hip)."""
+    nch, gpt = _nch(C), _gpt(C, g)
+    w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gq gpt + gl
+    w = w.reshape(C, g // gpt, gpt, C, 2 * g, 3, 3).permute(1, 4, 5, 6, 3, 0, 2)   # gq, kt, ky, kx, ci, c, gl
+    wa = torch.zeros(g // gpt, 2 * g, 3, 3, C, nch, gpt, **f32)
+    wa[:, :, :, :, :, :C] = w
+    ba = torch.zeros(g // gpt, nch, gpt, **f32)
+    ba[:, :C] = rb.conv3d0.conv3d.bias.detach().to(**f32).reshape(C, g // gpt, gpt).permute(1, 0, 2)
+    wb = torch.zeros(3, 3, C, nch, **f32)
+    wb[..., :C] = rb.conv3d1.weight.detach().to(**f32)[:, :, 0].permute(2, 3, 1, 0)   # ky, kx, ci, co
+    bb = torch.zeros(nch, **f32)
+    bb[:C] = rb.conv3d1.bias.detach().to(**f32)
+    return dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
 
 
 class GroupCausal3DConvVAE(nn.Module):
@@ -147,15 +166,6 @@ class VAE(BetterModule):
     def forward(self, x, t=0.1, cache=None):
         raise NotImplementedError(f"VAE.forward (encode + decode, training): use {_REF}")
 
-    def encode(self, x, cache=None):
-        raise NotImplementedError(f"VAE.encode: use {_REF}")
-
-    def encode_long_sequence(self, frames, cache=None, split_size=256):
-        raise NotImplementedError(f"VAE.encode_long_sequence: use {_REF}")
-
-    def frames_to_latents(self, frames):
-        raise NotImplementedError(f"VAE.frames_to_latents: use {_REF}")
-
     # ---- packed device weights
     def _pack(self, device):
         """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip, rebuilt when a parameter changed."""
@@ -172,17 +182,7 @@ class VAE(BetterModule):
                 nch, gpt = _nch(C), _gpt(C, g)
                 res = []
                 for rb in blk.res_blocks:
-                    w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gq gpt + gl
-                    w = w.reshape(C, g // gpt, gpt, C, 2 * g, 3, 3).permute(1, 4, 5, 6, 3, 0, 2)   # gq, kt, ky, kx, ci, c, gl
-                    wa = torch.zeros(g // gpt, 2 * g, 3, 3, C, nch, gpt, **f32)
-                    wa[:, :, :, :, :, :C] = w
-                    ba = torch.zeros(g // gpt, nch, gpt, **f32)
-                    ba[:, :C] = rb.conv3d0.conv3d.bias.detach().to(**f32).reshape(C, g // gpt, gpt).permute(1, 0, 2)
-                    wb = torch.zeros(3, 3, C, nch, **f32)
-                    wb[..., :C] = rb.conv3d1.weight.detach().to(**f32)[:, :, 0].permute(2, 3, 1, 0)   # ky, kx, ci, co
-                    bb = torch.zeros(nch, **f32)
-                    bb[:C] = rb.conv3d1.bias.detach().to(**f32)
-                    res.append(dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb, emb_off=eoff))
+                    res.append(dict(_pack_res(rb, C, g, f32), emb_off=eoff))
                     off = sum(x.numel() for x in tparams)
                     tparams += [rb.fourier_cond.freqs.detach().to(**f32), rb.fourier_cond.phases.detach().to(**f32),
                                 rb.t_cond.weight.detach().to(**f32).reshape(-1), rb.t_cond.bias.detach().to(**f32)]
@@ -295,3 +295,158 @@ class VAE(BetterModule):
         """latents (B, T, C, h, w) -> numpy int array (B, 4T, H, W, 3) = clip((mean + 1) 127.5, 0, 255) truncated (vae.py:288-318)."""
         frames, _ = self.decode_frames(latents, t)
         return frames.cpu().numpy().astype(int)
+
+    # ---- the encoder
+    def _pack_encoder(self, device):
+        """fp32 copies of the encoder's parameters on `device` in the layouts of csrc/vae_encoder.hip and csrc/vae.hip, rebuilt
+        when a parameter changed.  pk["params"] names every state_dict entry that went into it."""
+        params = list(self.encoder.parameters())
+        sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        pk = self.__dict__.get("_oniris_vae_enc_pack")
+        if pk is not None and pk["sig"] == sig:
+            return pk
+        f32 = dict(device=device, dtype=torch.float32)
+        blocks, names = [], []
+        with torch.no_grad():
+            for i, blk in enumerate(self.encoder.encoder_blocks):
+                Cin, C, g = self.encoder.in_channels[i], self.encoder.out_channels[i], self.encoder.group_sizes[i]
+                K = Cin * blk.time_compression * blk.spatial_compression ** 2
+                if K > 512:
+                    raise NotImplementedError(f"VAE encoder: block {i} compresses {K} channels: the HIP kernel takes up to 512")
+                g4 = (C + 3) // 4 * 4
+                wd = torch.zeros(K, 2, g4, **f32)              # per k = ((tc hc) wc) c: the conv weights | the area windows
+                wd[:, 0, :C] = blk.compression_block.weight.detach().to(**f32).reshape(C, K).t()
+                bd = torch.ones(2, g4, **f32)                  # the bias | the window lengths
+                bd[0] = 0
+                bd[0, :C] = blk.compression_block.bias.detach().to(**f32)
+                for o in range(C):
+                    s0, s1 = (o * K) // C, -((-(o + 1) * K) // C)
+                    wd[s0:s1, 1, o] = 1
+                    bd[1, o] = s1 - s0
+                pre = f"encoder.encoder_blocks.{i}."
+                names += [pre + "compression_block.weight", pre + "compression_block.bias"]
+                res = []
+                for j, rb in enumerate(blk.res_blocks):
+                    res.append(_pack_res(rb, C, g, f32))
+                    names += [pre + f"res_blocks.{j}.{n}" for n in ("conv3d0.conv3d.weight", "conv3d0.conv3d.bias", "conv3d1.weight",
+                                                                   "conv3d1.bias")]
+                blocks.append(dict(Cin=Cin, C=C, g=g, nch=_nch(C), gpt=_gpt(C, g), tc=blk.time_compression, sc=blk.spatial_compression,
+                                   wd=wd.contiguous(), bd=bd, res=res))
+            pk = dict(sig=sig, blocks=blocks, params=names, zeros={})
+        self.__dict__["_oniris_vae_enc_pack"] = pk
+        return pk
+
+    def _check_frames(self, what, shape, layout, B, C, T, H, W):
+        """The shape checks of every encoder entry point; they come before anything else."""
+        tcomp, scomp, c0 = int(self.time_compression), int(self.spatial_compression), self.encoder.in_channels[0]
+        if B is None or C != c0:
+            raise ValueError(f"VAE.{what}: expected {layout.format(c=c0)}, got {tuple(shape)}")
+        if T % tcomp != 0 or T == 0:
+            raise ValueError(f"VAE.{what}: {T} frames: the number of frames must be a positive multiple of the time compression {tcomp}")
+        if H % scomp != 0 or W % scomp != 0 or H == 0 or W == 0:
+            raise ValueError(f"VAE.{what}: frames of {H} x {W}: height and width must be positive multiples of the spatial "
+                             f"compression {scomp}")
+
+    def _encoder_device(self, what, x=None):
+        dev = self.device if x is None else x.device
+        if dev.type != "cuda" or self.device.type != "cuda":
+            raise NotImplementedError(f"VAE.{what}: the encoder runs on HIP kernels only (model and input on the GPU); on the CPU "
+                                      f"use {_REF}")
+        return dev
+
+    def _run_enc(self, x, strides, T, H, W, normalize, cache, want="mean"):
+        """x: fp32 or uint8 frames addressed by element strides (b, t, h, w, c); returns (mean (B, C, t, h, w) | normalised latents
+        (B, t, C, h, w), cache)."""
+        B, dev = x.shape[0], x.device
+        pk = self._pack_encoder(dev)
+        s = _stream()
+        zeros = pk["zeros"].get(B)
+        if zeros is None:                                    # the FiLM scale | shift of a ResBlock without t: zero
+            zeros = pk["zeros"][B] = torch.zeros(B * 2 * MAX_WIDTH, dtype=torch.float32, device=dev)
+        cache = {} if cache is None else cache
+        new_cache = {}
+        u8 = x.dtype == torch.uint8
+        for i, bk in enumerate(pk["blocks"]):
+            C, g, tc, sc = bk["C"], bk["g"], bk["tc"], bk["sc"]
+            T, H, W = T // tc, H // sc, W // sc
+            y = torch.empty(B, T, H, W, C, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib.oniris_vae_down(_p(x), int(u8), *strides, B, T, H, W, bk["Cin"], tc, sc, int(normalize), _p(bk["wd"]),
+                                                _p(bk["bd"]), C, _p(y), s), "vae_down")
+            x, strides, u8, normalize = y, y.stride()[:4] + (1,), False, False
+            bc = cache.get(f"encoder_block_{i}", {})
+            nbc = new_cache[f"encoder_block_{i}"] = {}
+            for j, rb in enumerate(bk["res"]):
+                cin = bc.get(f"res_block_{j}", {}).get("conv3d_res0")
+                if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != dev or cin.dtype != torch.float32):
+                    raise ValueError(f"VAE encoder cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
+                                     f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
+                cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=dev)
+                u = torch.empty_like(x)
+                _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), _p(zeros), _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g,
+                                                     bk["nch"], bk["gpt"], _p(u), s), "vae_res_a")
+                xn = torch.empty_like(x)
+                _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
+                           "vae_res_b")
+                x = xn
+                nbc[f"res_block_{j}"] = {"conv3d_res0": cout}
+        if want == "latents":
+            out = torch.empty(B, T, C, H, W, dtype=torch.float32, device=dev)
+            sb, st, scc, sh, sw = out.stride()
+            mean = self.mean.to(device=dev, dtype=torch.float32).contiguous()
+            std = self.std.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            out = torch.empty(B, C, T, H, W, dtype=torch.float32, device=dev)
+            sb, scc, st, sh, sw = out.stride()
+            mean = std = None
+        _lib.check(_lib.lib.oniris_vae_latents(_p(x), B, T, H, W, C, _p(mean), _p(std), _p(out), sb, st, sh, sw, scc, s), "vae_latents")
+        return out, new_cache
+
+    @torch.no_grad()
+    def encode(self, x, cache=None):
+        """x (B, 3, T, H, W) in [-1, 1] -> (mean (B, C, T / 4, H / 4, W / 4), cache) (vae.py:239-241).  The cache holds, under the
+        reference's keys cache['encoder_block_{i}']['res_block_{j}']['conv3d_res0'], the last g activated input frames of every
+        group-causal conv as opaque channels-last (B, g, H, W, C) fp32 tensors; pass it back to continue the sequence."""
+        self._check_frames("encode", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
+        self._encoder_device("encode", x)
+        x = x.float()
+        sb, sc, st, sh, sw = x.stride()
+        return self._run_enc(x, (sb, st, sh, sw, sc), x.shape[2], x.shape[3], x.shape[4], False, cache)
+
+    @torch.no_grad()
+    def encode_long_sequence(self, frames, cache=None, split_size=256):
+        """encode over chunks of split_size frames through the cache, each moved to the model's device on its own; returns the
+        mean (vae.py:250-259).  split_size must be a multiple of the time compression."""
+        self._check_frames("encode_long_sequence", frames.shape, "frames (B, {c}, T, H, W)",
+                           *(frames.shape if frames.dim() == 5 else (None,) * 5))
+        if split_size <= 0 or split_size % int(self.time_compression) != 0:
+            raise ValueError(f"VAE.encode_long_sequence: split_size {split_size} must be a positive multiple of the time compression "
+                             f"{int(self.time_compression)}")
+        dev = self._encoder_device("encode_long_sequence")
+        means = []
+        for s0 in range(0, frames.shape[2], split_size):
+            m, cache = self.encode(frames[:, :, s0:s0 + split_size].to(dev), cache=cache)
+            means.append(m)
+        return torch.cat(means, dim=2)
+
+    @torch.no_grad()
+    def encode_frames(self, frames, cache=None):
+        """Streaming frames_to_latents: frames (B, 4t, H, W, 3) with values 0..255, uint8 or any real dtype, on the GPU ->
+        (latents (B, t, C, h, w) fp32, normalised as Precond and the sampler take them, cache).  uint8 frames are read in place and
+        frames / 127.5 - 1 is applied on load.  Feed the returned cache to the next call: chunk by chunk (the smallest chunk is one
+        latent frame), the result equals frames_to_latents over the whole sequence."""
+        B, T, H, W, C = frames.shape if frames.dim() == 5 else (None,) * 5
+        self._check_frames("encode_frames", frames.shape, "frames (B, T, H, W, {c})", B, C, T, H, W)
+        self._encoder_device("encode_frames", frames)
+        if not hasattr(self, "mean"):
+            raise RuntimeError("VAE: frames_to_latents needs the `mean` / `std` constructor arguments (as in the reference)")
+        if frames.dtype != torch.uint8:
+            frames = frames.float()
+        sb, st, sh, sw, sc = frames.stride()
+        return self._run_enc(frames, (sb, st, sh, sw, sc), T, H, W, True, cache, want="latents")
+
+    @torch.no_grad()
+    def frames_to_latents(self, frames):
+        """frames (B, T, H, W, 3), values 0..255 -> latents (B, T / 4, C, h, w) = (encode(frames / 127.5 - 1) - mean) / std, the
+        formula cs_train.py:102 applies by hand and the inverse of the affine in latents_to_frames.  (The reference's own method,
+        vae.py:264-284, does not run: it unpacks four values from encode, adds std and returns nothing.)"""
+        return self.encode_frames(frames)[0]

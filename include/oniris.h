@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
@@ -632,6 +632,25 @@ int oniris_vae_res_b(const float* u, const float* res, const float* w, const flo
 int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout, int split,
                    const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc,
                    uint8_t* frames, oniris_stream_t stream);
+
+/* VAE encoder (reference: EncoderDecoder(type='encoder') vae.py:96-204, VAE.encode :239-241), inference, fp32 throughout.
+ * csrc/vae_encoder.hip.  Its ResBlocks are oniris_vae_res_a / oniris_vae_res_b with a zero emb buffer (the encoder passes
+ * t = None, vae.py:78-82; v (1 + 0) + 0 is exact) and the group sizes cumprod(time_compressions) reversed (vae.py:180-181).
+ * oniris_vae_down: 'b c (t tc) (h hc) (w wc) -> b (tc hc wc c) t h w' (vae.py:157-161), the compression 1x1 conv
+ * K = Cin tc sc^2 -> Cout and the channel-area residual of the rearranged input (vae.py:118-122, :136-141), in one launch;
+ * out channels-last [B][To][Ho][Wo][Cout].  w packed [K][2][G4] (G4 = Cout rounded up to a multiple of 4): per rearranged
+ * channel k the conv weights, then 1 where k lies in output o's area window [floor(o K / Cout), ceil((o + 1) K / Cout)) and
+ * 0 elsewhere; bias packed [2][G4]: the bias, then the window lengths (1 beyond Cout).  x is addressed through element strides sb / st / sh / sw / sc and holds To tc x Ho sc x Wo sc
+ * pixels of Cin channels, fp32 or (x_is_u8) uint8; normalize: x / 127.5 - 1 is applied on load (vae.py:271).
+ * K <= 512, Cout <= 64, tc and sc in {1, 2}.
+ * oniris_vae_latents: x channels-last [B][T][H][W][C] -> out through element strides, as it is (mean / std NULL) or
+ * (x - mean[c]) / std[c].  The summation order of every output is fixed (rearranged channel ascending, bias, residual): an
+ * encode in chunks through the cache is bit-identical to the whole sequence.                                                */
+int oniris_vae_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B, int To, int Ho,
+                    int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w, const float* bias, int Cout, float* out,
+                    oniris_stream_t stream);
+int oniris_vae_latents(const float* x, int B, int T, int H, int W, int C, const float* mean, const float* std, float* out,
+                       int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, oniris_stream_t stream);
 
 #ifdef __cplusplus
 }
