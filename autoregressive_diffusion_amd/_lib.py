@@ -40,7 +40,9 @@ class ConvArgs(C.Structure):
                 ("big_tile", c_int32), ("escale_pitch", c_int32),
                 ("splitk_ws", c_void_p), ("splitk_ws_bytes", C.c_size_t), ("clip_flag", c_void_p),
                 ("ctx_prod", c_void_p), ("ctx_prod_mode", c_int32), ("x_split", c_int32), ("x2", c_void_p), ("act_out", c_void_p),
-                ("cat_w1", c_float), ("cat_w2", c_float), ("ctx_rows", c_int32)]
+                ("cat_w1", c_float), ("cat_w2", c_float), ("ctx_rows", c_int32),
+                ("ab_c1", c_int32), ("ab_da", c_void_p), ("ab_xo", c_void_p), ("ab_dskip", c_void_p), ("ab_dadd", c_void_p),
+                ("ab_w1", c_float), ("ab_w2", c_float), ("ab_dxo_scale", c_float)]
 
 
 class WgradArgs(C.Structure):
@@ -73,7 +75,7 @@ class AttnF32Args(C.Structure):
                 ("T", c_int32), ("q_frame_off", c_int32), ("scale", c_float), ("pad_", c_int32)]
 
 
-EPI_NONE, EPI_EMB_SILU, EPI_MPSUM = 0, 1, 2
+EPI_NONE, EPI_EMB_SILU, EPI_MPSUM, EPI_ACT_BWD = 0, 1, 2, 3
 
 # every symbol include/oniris.h declares (tests/test_abi.py checks the list against the header)
 _SIGS = {

@@ -115,6 +115,23 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
 __device__ __forceinline__ float sigmoid_fast(float z) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
 }
+// Adjoint of mp_cat + mp_silu without the pixel norm (utils.py:112, :128-134), per element -- shared by act_bwd_kernel<NORM = false>
+// (elementwise.hip) and the ONIRIS_EPI_ACT_BWD conv epilogue (conv_kernels.h), whose results must agree bit for bit:
+//   g = da * silu'(xo) / 0.596 [_da]  (+ dxo_scale * dxo) [_dxo];   result = g * w (+ add) [_out]
+// Every multiply-add is spelled out -- an fma where it says fmaf, separately rounded products elsewhere (a product never feeds an
+// addition directly) -- so that the compiler's contraction has nothing to decide at either call site.
+__device__ __forceinline__ float act_adjoint_da(float da, float xo) {
+  const float sg = sigmoid_fast(xo);
+  const float one_m = 1.f - sg;
+  const float u = __builtin_fmaf(one_m, xo, 1.f);       // silu'(z) = sg * (1 + z * (1 - sg))
+  float g = sg * u;
+  g = g * da;
+  return g * (1.0f / 0.596f);
+}
+__device__ __forceinline__ float act_adjoint_dxo(float g, float dxo_scale, float dxo) { return __builtin_fmaf(dxo_scale, dxo, g); }
+__device__ __forceinline__ float act_adjoint_out(float g, float w, bool has_add, float add) {
+  return has_add ? __builtin_fmaf(w, g, add) : g * w;
+}
 __device__ __forceinline__ int mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __device__ __forceinline__ float wave_sum(float v) {

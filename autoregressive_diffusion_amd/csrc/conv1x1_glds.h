@@ -11,7 +11,7 @@
 // blocks) are consecutive in a workgroup's run, so the activation chunk is re-read from L2, not HBM.
 // Rows are 128 bytes, unpadded (the DMA image is lane-linear); the 16-byte pieces are XOR-swizzled on the source side
 // with (row >> 1) & 7, which makes the 16-row groups of a ds_read_b128 conflict-free (same scheme as the attention
-// K tile).  Epilogues: none / mp_sum(+clip) with optional raw output, as conv_kernels.h.
+// K tile).  Epilogues: none / mp_sum(+clip) with optional raw output, as conv_kernels.h; <ACTB>: ONIRIS_EPI_ACT_BWD.
 #pragma once
 #include "conv_kernels.h"
 #include "lds_dma.h"
@@ -25,6 +25,8 @@ struct C1Cfg {
   static_assert(NSTG * STG <= 160 * 1024, "stages must fit the LDS");
 };
 
+// ACTB: the instantiation carries the ONIRIS_EPI_ACT_BWD epilogue (include/oniris.h) and no other; <false> compiles as before.
+template <bool ACTB>
 __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using Cfg = C1Cfg;
@@ -167,7 +169,28 @@ __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
         }
       };
       float v[16];
-      if (a.epi == ONIRIS_EPI_MPSUM) {
+      if constexpr (ACTB) {
+        // the rounded dgrad goes through the wave's transpose tile; the adjoint of mp_cat + mp_silu is applied to each 16-byte
+        // piece on its way out (conv_act_bwd_piece, conv_kernels.h): the gradient of the concatenated tensor never reaches HBM
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) v[i] = acc[m][nt][i];
+          put(nt, v);
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const int id = it * 64 + lane, row = id >> 3, part = id & 7;
+          const int co = cow + part * 8;
+          if (prow + row < M && co < Cout) {
+            // (loads right in front of their use: issued ahead of the barrier and the LDS staging, 64 more registers deep, the
+            // launches were slower -- bench +1.07 % instead of +1.40 % against the parent on one box)
+            bf16x8 dav, xov;
+            conv_act_bwd_load(a, d.nt != 0, (size_t)(prow + row), co, dav, xov);
+            conv_act_bwd_piece(a, d.nt != 0, *(const bf16x8*)(ep + row * EROW + part * 16), dav, xov, (size_t)(prow + row), co);
+          }
+        }
+      } else if (a.epi == ONIRIS_EPI_MPSUM) {
         if (a.out2) {
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt) {
@@ -216,7 +239,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
 static inline bool conv1x1_glds_ok(const OnirisConvArgs& a) {
   const long long M = (long long)a.B * a.S * a.T * a.H * a.W;
   return a.taps == 1 && !a.ctx && a.Cin % 64 == 0 && a.CinP == a.Cin && a.Cin <= 1024 && a.Cout % 8 == 0 &&
-         (a.epi == ONIRIS_EPI_NONE || a.epi == ONIRIS_EPI_MPSUM) && M >= 8192 && M * a.Cin * 2 < (1LL << 31) &&
+         (a.epi == ONIRIS_EPI_NONE || a.epi == ONIRIS_EPI_MPSUM || a.epi == ONIRIS_EPI_ACT_BWD) && M >= 8192 && M * a.Cin * 2 < (1LL << 31) &&
          (long long)a.CoutP * a.CinP * 2 < (1LL << 31);
 }
 
@@ -231,7 +254,10 @@ static int launch_conv1x1_glds(const OnirisConvArgs& a, hipStream_t stream) {
   const long long ntiles = (long long)d.ntt * d.ncob;
   const int ncu = oniris_persistent_wgs();       // one workgroup per CU (minus the CUs reserved for a gradient exchange in flight)
   const long long nblk = ntiles < ncu ? ntiles : ncu;
-  oniris_launch_tagged(d.nt ? "nt-stores" : nullptr, conv1x1_glds_kernel, dim3((unsigned)nblk), dim3(C1Cfg::NTHR), stream, d);
+  if (a.epi == ONIRIS_EPI_ACT_BWD)
+    oniris_launch_tagged(d.nt ? "nt-stores" : nullptr, conv1x1_glds_kernel<true>, dim3((unsigned)nblk), dim3(C1Cfg::NTHR), stream, d);
+  else
+    oniris_launch_tagged(d.nt ? "nt-stores" : nullptr, conv1x1_glds_kernel<false>, dim3((unsigned)nblk), dim3(C1Cfg::NTHR), stream, d);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }

@@ -23,6 +23,10 @@ extern "C" int oniris_conv_fwd(const OnirisConvArgs* args, oniris_stream_t strea
                    "conv_fwd: bad padded sizes CoutP=%d CinP=%d", a.CoutP, a.CinP);
   ONIRIS_CHECK_ARG(a.epi != ONIRIS_EPI_MPSUM || a.res, "conv_fwd: EPI_MPSUM needs res");
   ONIRIS_CHECK_ARG(a.epi != ONIRIS_EPI_EMB_SILU || (a.escale && a.out2), "conv_fwd: EPI_EMB_SILU needs escale/out2");
+  ONIRIS_CHECK_ARG(a.epi != ONIRIS_EPI_ACT_BWD ||
+                       (a.taps == 1 && a.S == 1 && !a.ctx && !a.x2 && !a.out2 && !a.ctx_out && !a.coef_own && !a.coef_ctx && a.ab_da && a.ab_xo &&
+                        a.ab_dskip && a.ab_c1 > 0 && a.ab_c1 < a.Cout && a.ab_c1 % 8 == 0 && a.ctx_prod_mode == 0 && a.ctx_rows == 0),
+                   "conv_fwd: EPI_ACT_BWD is a plain 1x1 launch (S == 1) with ab_da / ab_xo / ab_dskip and 0 < ab_c1 < Cout, ab_c1 %% 8 == 0");
   ONIRIS_CHECK_ARG(a.x2 == nullptr || (a.taps == 1 && a.ctx == nullptr), "conv_fwd: x2 (concatenated input) is a 1x1, context-free option");
   const bool has_ctx = a.ctx != nullptr;
   ONIRIS_CHECK_ARG(!has_ctx || (a.w_ctx && a.taps == 9), "conv_fwd: context path needs w_ctx and taps == 9");

@@ -25,6 +25,16 @@ int conv_dispatch_s1(const OnirisConvArgs& a, hipStream_t st) {
   return conv3x3_pick<1, false>(a, st);
 }
 int conv_dispatch_1x1(const OnirisConvArgs& a, hipStream_t st) {
+  if (a.epi == ONIRIS_EPI_ACT_BWD) {
+    // the dgrad of a decoder Block's skip conv with the mp_cat + mp_silu adjoint as its epilogue: the two families that run these
+    // dgrads in training, on the same K order as their plain instantiations (bit-identical to the two launches)
+    if (a.big_tile >= 3 && conv1x1_glds_ok(a)) return launch_conv1x1_glds(a, st);
+    if (a.CoutP % 64 == 0) return launch_conv_fwd<1, 1, 64, 2, false, 16, 4, true>(a, st);
+    if (a.CoutP % 96 == 0) return launch_conv_fwd<1, 1, 64, 3, false, 16, 4, true>(a, st);
+    oniris_set_error("conv_fwd: EPI_ACT_BWD is served by the LDS-DMA 1x1 kernel and by the register-staged one with CoutP %% 64 == 0 "
+                     "or CoutP %% 96 == 0 (got CoutP = %d)", a.CoutP);
+    return ONIRIS_EUNSUPPORTED;
+  }
   if (a.x2) {                                       // two-source input + activation side output: the register-staged kernel only
     if (a.x_split <= 0 || a.x_split >= a.Cin || a.x_split % 8 != 0 || a.Cin % 8 != 0 || a.S != 1 ||
         (a.big_tile >= 3 && conv1x1_glds_ok(a))) {

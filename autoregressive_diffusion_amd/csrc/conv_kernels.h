@@ -36,6 +36,42 @@ struct ConvDev {
   int nt;                // conv_glds_kernel: outputs go out with non-temporal stores (tensors beyond oniris_ew_nt_bytes())
 };
 
+#ifdef __HIPCC__
+// ONIRIS_EPI_ACT_BWD (include/oniris.h), one 16-byte piece: d = channels co .. co+7 of position pos of the conv result, already
+// rounded to bf16 (the flush of an epilogue reads it back from its LDS transpose tile: one lane = 8 consecutive channels of one
+// position, the thread layout of act_bwd_kernel -- da, xo, dadd are read and dx / dskip written as whole 16-byte vectors, 8 lanes
+// to a 128-byte line).  C1 % 8 == 0: a piece lies on one side of the split.
+__device__ __forceinline__ void conv_act_bwd_load(const OnirisConvArgs& a, const bool nt, const size_t pos, const int co, bf16x8& dav,
+                                                  bf16x8& xov) {
+  const bf16x8* pda = (const bf16x8*)((const bf16*)a.ab_da + pos * a.Cout + co);
+  const bf16x8* pxo = (const bf16x8*)((const bf16*)a.ab_xo + pos * a.Cout + co);
+  if (nt) { dav = __builtin_nontemporal_load(pda); xov = __builtin_nontemporal_load(pxo); }
+  else { dav = *pda; xov = *pxo; }
+}
+__device__ __forceinline__ void conv_act_bwd_piece(const OnirisConvArgs& a, const bool nt, const bf16x8 d, const bf16x8 dav,
+                                                   const bf16x8 xov, const size_t pos, const int co) {
+  const int C = a.Cout, C1 = a.ab_c1;
+  const bool first = co < C1;
+  const bool has_add = first && a.ab_dadd != nullptr;
+  bf16x8 addv;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) addv[i] = f2bf(0.f);
+  if (has_add) {
+    const bf16x8* pad = (const bf16x8*)((const bf16*)a.ab_dadd + pos * C1 + co);
+    addv = nt ? __builtin_nontemporal_load(pad) : *pad;
+  }
+  const float w = first ? a.ab_w1 : a.ab_w2;
+  bf16x8 o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float g = act_adjoint_dxo(act_adjoint_da(bf2f(dav[i]), bf2f(xov[i])), a.ab_dxo_scale, bf2f(d[i]));
+    o[i] = f2bf(act_adjoint_out(g, w, has_add, bf2f(addv[i])));
+  }
+  bf16x8* dst = first ? (bf16x8*)((bf16*)a.out + pos * C1 + co) : (bf16x8*)((bf16*)a.ab_dskip + pos * (C - C1) + (co - C1));
+  if (nt) __builtin_nontemporal_store(o, dst); else *dst = o;
+}
+#endif
+
 template <int S, int TAPS, int CK, int NT, bool HAS_CTX, int PW, int NW = 4>
 struct ConvCfg {
   using P = Patch<PW, 32 * NW>;
@@ -50,8 +86,11 @@ struct ConvCfg {
   static constexpr int LDS_BYTES = ((AROWS + WROWS) * ROWB > EPI_BYTES) ? (AROWS + WROWS) * ROWB : EPI_BYTES;
 };
 
-template <int S, int TAPS, int CK, int NT, bool HAS_CTX, int PW, int NW = 4>
+// ACTB: the instantiation carries the ONIRIS_EPI_ACT_BWD epilogue and nothing else (1x1, S == 1, no split-K): every other
+// instantiation compiles exactly as it did without it.
+template <int S, int TAPS, int CK, int NT, bool HAS_CTX, int PW, int NW = 4, bool ACTB = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(const ConvDev d) {
+  static_assert(!ACTB || (S == 1 && TAPS == 1 && !HAS_CTX), "ONIRIS_EPI_ACT_BWD is a 1x1, context-free epilogue");
   using Cfg = ConvCfg<S, TAPS, CK, NT, HAS_CTX, PW, NW>;
   using P = typename Cfg::P;
   constexpr int BN = Cfg::BN, ROWB = Cfg::ROWB, PARTS = Cfg::PARTS;
@@ -444,6 +483,24 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
           *(bf16x4*)(ep + pr * EROW + (nt * 32 + 8 * g + 4 * h) * 2) = o;
         }
     };
+    if constexpr (ACTB) {
+      // the rounded dgrad goes through the wave's transpose tile; the adjoint of mp_cat + mp_silu is applied to each 16-byte piece
+      // on its way out (conv_act_bwd_piece)
+      stage();
+      constexpr int PO = BN / 8;
+#pragma unroll
+      for (int it = 0; it < 32 * PO / 64; ++it) {
+        const int id = it * 64 + lane;
+        const int row = id / PO, part = id % PO;
+        const int q = q0 + wave * 32 + row, co = co0 + part * 8;
+        if (q < T * HWp && co < a.Cout) {
+          bf16x8 dav, xov;
+          conv_act_bwd_load(a, d.nt != 0, blk + (size_t)q, co, dav, xov);
+          conv_act_bwd_piece(a, d.nt != 0, *(const bf16x8*)(ep + row * EROW + part * 16), dav, xov, blk + (size_t)q, co);
+        }
+      }
+      continue;
+    }
     if (a.epi == ONIRIS_EPI_MPSUM) {
       if (a.out2) { stage(); flush((bf16*)a.out2, blk); }       // raw conv output (needed for d gate)
 #pragma unroll
@@ -496,7 +553,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
   }
 }
 
-template <int S, int TAPS, int CK, int NT, bool HAS_CTX, int PW, int NW = 4>
+template <int S, int TAPS, int CK, int NT, bool HAS_CTX, int PW, int NW = 4, bool ACTB = false>
 static int launch_conv_fwd(const OnirisConvArgs& a, hipStream_t stream) {
   using Cfg = ConvCfg<S, TAPS, CK, NT, HAS_CTX, PW, NW>;
   using P = typename Cfg::P;
@@ -511,8 +568,17 @@ static int launch_conv_fwd(const OnirisConvArgs& a, hipStream_t stream) {
   long long nblk = (long long)d.ntx * d.nty * d.ntt * a.B * d.ncob;
   if (nblk <= 0 || nblk > 0x7fffffffLL) { oniris_set_error("conv_fwd: bad grid %lld", nblk); return ONIRIS_EINVAL; }
   // split-K when the caller lent a workspace and the tiles alone leave most of the chip idle
-  d.ksplit = 1; d.reduce = 0; d.grid3d = 0;
+  d.ksplit = 1; d.reduce = 0; d.grid3d = 0; d.nt = 0;
   const long long ntile = nblk;
+  if (ACTB) {                  // training-sized by construction: one launch, grid (position tile, batch element, channel block)
+    if (a.B > 65535 || d.ncob > 65535) { oniris_set_error("conv_fwd: EPI_ACT_BWD grid out of range"); return ONIRIS_EUNSUPPORTED; }
+    d.grid3d = 1;
+    d.nt = (long long)a.B * a.T * a.H * a.W * a.Cout * 2 >= oniris_ew_nt_bytes();
+    oniris_launch_tagged(d.nt ? "nt-stores" : nullptr, conv_fwd_kernel<S, TAPS, CK, NT, HAS_CTX, PW, NW, ACTB>,
+                         dim3((unsigned)d.ntt, (unsigned)a.B, (unsigned)d.ncob), dim3(Cfg::NTHR), stream, d);
+    ONIRIS_LAUNCH_CHECK();
+    return ONIRIS_OK;
+  }
   if (a.splitk_ws && nblk <= 64) {
     const int nphase = cdiv(a.Cin, CK) * (HAS_CTX ? 3 : 1);
     constexpr size_t per = (size_t)(S + (HAS_CTX ? 1 : 0)) * NT * Cfg::NTHR * 16 * sizeof(float);
@@ -526,7 +592,7 @@ static int launch_conv_fwd(const OnirisConvArgs& a, hipStream_t stream) {
     if ((size_t)nblk * ks * per > a.splitk_ws_bytes) ks = (long long)(a.splitk_ws_bytes / (nblk * per));
     if (ks > 1) { d.ksplit = (int)ks; nblk *= ks; }
   }
-  auto kern = conv_fwd_kernel<S, TAPS, CK, NT, HAS_CTX, PW, NW>;
+  auto kern = conv_fwd_kernel<S, TAPS, CK, NT, HAS_CTX, PW, NW, ACTB>;
   if (TAPS == 1 && d.ksplit == 1 && a.B <= 65535 && d.ncob <= 65535) {
     d.grid3d = 1;
     ONIRIS_KLAUNCH(kern, dim3((unsigned)d.ntt, (unsigned)a.B, (unsigned)d.ncob), dim3(Cfg::NTHR), 0, stream, d);

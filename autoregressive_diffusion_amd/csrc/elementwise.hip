@@ -112,12 +112,22 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16* __restrict__ d
   if (ok) {
     const bf16x8 xin = ldv<NT>((const bf16x8*)(xo + pix * C + cg * 8));
     const bf16x8 dain = ldv<NT>((const bf16x8*)(da + pix * C + cg * 8));
+    if constexpr (!NORM) {                             // the arithmetic the ONIRIS_EPI_ACT_BWD conv epilogue shares (common.h)
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { xv[i] = bf2f(xin[i]); g[i] = bf2f(dain[i]) * dsilu_f(xv[i]) * SILU_SCALE; }
-    if (dxo) {
-      const bf16x8 d2 = ldv<NT>((const bf16x8*)(dxo + pix * C + cg * 8));
+      for (int i = 0; i < 8; ++i) g[i] = act_adjoint_da(bf2f(dain[i]), bf2f(xin[i]));
+      if (dxo) {
+        const bf16x8 d2 = ldv<NT>((const bf16x8*)(dxo + pix * C + cg * 8));
 #pragma unroll
-      for (int i = 0; i < 8; ++i) g[i] += dxo_scale * bf2f(d2[i]);
+        for (int i = 0; i < 8; ++i) g[i] = act_adjoint_dxo(g[i], dxo_scale, bf2f(d2[i]));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { xv[i] = bf2f(xin[i]); g[i] = bf2f(dain[i]) * dsilu_f(xv[i]) * SILU_SCALE; }
+      if (dxo) {
+        const bf16x8 d2 = ldv<NT>((const bf16x8*)(dxo + pix * C + cg * 8));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g[i] += dxo_scale * bf2f(d2[i]);
+      }
     }
   }
   if (NORM) {
@@ -140,15 +150,15 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16* __restrict__ d
     if (dadd) {
       const bf16x8 d3 = ldv<NT>((const bf16x8*)(dadd + pix * C1 + c));
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = f2bf(g[i] * w1 + bf2f(d3[i]));
+      for (int i = 0; i < 8; ++i) o[i] = f2bf(NORM ? g[i] * w1 + bf2f(d3[i]) : act_adjoint_out(g[i], w1, true, bf2f(d3[i])));
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = f2bf(g[i] * w1);
+      for (int i = 0; i < 8; ++i) o[i] = f2bf(NORM ? g[i] * w1 : act_adjoint_out(g[i], w1, false, 0.f));
     }
     stv<NT>((bf16x8*)(dx + pix * C1 + c), o);
   } else {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = f2bf(g[i] * w2);
+    for (int i = 0; i < 8; ++i) o[i] = f2bf(NORM ? g[i] * w2 : act_adjoint_out(g[i], w2, false, 0.f));
     stv<NT>((bf16x8*)(dskip + pix * C2 + (c - C1)), o);
   }
 }

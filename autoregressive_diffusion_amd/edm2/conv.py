@@ -85,8 +85,9 @@ class MPConv(nn.Module):
         self.weight = NormalizedWeight(in_channels, out_channels, kernel)
         assert dilation == 1
 
-    def _cl(self, x, res=None, ta=0.0, tb=0.0, clip=0.0, in_slot=None, res_slot=None):
-        return ops.conv(x, self.weight.pw, res, ta, tb, clip, in_slot=in_slot, res_slot=res_slot)
+    def _cl(self, x, res=None, ta=0.0, tb=0.0, clip=0.0, in_slot=None, res_slot=None, dgrad_slot=None):
+        kw = dict(dgrad_slot=dgrad_slot) if dgrad_slot is not None else {}       # (ops.DgradSlot: a decoder Block's skip conv)
+        return ops.conv(x, self.weight.pw, res, ta, tb, clip, in_slot=in_slot, res_slot=res_slot, **kw)
 
     def forward(self, x, gain=1):
         if _fp32.active():                                      # Precond(use_fp16=False) / force_fp32=True: fp32 end to end

@@ -64,6 +64,7 @@ class Block(nn.Module):
         # xs: the activation's xo is the residual of conv_res1 (no 1x1 skip conv in between): that conv parks the residual gradient
         # as (gradient of its output, ta) and the activation's backward kernel applies the factor -- ta * g is never written
         skip_conv_done = False
+        dgs = None
         want_xs = (private_out and ops.ALIAS2 and self.training and torch.is_grad_enabled()
                    and not (self.flavor == "dec" and self.conv_skip is not None))
         if self.flavor == "enc" and self.conv_skip is not None:
@@ -82,7 +83,12 @@ class Block(nn.Module):
             x, a = ops.conv_cat_act(x, skip, cat_w[0], cat_w[1], self.conv_skip.weight.pw)
             skip_conv_done = True
         elif skip is not None:
-            x, a = ops.act(x, skip, cat_w[0], cat_w[1], want_xo=True, in_slot=in_slot, skip_slot=skip_slot, xo_slot=xs)   # x <- mp_cat(x, skip); a = mp_silu(x)
+            # training: the 1x1 skip conv below is xo's only consumer -- its data gradient and this activation's adjoint run as ONE
+            # backward launch (ops.DgradSlot); decided here, in forward, None = the two launches
+            if self.conv_skip is not None and self.training and xs is None:
+                dgs = ops.skip_act_bwd_slot(x, skip, self.conv_skip.weight.pw)
+            x, a = ops.act(x, skip, cat_w[0], cat_w[1], want_xo=True, in_slot=in_slot, skip_slot=skip_slot, xo_slot=xs,
+                           **(dict(dgrad_slot=dgs) if dgs is not None else {}))   # x <- mp_cat(x, skip); a = mp_silu(x)
         else:
             x, a = ops.act(x, want_xo=True, in_slot=in_slot, resample=rs, xo_slot=xs)  # (no resampling: x comes back as an alias of itself)
         N = x.shape[0]
@@ -94,7 +100,7 @@ class Block(nn.Module):
         if self.training and self.dropout != 0:
             y = F.dropout(y, p=self.dropout)
         if self.flavor == "dec" and self.conv_skip is not None and not skip_conv_done:
-            x = self.conv_skip._cl(x)
+            x = self.conv_skip._cl(x, dgrad_slot=dgs)
         t = self.res_balance
         den = 1.0 / math.sqrt((1 - t) ** 2 + t ** 2)
         clip = float(self.clip_act) if self.clip_act is not None else 0.0

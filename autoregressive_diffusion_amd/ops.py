@@ -452,6 +452,7 @@ class WeightBank:
             self.zero_arena.reset(self.items[0][0].param.device)   # the previous step's backward is done with its accumulators
             self._flags = None                         # (clip flags: a fresh tensor per forward, see take_flag)
             GradSlot.live = []
+            DgradSlot._check_queued = False            # (a backward that raised may have left its end-of-backward check queued)
         global _weights_epoch
         if training:
             _weights_epoch += 1                        # parameters are rewritten in place (forced normalisation)
@@ -624,7 +625,8 @@ CLIP_FLAG = int(_os.environ.get("ONIRIS_CLIP_FLAG", "1"))    # 0: the mp_sum bac
 def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, Cin, CinP, Cout, CoutP, taps,
                  ctx_bstride=0, ctx_T=0, coff=(0, 0), ctx_fill=0.0, epi=0, res=None, escale=None, emb_gain=None,
                  out2=None, ta=0.0, tb=0.0, clip=0.0, ctx_out=None, clip_flag=None, ctx_prod=None, ctx_prod_mode=0,
-                 x2=None, act_out=None, x_split=0, cat_w=(1.0, 1.0), ctx_rows=0):
+                 x2=None, act_out=None, x_split=0, cat_w=(1.0, 1.0), ctx_rows=0, act_bwd=None):
+    """act_bwd = (da, xo, dskip, dadd, C1, w1, w2, dxo_scale) with epi = EPI_ACT_BWD: `out` is dx (see include/oniris.h)."""
     if KernelProfile.enabled:
         flops = 2.0 * B * S * T * H * W * Cout * Cin * taps
         if ctx is not None:
@@ -646,19 +648,21 @@ def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, C
               and ((H % 16 == 0 and W % 16 == 0) or (H == 8 and W == 8 and CoutP % 64 == 0))):   # conv_dispatch_s1()
             key = (f"conv_glds_kernel<NT={nt},PW=16,NW=8,MT=1,WC=1,CTX=0>" if H % 16 == 0 else
                    "conv_glds_kernel<NT=1,PW=8,NW=8,MT=1,WC=2,CTX=0>")
-        elif (BIG_TILE >= 3 and taps == 1 and ctx is None and Cin % 64 == 0 and CinP == Cin and epi in (0, _lib.EPI_MPSUM)
-              and B * S * T * H * W >= 8192):                 # conv1x1_glds_ok() in csrc/conv1x1_glds.h
-            key = "conv1x1_glds_kernel"
+        elif (BIG_TILE >= 3 and taps == 1 and ctx is None and Cin % 64 == 0 and CinP == Cin
+              and epi in (0, _lib.EPI_MPSUM, _lib.EPI_ACT_BWD) and B * S * T * H * W >= 8192):   # conv1x1_glds_ok() in csrc/conv1x1_glds.h
+            key = "conv1x1_glds_kernel<ACTB>" if epi == _lib.EPI_ACT_BWD else "conv1x1_glds_kernel"
+        elif epi == _lib.EPI_ACT_BWD:                             # conv_dispatch_1x1(): the register-staged kernel, 64- or 96-channel tiles
+            key = f"conv_fwd_kernel<S=1,TAPS=1,CK=64,NT={2 if CoutP % 64 == 0 else 3},CTX=0,PW={_patch_w(W)},ACTB>"
         else:
             key = f"conv_fwd_kernel<S={S},TAPS={taps},CK={32 if taps == 9 else 64},NT={nt},CTX={int(ctx is not None)},PW={_patch_w(W)}>"
         if PROFILE_SHAPES:
-            key += f" [{H}x{W} {Cin}->{Cout} epi={epi}{' res' if res is not None else ''}{' out2' if out2 is not None else ''}{' y3' if ctx_out is not None else ''}{' dgrad' if coff[0] > 0 else ''}]"
+            key += f" [{H}x{W} {Cin}->{Cout} epi={epi}{' act_bwd' if act_bwd is not None else ''}{' dadd' if act_bwd is not None and act_bwd[3] is not None else ''}{' res' if res is not None else ''}{' out2' if out2 is not None else ''}{' y3' if ctx_out is not None else ''}{' dgrad' if coff[0] > 0 else ''}]"
         KernelProfile.enabled = False
         try:
             e0, e1 = _timed_launch(lambda: _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, Cin, CinP,
                                                         Cout, CoutP, taps, ctx_bstride, ctx_T, coff, ctx_fill, epi, res, escale,
                                                         emb_gain, out2, ta, tb, clip, ctx_out, clip_flag, ctx_prod, ctx_prod_mode,
-                                                        ctx_rows=ctx_rows))
+                                                        ctx_rows=ctx_rows, act_bwd=act_bwd))
         finally:
             KernelProfile.enabled = True
         # algorithmic HBM bytes of the launch (every operand read once, every result written once; the context
@@ -669,6 +673,8 @@ def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, C
                         + taps * CoutP * CinP * (3 if ctx is not None else 1))
         if ctx is not None and ctx.data_ptr() != x.data_ptr():
             nbytes += 2.0 * B * ctx_T * H * W * Cin
+        if act_bwd is not None:          # + da and xo read once, dadd if present (dx and dskip together are the Cout channels counted above)
+            nbytes += 2.0 * px * (2 * Cout + (act_bwd[4] if act_bwd[3] is not None else 0))
         KernelProfile.records.append((key, flops, e0, e1, nbytes))
         return
     a = _lib.ConvArgs()
@@ -687,6 +693,9 @@ def _conv_launch(x, ctx, w_own, w_ctx, out, coef_own, coef_ctx, B, S, T, H, W, C
         a.x2, a.act_out, a.x_split, a.cat_w1, a.cat_w2 = _p(x2), _p(act_out), x_split, cat_w[0], cat_w[1]
     a.big_tile = BIG_TILE
     a.ctx_rows = ctx_rows
+    if act_bwd is not None:
+        da, xo, dskip, dadd, a.ab_c1, a.ab_w1, a.ab_w2, a.ab_dxo_scale = act_bwd
+        a.ab_da, a.ab_xo, a.ab_dskip, a.ab_dadd = _p(da), _p(xo), _p(dskip), _p(dadd)
     if SPLITK and B * S * T * H * W <= 64 * 256 and ctx_prod_mode == 0 and ctx_rows == 0:      # few tiles (one rollout frame): lend the split-K workspace
         ws = _splitk_workspace(x.device)
         a.splitk_ws, a.splitk_ws_bytes = _p(ws), ws.numel() * 4
@@ -764,11 +773,15 @@ def _wgrad_launch(x, dy, pw, scale, B, T, H, W, Cin, CinP, Cout, CoutP, taps, xb
 
 class ConvCfg:
     """Static configuration of one conv op (not a tensor: passed through autograd untouched)."""
-    __slots__ = ("pw2", "pw3", "B", "T", "epi", "ta", "tb", "clip", "need_grad", "in_slot", "res_slot", "grad_private", "res_alias")
+    __slots__ = ("pw2", "pw3", "B", "T", "epi", "ta", "tb", "clip", "need_grad", "in_slot", "res_slot", "grad_private", "res_alias",
+                 "dgrad_slot")
 
     def __init__(self, pw2, pw3=None, B=1, T=1, epi="none", ta=0.0, tb=0.0, clip=0.0, need_grad=True, in_slot=None,
-                 res_slot=None, grad_private=False, res_alias=False):
+                 res_slot=None, grad_private=False, res_alias=False, dgrad_slot=None):
         self.pw2, self.pw3, self.B, self.T = pw2, pw3, B, T
+        # DgradSlot shared with the _ActFn whose xo this (plain 1x1) conv reads: the backward parks its data gradient there instead
+        # of launching it -- that activation's backward runs it with its own adjoint as the epilogue (skip_act_bwd_slot)
+        self.dgrad_slot = dgrad_slot
         # the caller vouches that the gradient of this op's output is a tensor nobody else reads (UNet.forward with GradSlots:
         # it comes out of the ONE backward kernel that joined the gradients of all consumers): the backward may then mask it
         # in place instead of writing a masked copy (the clip_flag aliasing protocol below).  Anywhere else -- y.backward(g)
@@ -962,7 +975,10 @@ class _ConvOp(torch.autograd.Function):
             if grp:
                 _wgrad_launch_group(grp)
         else:
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[0] and cfg.dgrad_slot is not None:
+                # parked: _ActFn.backward launches this dgrad with the mp_cat + mp_silu adjoint as its epilogue; autograd hears None
+                cfg.dgrad_slot.put((dout, pw2, (N, H, W, Cin, Co)))
+            elif ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)
                 dadd = cfg.in_slot.take() if cfg.in_slot is not None else None       # (see GradSlot)
                 if dadd is not None:             # dx = dadd + dgrad: the mp_sum epilogue with ta = tb = 1, no clip
@@ -1020,13 +1036,14 @@ def gate_coefs(gate):
 
 
 def conv(x, pw, res=None, ta=0.0, tb=0.0, clip=0.0, cscale=None, in_slot=None, res_slot=None, grad_private=False,
-         res_alias=False):
+         res_alias=False, dgrad_slot=None):
     """MPConv forward on packed weights.  Optional fused epilogues: res -> clip(ta*res + tb*conv(x));
     cscale (N,Cout) fp32 -> silu(conv(x)*cscale)/0.596.  in_slot: GradSlot of x; res_slot: GradSlot that takes d res;
-    grad_private / res_alias: see ConvCfg."""
+    grad_private / res_alias / dgrad_slot: see ConvCfg."""
     epi = "mpsum" if res is not None else ("emb_silu" if cscale is not None else "none")
+    assert dgrad_slot is None or (epi == "none" and in_slot is None and pw.taps == 1)
     cfg = ConvCfg(pw, None, epi=epi, ta=ta, tb=tb, clip=clip, need_grad=torch.is_grad_enabled(), in_slot=in_slot,
-                  res_slot=res_slot, grad_private=grad_private, res_alias=res_alias)
+                  res_slot=res_slot, grad_private=grad_private, res_alias=res_alias, dgrad_slot=dgrad_slot)
     sched = pw.param
     if getattr(pw, "members", None) and not sched.requires_grad:      # a group whose first member is frozen: any trainable member
         sched = next((m.param for m in pw.members if m.param.requires_grad), sched)     # keeps the node in the graph
@@ -1239,6 +1256,65 @@ class GradSlot:
         return g, sc
 
 
+SKIP_ACT_BWD = int(_os.environ.get("ONIRIS_SKIP_ACT_BWD", "1"))    # 0: the decoder skip conv's dgrad and act_bwd as two launches (A/B, tests)
+
+
+class DgradSlot(GradSlot):
+    """Side channel between the 1x1 skip conv of a decoder Block and the activation whose xo it reads (networks_edm2.py:230 mp_cat,
+    :73 mp_silu, :85 conv_skip).  In backward the conv does not launch its data gradient: it parks (dout, packed weight, shapes)
+    here and reports None; the activation's backward -- which autograd runs after both of its consumers -- launches that dgrad
+    with its own adjoint as the epilogue (ONIRIS_EPI_ACT_BWD): the gradient of the concatenated tensor, written once and read
+    once before, never reaches HBM.  Like every GradSlot it is checked at the end of backward: a parked dgrad nobody took (a
+    partial backward that stops short of the activation) raises instead of dropping a gradient."""
+    __slots__ = ()
+    _check_queued = False
+
+    def put(self, parked, scale=1.0):
+        assert self.g is None, "a skip conv's dgrad is parked once per backward"
+        self.g = parked
+        if not DgradSlot._check_queued:       # (a frozen net queues no WeightBank._finish: the end-of-backward check comes from here)
+            DgradSlot._check_queued = True
+            torch.autograd.Variable._execution_engine.queue_callback(DgradSlot._end_of_backward)
+
+    @staticmethod
+    def _end_of_backward():
+        DgradSlot._check_queued = False
+        GradSlot.check_all_taken()
+
+    def take(self):
+        parked, self.g = self.g, None
+        return parked
+
+
+def _skip_act_bwd_family(npos, Co, pw):
+    """Which kernel family runs the 1x1 dgrad [npos][Co] -> [npos][pw.cin] with the ONIRIS_EPI_ACT_BWD epilogue -- 'glds' / 'staged' --
+    or None where the fused launch is not offered (mirrors conv_dispatch_1x1 in csrc/conv_fwd_s1.hip).  None also where the plain
+    dgrad would sum K in another order (the few-tile kernel, split-K): the fused launch is bit-identical to the two it replaces."""
+    CinP, CoutP = pw.CinPb, pw.CoutPb
+    if (BIG_TILE >= 3 and Co % 64 == 0 and CinP == Co and Co <= 1024 and npos >= 8192 and npos * Co * 2 < (1 << 31)
+            and CoutP * CinP * 2 < (1 << 31)):                                  # conv1x1_glds_ok()
+        return "glds"
+    if -(-npos // 32) * (CoutP // 32) <= 256 or (Co >= 768 and npos <= 64 * 256):   # conv1x1_few_ok() / a split-K launch
+        return None
+    return "staged" if (CoutP % 64 == 0 or CoutP % 96 == 0) else None
+
+
+def skip_act_bwd_slot(x, skip, pw):
+    """Decided in forward: a DgradSlot when the backward of `conv(act(x, skip, want_xo=True)[0], pw)` can run as ONE launch (see
+    DgradSlot), else None -- today's two launches.  Needs: gradients wanted for x, skip and therefore xo; contiguous bf16 inputs; a
+    plain 1x1 weight of matching width; a kernel family that serves the shape."""
+    if not (SKIP_ACT_BWD and GRAD_SLOTS and torch.is_grad_enabled() and x.is_cuda and x.requires_grad and skip.requires_grad
+            and x.dtype == BF16 and skip.dtype == BF16 and x.is_contiguous() and skip.is_contiguous()):
+        return None
+    C1, C2 = x.shape[-1], skip.shape[-1]
+    if pw.taps != 1 or pw.cin != C1 + C2 or C1 % 8 != 0 or C2 % 8 != 0 or getattr(pw, "members", None):
+        return None
+    npos = x.numel() // C1
+    if _skip_act_bwd_family(npos, roundup(pw.cout, 8), pw) is None:
+        return None
+    return DgradSlot()
+
+
 class _ActFn(torch.autograd.Function):
     """(xo, a) = act(x[, skip]):  v = cat(w1*x, w2*skip); norm: v /= eps + |v|/sqrt(C); xo = v; a = silu(v)/0.596.
     in_slot / skip_slot: GradSlots of x / of skip (see GradSlot).  rs: x is resampled first (1 = 2x2 mean, 2 = nearest
@@ -1246,7 +1322,7 @@ class _ActFn(torch.autograd.Function):
     act_bwd, and in_slot then belongs to the un-resampled x."""
 
     @staticmethod
-    def forward(ctx, x, skip, w1, w2, norm, want_xo, in_slot=None, skip_slot=None, rs=0, xo_slot=None):
+    def forward(ctx, x, skip, w1, w2, norm, want_xo, in_slot=None, skip_slot=None, rs=0, xo_slot=None, dgrad_slot=None):
         _need_gpu(x)
         C1 = x.shape[-1]
         C2 = skip.shape[-1] if skip is not None else 0
@@ -1273,7 +1349,8 @@ class _ActFn(torch.autograd.Function):
         check(lib.oniris_act_fwd(_p(x), _p(skip), _p(xo), _p(a), _p(sden), npix, C1, C2, w1, w2, int(norm), rs, Ho, Wo,
                                  _stream()), "act_fwd")
         ctx.meta = (C1, C2, w1, w2, norm, npix, (*oshape, C1), skip.shape if skip is not None else None, rs, tuple(x.shape))
-        ctx.slots = (in_slot, skip_slot, xo_slot)
+        assert dgrad_slot is None or (want_xo and skip is not None and not norm and not rs)
+        ctx.slots = (in_slot, skip_slot, xo_slot, dgrad_slot)
         ctx.set_materialize_grads(False)                 # (an output whose consumer parked its gradient in xo_slot arrives as None,
                                                          #  not as a zero tensor that would then be ADDED to the parked one)
         # without norm/cat xo would just be x itself: reuse the input for the silu' evaluation
@@ -1295,7 +1372,10 @@ class _ActFn(torch.autograd.Function):
         if da is None:
             da = torch.zeros(xo.shape, dtype=BF16, device=xo.device)
         da = da.contiguous()
-        in_slot, skip_slot, xo_slot = ctx.slots
+        in_slot, skip_slot, xo_slot, dgrad_slot = ctx.slots
+        parked_dgrad = dgrad_slot.take() if dgrad_slot is not None else None
+        if parked_dgrad is not None and (dxo is not None or xo_slot is not None):
+            raise RuntimeError("a parked skip-conv dgrad is the only gradient of xo (ops.DgradSlot): another one arrived")
         dxo_scale = 1.0
         if xo_slot is not None:                          # the gradient of xo parked by its consumer, possibly as (g, scale): the
             parked, sc = xo_slot.take_scaled()           # residual gradient of an mp_sum epilogue = ta * (gradient of its output)
@@ -1311,8 +1391,15 @@ class _ActFn(torch.autograd.Function):
         if dadd is not None:
             dadd = dadd.contiguous()
             assert tuple(dadd.shape) == (tuple(xin_shape) if rs else tuple(dx.shape))
-        check(lib.oniris_act_bwd(_p(da), _p(dxo), _p(xo), _p(sden), _p(dx), _p(dskip), _p(None if rs else dadd), npix, C1, C2,
-                                 w1, w2, int(norm), dxo_scale, _stream()), "act_bwd")
+        if parked_dgrad is not None:
+            # the skip conv's data gradient with this adjoint as its epilogue: dxo = the rounded dgrad never leaves the kernel
+            dout, pw, (N_, H_, W_, Cin_, Co_) = parked_dgrad
+            assert Cin_ == C1 + C2 and N_ * H_ * W_ == npix
+            _conv_launch(dout, None, pw.wb, None, dx, None, None, 1, 1, N_, H_, W_, Co_, pw.CinPb, Cin_, pw.CoutPb, 1,
+                         epi=_lib.EPI_ACT_BWD, act_bwd=(da, xo, dskip, dadd, C1, w1, w2, 1.0))
+        else:
+            check(lib.oniris_act_bwd(_p(da), _p(dxo), _p(xo), _p(sden), _p(dx), _p(dskip), _p(None if rs else dadd), npix, C1, C2,
+                                     w1, w2, int(norm), dxo_scale, _stream()), "act_bwd")
         if rs:                                           # adjoint of the resampling (+ the second gradient of the input)
             N_, Ho, Wo = xshape[0], xshape[1], xshape[2]
             dpre = torch.empty(xin_shape, dtype=BF16, device=xo.device)
@@ -1324,14 +1411,16 @@ class _ActFn(torch.autograd.Function):
         if skip_slot is not None and dskip is not None:
             skip_slot.put(dskip)                      # joins the encoder-side gradient inside that consumer's kernel
             dskip = None
-        return dx, dskip, None, None, None, None, None, None, None, None
+        return dx, dskip, None, None, None, None, None, None, None, None, None
 
 
-def act(x, skip=None, w1=1.0, w2=1.0, norm=False, want_xo=False, in_slot=None, skip_slot=None, resample="keep", xo_slot=None):
+def act(x, skip=None, w1=1.0, w2=1.0, norm=False, want_xo=False, in_slot=None, skip_slot=None, resample="keep", xo_slot=None,
+        dgrad_slot=None):
     """resample 'down' / 'up': x is resampled first, in the same launch (the reference's Block.forward, :63).
-    xo_slot: GradSlot in which a consumer of xo parks its gradient (GradSlot.put(g, scale)) instead of handing it to autograd."""
+    xo_slot: GradSlot in which a consumer of xo parks its gradient (GradSlot.put(g, scale)) instead of handing it to autograd.
+    dgrad_slot: DgradSlot shared with the 1x1 conv that is xo's only consumer (skip_act_bwd_slot)."""
     rs = {"keep": 0, "down": 1, "up": 2}[resample]
-    return _ActFn.apply(x, skip, float(w1), float(w2), bool(norm), bool(want_xo), in_slot, skip_slot, rs, xo_slot)
+    return _ActFn.apply(x, skip, float(w1), float(w2), bool(norm), bool(want_xo), in_slot, skip_slot, rs, xo_slot, dgrad_slot)
 
 
 def resample_taps(f):

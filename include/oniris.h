@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
@@ -226,8 +226,22 @@ int oniris_sqnorm(const float* g, size_t n, float* out, oniris_stream_t stream);
  *   ONIRIS_EPI_EMB_SILU  out = v ; out2 = silu(v * escale[n][co]) / 0.596        (escale = 1 + emb_gain*emb_linear(emb))
  *   ONIRIS_EPI_MPSUM     out = clip( ta * res[n][p][co] + tb * v , +-clip )     (clip <= 0: no clipping);
  *                        out2 (optional) = v, the raw conv output (kept for the gate gradient)
+ *   ONIRIS_EPI_ACT_BWD   (added within ABI 14; 1x1, context-free, S == 1) the launch is the DATA GRADIENT of a decoder Block's 1x1
+ *                        skip conv (networks_edm2.py:85) and its epilogue is oniris_act_bwd without the pixel norm -- the adjoint of
+ *                        mp_cat + mp_silu (:230, :73) -- so the gradient of the concatenated tensor is never written or re-read.
+ *                        Cout = C1 + C2 with C1 = ab_c1 (C1, C2 multiples of 8).  Per output element (pos, c), v the conv result:
+ *                          d  = bf16(v)                                     (what ONIRIS_EPI_NONE would have stored)
+ *                          g  = ab_da[pos][c] * silu'(ab_xo[pos][c]) / 0.596 + ab_dxo_scale * d
+ *                          c <  C1:  out[pos][c]           = bf16(g * ab_w1 (+ ab_dadd[pos][c]))      out      [pos][C1]
+ *                          c >= C1:  ab_dskip[pos][c - C1] = bf16(g * ab_w2)                          ab_dskip [pos][C2]
+ *                        in the fp32 arithmetic of oniris_act_bwd, multiply-adds grouped alike: bit-identical to ONIRIS_EPI_NONE
+ *                        into a scratch tensor followed by oniris_act_bwd(da, dxo = scratch, xo, ..., dxo_scale).  Elementwise: no
+ *                        atomics, no reductions.  ab_da / ab_xo are [pos][Cout]; ab_dadd (optional) is [pos][C1].  Served by the
+ *                        LDS-DMA 1x1 kernel (csrc/conv1x1_glds.h) and by the register-staged 1x1 kernel when CoutP is a multiple of
+ *                        64 or of 96; any other launch fails with ONIRIS_EUNSUPPORTED (the caller keeps the two launches).  The
+ *                        non-temporal policy (oniris_set_ew_nt_bytes) follows the bytes of one [pos][Cout] tensor.
  */
-enum { ONIRIS_EPI_NONE = 0, ONIRIS_EPI_EMB_SILU = 1, ONIRIS_EPI_MPSUM = 2 };
+enum { ONIRIS_EPI_NONE = 0, ONIRIS_EPI_EMB_SILU = 1, ONIRIS_EPI_MPSUM = 2, ONIRIS_EPI_ACT_BWD = 3 };
 
 typedef struct OnirisConvArgs {
   const void* x;          /* bf16 [B*S*T][H][W][Cin]                                                              */
@@ -301,6 +315,13 @@ typedef struct OnirisConvArgs {
    * x, out, out2 and res hold B.  0: off (every row is a cached row).  Any other B, and a launch with ctx_rows > 0 that the
    * one-frame kernel cannot serve, fail with ONIRIS_EUNSUPPORTED.                                                          */
   int32_t ctx_rows;
+  /* ONIRIS_EPI_ACT_BWD (see the epilogue list above; unused by every other epilogue) */
+  int32_t ab_c1;          /* C1: channels [0, C1) of the result go to out, [C1, Cout) to ab_dskip                  */
+  const void* ab_da;      /* bf16 [pos][Cout]: gradient of the activation a = mp_silu(xo)                          */
+  const void* ab_xo;      /* bf16 [pos][Cout]: the concatenated tensor the forward kept                            */
+  void* ab_dskip;         /* bf16 [pos][Cout - C1]                                                                 */
+  const void* ab_dadd;    /* bf16 [pos][C1] or NULL: a second, complete gradient of x (oniris_act_bwd's dadd)      */
+  float ab_w1, ab_w2, ab_dxo_scale;
 } OnirisConvArgs;
 
 int oniris_conv_fwd(const OnirisConvArgs* args /* [host] */, oniris_stream_t stream);
