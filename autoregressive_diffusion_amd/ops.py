@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, check
+from ._lib import lib, check, OnirisError
 
 BF16 = torch.bfloat16
 
@@ -149,9 +149,19 @@ def census_start():
     check(lib.oniris_census(1), "census")
 
 
+def census_peek():
+    """The census so far, {'kernel instantiation[ [tag]]': launches}, WITHOUT stopping or clearing it (oniris_census_read works
+    while the census is on): the difference of two peeks is what the launches in between were.  Empty while no census has run."""
+    return _census_read()
+
+
 def census_stop():
     """Stop the census; returns {'kernel instantiation[ [tag]]': launches}."""
     check(lib.oniris_census(0), "census")
+    return _census_read()
+
+
+def _census_read():
     need = int(lib.oniris_census_read(None, 0))
     buf = ctypes.create_string_buffer(need)
     lib.oniris_census_read(buf, need)
@@ -603,6 +613,34 @@ def _patch_w(W):
     return 16 if W >= 16 else W
 
 
+def conv3x3_size_ok(H, W):
+    """The image sizes every 3x3 path serves -- forward, data gradient and weight gradient (conv3x3_pick_patch in
+    csrc/conv_fwd_common.h, oniris_conv_wgrad_group in csrc/conv_wgrad.hip; include/oniris.h at OnirisConvArgs.taps):
+    16-pixel-wide tiles of 8 rows (W % 16 == 0 and H % 8 == 0), or images 8, 4 or 2 pixels wide whose height is a multiple of
+    the width.  Not symmetric: 8x4 (H x W) is served and 4x8 is not -- a portrait input keeps a UNet level that a landscape one
+    of the same area loses.  One exception lies outside: the streaming FORWARD of a gated 32 -> <= 32 conv takes W % 16 == 0
+    with H % 4 == 0 (12x16), but no weight-gradient kernel does, so it is served without gradients only (_conv3x3_check)."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        return False
+    if W % 16 == 0:
+        return H % 8 == 0
+    return W in (8, 4, 2) and H % W == 0
+
+
+def _conv3x3_check(H, W, forward_only_ok, wants_grad):
+    """Refuse a 3x3 launch outside conv3x3_size_ok() BEFORE anything is launched or allocated for the backward.
+    forward_only_ok: the forward has a kernel for this size that the backward lacks (the streaming kernel at H % 4 == 0)."""
+    if conv3x3_size_ok(H, W):
+        return
+    if not forward_only_ok:
+        raise OnirisError(f"conv: unsupported image size {H}x{W} (H x W) for a 3x3 kernel: served are W % 16 == 0 with H % 8 == 0, "
+                          f"and W in (8, 4, 2) with H % W == 0")
+    if wants_grad:
+        raise OnirisError(f"conv: image size {H}x{W} (H x W) is served forward-only (streaming kernel, H % 4 == 0): the weight "
+                          f"gradient needs H % 8 == 0 -- run it under torch.no_grad() or pad the image")
+
+
 def _s2ctx_family(T, H, W, Cin, CinP, CoutP, ctx_T, coff, ctx_fill):
     """Which kernel family conv_dispatch_s2ctx() (csrc/conv_fwd_s2ctx.hip) picks for a gated conv in the DART training layout:
     'stream' (conv_stream.h), 'glds16' / 'glds8' (conv_glds.h) or 'staged' (conv_kernels.h).  Mirrors the C side."""
@@ -833,6 +871,9 @@ class _ConvOp(torch.autograd.Function):
         pw2, pw3 = cfg.pw2, cfg.pw3
         gated = pw3 is not None
         N, H, W, Cin = x.shape
+        if pw2.taps == 9 and not conv3x3_size_ok(H, W):    # refused here, before any launch: never half-way through the backward
+            _conv3x3_check(H, W, gated and _s2ctx_family(cfg.T, H, W, Cin, pw2.CinP, pw2.CoutP, cfg.T, (-2, -1), 1.0) == "stream",
+                           cfg.need_grad and any(ctx.needs_input_grad))
         Co = roundup(pw2.cout, 8)                       # channel counts in HBM are multiples of 8 (16-byte vectors)
         dev = x.device
         kw = {}

@@ -254,6 +254,15 @@ typedef struct OnirisConvArgs {
   int32_t B, S, T, H, W;
   int32_t Cin, CinP, Cout, CoutP;
   int32_t taps;           /* 9 (3x3, zero padding 1) or 1                                                         */
+  /* Image sizes of the 3x3 kernels (taps == 9), H rows x W columns -- the domain is NOT symmetric in H and W:
+   *   W % 16 == 0 and H % 8 == 0   (16-pixel-wide tiles of 8 or 16 rows), or
+   *   W == 8, 4 or 2 and H % W == 0 (whole rows; several frames per tile when the image is smaller than one).
+   * So 8x4 (H x W) is served and 4x8 is not: of two inputs of the same area the portrait one keeps a UNet level the
+   * landscape one loses.  oniris_conv_wgrad[_group] takes exactly this domain.  One forward-only exception: the
+   * streaming kernel of the DART training layout (S == 2, Cin == 32, CoutP == 32) also takes W % 16 == 0 with
+   * H % 4 == 0 (e.g. 12x16), which no weight-gradient kernel does.  Any other size returns ONIRIS_EUNSUPPORTED
+   * before anything is launched.  (The one-frame cached evaluation, csrc/conv_eval1.h, takes H % 8 == 0 and
+   * W % 8 == 0.)  The wrappers state the domain once: ops.conv3x3_size_ok(H, W).                                */
   int32_t ctx_bstride, ctx_T, coff0, coff1;
   float ctx_fill;
   int32_t epi;

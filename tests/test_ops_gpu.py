@@ -115,6 +115,12 @@ def test_weight_perm3():
                                             # ... with a ragged last 32- / 64-position tile (36 and 100 positions per image)
                                             (1, 6, 128, 64, 1), (2, 10, 64, 32, 1), (5, 10, 192, 96, 1)])
 def test_conv_plain(N, H, cin, cout, k):
+    _conv_plain_case(N, H, H, cin, cout, k)
+
+
+def _conv_plain_case(N, H, W, cin, cout, k, mark=None):
+    """Body of test_conv_plain on an H x W image (tests/test_nonsquare_gpu.py calls it with H != W).  mark: called with 'fwd' after the
+    forward launch and 'bwd' after the backward ones (the caller reads the dispatch census in between)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(2)
     kk = (k, k) if k == 3 else ((1, 1) if H > 1 else ())
@@ -122,11 +128,17 @@ def test_conv_plain(N, H, cin, cout, k):
     p = torch.nn.Parameter(w0.clone().to(DEV))
     bank, (pw,) = make_bank([p])
     bank.prepare(training=True)
-    x0 = bfr(torch.randn(N, cin, H, H))
+    x0 = bfr(torch.randn(N, cin, H, W))
     x = nhwc(x0).requires_grad_(True)
+    if mark:
+        mark("start")
     y = ops.conv(x, pw)
-    gy0 = bfr(torch.randn(N, cout, H, H))
+    if mark:
+        mark("fwd")
+    gy0 = bfr(torch.randn(N, cout, H, W))
     y.backward(nhwc(gy0))
+    if mark:
+        mark("bwd")
     bank.backward()
     wr = w0.clone().requires_grad_(True)
     xr = x0.clone().requires_grad_(True)
@@ -134,8 +146,9 @@ def test_conv_plain(N, H, cin, cout, k):
     yr = torch.nn.functional.conv2d(xr, w_eff.reshape(cout, cin, k, k), padding=k // 2)
     (yr * gy0).sum().backward()
     e = (rel(nchw(y), yr), rel(nchw(x.grad), xr.grad), rel(p.grad, wr.grad))
-    print("conv_plain", (N, H, cin, cout, k), "rel err y/dx/dw", e)
+    print("conv_plain", (N, H, cin, cout, k) if H == W else (N, H, W, cin, cout, k), "rel err y/dx/dw", e)
     assert e[0] < 1e-2 and e[1] < 1e-2 and e[2] < 2e-2
+    return e
 
 
 @pytest.mark.usefixtures("nt_policy")
@@ -156,6 +169,11 @@ def test_conv_plain(N, H, cin, cout, k):
                                             # ... and its 8x16-pixel form (B * 4 * 16 tiles of 4x16 pixels > the 512 slabs of a weight)
                                             (9, 2, 64, 32, 24)])
 def test_gated_conv_train(B, T, H, cin, cout):
+    _gated_conv_train_case(B, T, H, H, cin, cout)
+
+
+def _gated_conv_train_case(B, T, H, W, cin, cout, mark=None):
+    """Body of test_gated_conv_train on an H x W image (tests/test_nonsquare_gpu.py: H != W); mark: see _conv_plain_case."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(3)
     w2 = O.normalize(O.normalize(torch.randn(cout, cin, 3, 3)))
@@ -164,13 +182,19 @@ def test_gated_conv_train(B, T, H, cin, cout):
     bank, (pw2, pw3) = make_bank([p2, p3])
     bank.prepare(training=True)
     N = B * 2 * T
-    x0 = bfr(torch.randn(N, cin, H, H))
+    x0 = bfr(torch.randn(N, cin, H, W))
     g0 = torch.rand(N) * 0.6 + 0.05
-    gy0 = bfr(torch.randn(N, cout, H, H))
+    gy0 = bfr(torch.randn(N, cout, H, W))
     x = nhwc(x0).requires_grad_(True)
     g = g0.clone().to(DEV).requires_grad_(True)
+    if mark:
+        mark("start")
     y = ops.gated_conv_train(x, g, pw2, pw3, B, T)
+    if mark:
+        mark("fwd")
     y.backward(nhwc(gy0))
+    if mark:
+        mark("bwd")
     bank.backward()
     # oracle (fused algebraic form, fp32)
     xr, gr = x0.clone().requires_grad_(True), g0.clone().requires_grad_(True)
@@ -179,19 +203,20 @@ def test_gated_conv_train(B, T, H, cin, cout):
     e3, _ = O.weight_effective(w3r, 1.0, True)
     F = torch.nn.functional
     y2 = F.conv2d(xr, e2, padding=1)
-    clean = xr.reshape(B, 2, T, cin, H, H)[:, 0]
-    ctx = torch.cat([torch.ones(B, 2, cin, H, H), clean], 1)
-    y3 = F.conv2d(ctx[:, 0:T].reshape(B * T, cin, H, H), e3[:, :, 0], padding=1) + \
-        F.conv2d(ctx[:, 1:T + 1].reshape(B * T, cin, H, H), e3[:, :, 1], padding=1)
-    y3 = y3.reshape(B, 1, T, cout, H, H).expand(B, 2, T, cout, H, H).reshape(N, cout, H, H)
+    clean = xr.reshape(B, 2, T, cin, H, W)[:, 0]
+    ctx = torch.cat([torch.ones(B, 2, cin, H, W), clean], 1)
+    y3 = F.conv2d(ctx[:, 0:T].reshape(B * T, cin, H, W), e3[:, :, 0], padding=1) + \
+        F.conv2d(ctx[:, 1:T + 1].reshape(B * T, cin, H, W), e3[:, :, 1], padding=1)
+    y3 = y3.reshape(B, 1, T, cout, H, W).expand(B, 2, T, cout, H, W).reshape(N, cout, H, W)
     yr = O.mp_sum(y2, y3, gr)
     (yr * gy0).sum().backward()
     e = dict(y=rel(nchw(y), yr), dx=rel(nchw(x.grad), xr.grad), dw2=rel(p2.grad, w2r.grad), dw3=rel(p3.grad, w3r.grad),
              dg=rel(g.grad, gr.grad))
-    print("gated_conv", (B, T, H, cin, cout), e)
+    print("gated_conv", (B, T, H, cin, cout) if H == W else (B, T, H, W, cin, cout), e)
     # 2x the measured floors (round 4, all eleven shapes: y / dx / dw 2.0-2.5e-3 = the bf16 rounding of inputs and outputs,
     # including the 64x64-level shape with the maximum number of bf16 split-K slabs; dg 1.9-5.7e-3)
     assert e["y"] < 5e-3 and e["dx"] < 5e-3 and e["dw2"] < 5e-3 and e["dw3"] < 5e-3 and e["dg"] < 1.2e-2
+    return e
 
 
 def test_gated_conv_eval_matches_oracle():
@@ -229,27 +254,34 @@ def test_gated_conv_eval_one_frame_splitk(B, H, cin, cout, epi, monkeypatch):
     """One generated frame per sequence (the sampler's shape): the context pair comes straight from the cache tensor
     and the K loop of the few tiles is split over workgroups (OnirisConvArgs.splitk_ws).  Checked against the fp32
     reference for every epilogue, and split-K on/off must agree to the bf16 rounding of the output."""
+    _one_frame_splitk_case(B, H, H, cin, cout, epi, monkeypatch)
+
+
+def _one_frame_splitk_case(B, H, W, cin, cout, epi, monkeypatch, mark=None):
+    """Body of test_gated_conv_eval_one_frame_splitk on an H x W image; mark(name) is called in front of either launch and at the end."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(cin + H)
     w2, w3 = torch.randn(cout, cin, 3, 3), torch.randn(cout, cin, 2, 3, 3)
     p2, p3 = torch.nn.Parameter(w2.clone().to(DEV)), torch.nn.Parameter(w3.clone().to(DEV))
     bank, (pw2, pw3) = make_bank([p2, p3])
     bank.prepare(training=False)
-    x0 = bfr(torch.randn(B, cin, H, H))
-    cache0 = bfr(torch.randn(B, cin, 2, H, H))
+    x0 = bfr(torch.randn(B, cin, H, W))
+    cache0 = bfr(torch.randn(B, cin, 2, H, W))
     g0 = torch.rand(B) * 0.6 + 0.05
     x = nhwc(x0)
-    pad = cache0.permute(0, 2, 3, 4, 1).to(DEV, torch.bfloat16).contiguous()          # (B, 2, H, H, C)
+    pad = cache0.permute(0, 2, 3, 4, 1).to(DEV, torch.bfloat16).contiguous()          # (B, 2, H, W, C)
     kw, F = {}, torch.nn.functional
     if epi == "silu":
         cs0 = torch.rand(B, cout) + 0.5
         kw = dict(cscale=cs0.to(DEV))
     elif epi == "mpsum":
-        r0 = bfr(torch.randn(B, cout, H, H))
+        r0 = bfr(torch.randn(B, cout, H, W))
         kw = dict(res=nhwc(r0), ta=0.7, tb=0.5, clip=2.0)
     outs = {}
     for sk in (1, 0):
         monkeypatch.setattr(ops, "SPLITK", sk)
+        if mark:
+            mark(f"splitk={sk}")
         outs[sk] = ops.gated_conv_eval(x, g0.to(DEV), pw2, pw3, B, 1, pad, ctx_T=2, **kw).float().cpu()
     e2, _ = O.weight_effective(w2, 1.0, False)
     e3, _ = O.weight_effective(w3, 1.0, False)
@@ -262,9 +294,12 @@ def test_gated_conv_eval_one_frame_splitk(B, H, cin, cout, epi, monkeypatch):
     got = outs[1].permute(0, 3, 1, 2)[:, :cout]
     e = rel(got, yr)
     d = (outs[1] - outs[0]).abs().max().item()
-    print("one-frame eval", (B, H, cin, cout, epi), "rel", e, "split vs unsplit max abs", d)
+    print("one-frame eval", (B, H, cin, cout, epi) if H == W else (B, H, W, cin, cout, epi), "rel", e, "split vs unsplit max abs", d)
     assert e < 1e-2
     assert d <= 2.0 ** -6 * max(1.0, float(outs[0].abs().max()))          # one bf16 ulp of the largest value
+    if mark:
+        mark("end")
+    return e, d
 
 
 @pytest.mark.selfcheck
@@ -310,31 +345,36 @@ def test_one_frame_conv_kept_context_product(B, H, cin, cout, epi):
     the context-phases-only launch (mode 3), and read back by own-phases-only launches (mode 2) -- all BIT-identical to the
     plain launch, for every epilogue, and with other gate coefficients than the ones the product was stored under (the
     sampler's 31 evaluations per frame differ in exactly that).  y3 itself against the fp32 reference."""
+    _kept_context_product_case(B, H, H, cin, cout, epi)
+
+
+def _kept_context_product_case(B, H, W, cin, cout, epi):
+    """Body of test_one_frame_conv_kept_context_product on an H x W image."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(cin + H + 1)
     w2, w3 = torch.randn(cout, cin, 3, 3), torch.randn(cout, cin, 2, 3, 3)
     p2, p3 = torch.nn.Parameter(w2.clone().to(DEV)), torch.nn.Parameter(w3.clone().to(DEV))
     bank, (pw2, pw3) = make_bank([p2, p3])
     bank.prepare(training=False)
-    cache0 = bfr(torch.randn(B, cin, 2, H, H))
-    pad = cache0.permute(0, 2, 3, 4, 1).to(DEV, torch.bfloat16).contiguous()          # (B, 2, H, H, C)
-    assert ops.ctx_product_ok(H, H, cin, cout)
+    cache0 = bfr(torch.randn(B, cin, 2, H, W))
+    pad = cache0.permute(0, 2, 3, 4, 1).to(DEV, torch.bfloat16).contiguous()          # (B, 2, H, W, C)
+    assert ops.ctx_product_ok(H, W, cin, cout)
     Co = ops.roundup(cout, 8)
     F = torch.nn.functional
     kept = None
     for it in range(3):                                                               # three "evaluations": new x, new gates
-        x0, g0 = bfr(torch.randn(B, cin, H, H)), torch.rand(B) * 0.6 + 0.05
+        x0, g0 = bfr(torch.randn(B, cin, H, W)), torch.rand(B) * 0.6 + 0.05
         x, g = nhwc(x0), g0.to(DEV)
         kw = {}
         if epi == "silu":
             cs0 = torch.rand(B, cout) + 0.5
             kw = dict(cscale=cs0.to(DEV))
         elif epi == "mpsum":
-            r0 = bfr(torch.randn(B, cout, H, H))
+            r0 = bfr(torch.randn(B, cout, H, W))
             kw = dict(res=nhwc(r0), ta=0.7, tb=0.5, clip=2.0)
         plain = ops.gated_conv_eval(x, g, pw2, pw3, B, 1, pad, ctx_T=2, **kw)
         if kept is None:
-            kept = torch.full((B, H, H, Co), float("nan"), device=DEV)
+            kept = torch.full((B, H, W, Co), float("nan"), device=DEV)
             stored = ops.gated_conv_eval(x, g, pw2, pw3, B, 1, pad, ctx_T=2, ctx_prod=kept, ctx_prod_mode=1, **kw)
             assert torch.equal(plain, stored)
             only = ops.gated_conv_ctx_product(pad, pw2, pw3, B)
@@ -342,7 +382,7 @@ def test_one_frame_conv_kept_context_product(B, H, cin, cout, epi):
             e3, _ = O.weight_effective(w3, 1.0, False)
             y3 = F.conv2d(cache0[:, :, 0], e3[:, :, 0], padding=1) + F.conv2d(cache0[:, :, 1], e3[:, :, 1], padding=1)
             e = rel(kept.cpu().permute(0, 3, 1, 2)[:, :cout], y3)
-            print("kept context product", (B, H, cin, cout), "rel", e)
+            print("kept context product", (B, H, cin, cout) if H == W else (B, H, W, cin, cout), "rel", e)
             assert e < 6e-3                                                           # bf16 operands, fp32 sum, fp32 store
         before = kept.clone()
         read = ops.gated_conv_eval(x, g, pw2, pw3, B, 1, pad, ctx_T=2, ctx_prod=kept, ctx_prod_mode=2, **kw)
@@ -357,11 +397,11 @@ def test_one_frame_conv_kept_context_product(B, H, cin, cout, epi):
             yr = (0.7 * r0 + 0.5 * yr).clamp(-2.0, 2.0)
         assert rel(read.float().cpu().permute(0, 3, 1, 2)[:, :cout], yr) < 1e-2
     # a launch the one-frame kernel cannot serve must refuse the mode instead of ignoring it
-    x2 = nhwc(bfr(torch.randn(2 * B, cin, H, H)))
-    ctx2 = torch.cat([pad, x2.reshape(B, 2, H, H, cin)], 1).contiguous()
+    x2 = nhwc(bfr(torch.randn(2 * B, cin, H, W)))
+    ctx2 = torch.cat([pad, x2.reshape(B, 2, H, W, cin)], 1).contiguous()
     with pytest.raises(RuntimeError):
-        ops._conv_launch(x2, ctx2, pw2.wf, pw3.wf, torch.empty(2 * B, H, H, Co, dtype=torch.bfloat16, device=DEV),
-                         torch.ones(2 * B, device=DEV), torch.ones(2 * B, device=DEV), B, 1, 2, H, H, cin, pw2.CinP, Co, pw2.CoutP, 9,
+        ops._conv_launch(x2, ctx2, pw2.wf, pw3.wf, torch.empty(2 * B, H, W, Co, dtype=torch.bfloat16, device=DEV),
+                         torch.ones(2 * B, device=DEV), torch.ones(2 * B, device=DEV), B, 1, 2, H, W, cin, pw2.CinP, Co, pw2.CoutP, 9,
                          ctx_bstride=4, ctx_T=4, coff=(0, 1), ctx_prod=kept, ctx_prod_mode=2)
 
 
@@ -969,9 +1009,18 @@ def test_clip_flags_survive_a_second_forward_before_backward():
                                                   (False, 128, 32, True), (False, 128, 32, False), (False, 128, 24, True)])
 def test_conv_epilogues(gated, H, cout, clipped):
     """conv + (x c, mp_silu) and conv + (mp_sum with residual, clip) epilogues, forward and backward."""
+    _conv_epilogues_case(gated, H, H, cout, clipped)
+
+
+_EPILOGUE_CONFIGS = (("emb_silu", False), ("mpsum", False), ("mpsum", True))
+
+
+def _conv_epilogues_case(gated, H, W, cout, clipped, B=1, T=4, cin=32, configs=_EPILOGUE_CONFIGS, expect_alias=True, mark=None):
+    """Body of test_conv_epilogues on an H x W image (tests/test_nonsquare_gpu.py: H != W, other B / T / cin, one config at a time).
+    expect_alias: the launch takes a kernel family that reports clips, so that a private clipped mp_sum backward masks the gradient
+    in place (the register-staged kernels do not: the backward then writes a masked copy).  mark: see _conv_plain_case."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(11)
-    B, T, cin = 1, 4, 32
     N = B * 2 * T
     w2 = O.normalize(O.normalize(torch.randn(cout, cin, 3, 3)))
     w3 = O.normalize(O.normalize(torch.randn(cout, cin, 2, 3, 3)))
@@ -979,28 +1028,35 @@ def test_conv_epilogues(gated, H, cout, clipped):
     # private: the caller vouches that nobody else reads the output's gradient (ops.ConvCfg.grad_private, what UNet.forward does):
     # the clip_flag aliasing protocol -- no masked copy; the gradient is masked IN PLACE when the forward clipped.  Without it
     # (the default: y.backward(g) with the caller's own g) the gradient tensor must come back untouched.
-    for epi, private in (("emb_silu", False), ("mpsum", False), ("mpsum", True)):
+    out = []
+    for epi, private in configs:
         p2, p3 = torch.nn.Parameter(w2.clone().to(DEV)), torch.nn.Parameter(w3.clone().to(DEV))
         bank, (pw2, pw3) = make_bank([p2, p3])
         bank.prepare(training=True)
-        x0 = bfr(torch.randn(N, cin, H, H))
+        x0 = bfr(torch.randn(N, cin, H, W))
         g0 = torch.rand(N) * 0.5 + 0.05
         c0 = 1 + 0.3 * torch.randn(N, cout)
-        r0 = bfr(torch.randn(N, cout, H, H) * (200 if clipped else 2))      # large residual: the +-256 clip is active
-        gy0 = bfr(torch.randn(N, cout, H, H))
+        r0 = bfr(torch.randn(N, cout, H, W) * (200 if clipped else 2))      # large residual: the +-256 clip is active
+        gy0 = bfr(torch.randn(N, cout, H, W))
         x = nhwc(x0).requires_grad_(True)
         gate = g0.clone().to(DEV).requires_grad_(True)
         cs = c0.clone().to(DEV).requires_grad_(True)
         res = nhwc(r0).requires_grad_(True)
         kw = dict(cscale=cs) if epi == "emb_silu" else dict(res=res, ta=0.9, tb=0.4, clip=256.0)
+        if mark:
+            mark("start")
         y = (ops.gated_conv_train(x, gate, pw2, pw3, B, T, grad_private=private, **kw) if gated else
              ops.conv(x, pw2, grad_private=private, **kw) if epi == "mpsum" else ops.conv(x, pw2, **kw))
         gy = nhwc(gy0)
         gy_before = gy.clone()
+        if mark:
+            mark("fwd")
         y.backward(gy)
+        if mark:
+            mark("bwd")
         if not private:
             assert torch.equal(gy, gy_before), "the backward wrote into the caller's gradient tensor"
-        elif clipped and ops.CLIP_FLAG:
+        elif clipped and ops.CLIP_FLAG and expect_alias:
             assert not torch.equal(gy, gy_before), "aliasing protocol not exercised (expected the in-place mask)"
         # oracle
         xr, gr = x0.clone().requires_grad_(True), g0.clone().requires_grad_(True)
@@ -1010,11 +1066,11 @@ def test_conv_epilogues(gated, H, cout, clipped):
         v = F.conv2d(xr, e2, padding=1)
         if gated:
             e3, _ = O.weight_effective(w3r, 1.0, True)
-            clean = xr.reshape(B, 2, T, cin, H, H)[:, 0]
-            ctx = torch.cat([torch.ones(B, 2, cin, H, H), clean], 1)
-            y3 = F.conv2d(ctx[:, 0:T].reshape(B * T, cin, H, H), e3[:, :, 0], padding=1) + \
-                F.conv2d(ctx[:, 1:T + 1].reshape(B * T, cin, H, H), e3[:, :, 1], padding=1)
-            y3 = y3.reshape(B, 1, T, cout, H, H).expand(B, 2, T, cout, H, H).reshape(N, cout, H, H)
+            clean = xr.reshape(B, 2, T, cin, H, W)[:, 0]
+            ctx = torch.cat([torch.ones(B, 2, cin, H, W), clean], 1)
+            y3 = F.conv2d(ctx[:, 0:T].reshape(B * T, cin, H, W), e3[:, :, 0], padding=1) + \
+                F.conv2d(ctx[:, 1:T + 1].reshape(B * T, cin, H, W), e3[:, :, 1], padding=1)
+            y3 = y3.reshape(B, 1, T, cout, H, W).expand(B, 2, T, cout, H, W).reshape(N, cout, H, W)
             v = O.mp_sum(v, y3, gr)
         if epi == "emb_silu":
             yr = O.mp_silu(v * cr[:, :, None, None])
@@ -1037,6 +1093,8 @@ def test_conv_epilogues(gated, H, cout, clipped):
         print("conv epilogue", epi, "gated" if gated else "plain", "private" if private else "", e)
         assert e["y"] < 1e-2 and e["dx"] < 1.5e-2 and e["dw2"] < 2e-2
         assert all(v_ < 3e-2 for v_ in e.values()), e
+        out.append(e)
+    return out
 
 
 def test_sampler_update_matches_tensor_expressions():

@@ -36,19 +36,25 @@ def packed_weight(pw, cout, cin, kshape):
 @pytest.mark.usefixtures("nt_policy")
 @pytest.mark.parametrize("N,H,cin,cout,k", [(6, 16, 64, 64, 3), (4, 32, 32, 96, 3), (8, 8, 256, 128, 3), (9, 32, 128, 136, 1), (6, 32, 32, 96, 1)])
 def test_conv_plain_bf16_faithful(N, H, cin, cout, k):
+    _conv_plain_bf16_faithful_case(N, H, H, cin, cout, k)
+
+
+def _conv_plain_bf16_faithful_case(N, H, W, cin, cout, k):
+    """Body of test_conv_plain_bf16_faithful on an H x W image; returns (got, ref) for element-wise checks (tests/test_nonsquare_gpu.py)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(3)
     p = torch.nn.Parameter(torch.randn(cout, cin, k, k).to(DEV))
     bank, (pw,) = make_bank([p])
     bank.prepare(training=False)
     w = packed_weight(pw, cout, cin, (k, k))
-    x0 = bfr(torch.randn(N, cin, H, H))
+    x0 = bfr(torch.randn(N, cin, H, W))
     with torch.no_grad():
         y = ops.conv(nhwc(x0), pw)
     ref = bfr(F.conv2d(x0.double(), w.double(), padding=k // 2).float())
     e = sd(nchw(y)[:, :cout], ref)
-    print("conv_plain bf16-faithful", (N, H, cin, cout, k), e)
+    print("conv_plain bf16-faithful", (N, H, cin, cout, k) if H == W else (N, H, W, cin, cout, k), e)
     assert e <= TIGHT
+    return nchw(y)[:, :cout], ref
 
 
 @pytest.mark.usefixtures("nt_policy")
@@ -62,6 +68,11 @@ def test_conv_plain_bf16_faithful(N, H, cin, cout, k):
 def test_gated_conv_train_forward_bf16_faithful(B, T, H, cin, cout, epi):
     """DART training layout (edm2/conv.py:59-95): own 3x3 product + the two context taps over the CLEAN frames t-2, t-1 (padding
     frames of ones, :68), gated sum in fp32, fused epilogue -- every output the launch writes."""
+    _gated_forward_bf16_faithful_case(B, T, H, H, cin, cout, epi)
+
+
+def _gated_forward_bf16_faithful_case(B, T, H, W, cin, cout, epi):
+    """Body of test_gated_conv_train_forward_bf16_faithful on an H x W image; returns (got, ref)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(4 + cin)
     p2 = torch.nn.Parameter(torch.randn(cout, cin, 3, 3).to(DEV)); p3 = torch.nn.Parameter(torch.randn(cout, cin, 2, 3, 3).to(DEV))
@@ -69,23 +80,23 @@ def test_gated_conv_train_forward_bf16_faithful(B, T, H, cin, cout, epi):
     bank.prepare(training=False)
     w2, w3 = packed_weight(pw2, cout, cin, (3, 3)).double(), packed_weight(pw3, cout, cin, (2, 3, 3)).double()
     N = B * 2 * T
-    x0 = bfr(torch.randn(N, cin, H, H))
+    x0 = bfr(torch.randn(N, cin, H, W))
     ca, cb = torch.rand(N) * 0.5 + 0.5, torch.rand(N) * 0.5
     kw = {}
     if epi == "silu":
         cs = torch.rand(N, cout) + 0.5
         kw = dict(cscale=cs.to(DEV))
     elif epi == "mpsum":
-        r0 = bfr(torch.randn(N, cout, H, H))
+        r0 = bfr(torch.randn(N, cout, H, W))
         kw = dict(res=nhwc(r0), ta=0.7, tb=0.5, clip=2.5)
     with torch.no_grad():
         y = ops.gated_conv_train(nhwc(x0), None, pw2, pw3, B, T, coefs=(ca.to(DEV), cb.to(DEV)), **kw)
-    xs = x0.double().reshape(B, 2, T, cin, H, H)
-    clean = torch.cat([torch.ones(B, 2, cin, H, H, dtype=torch.float64), xs[:, 0]], dim=1)              # frames -2, -1, 0 .. T-1
-    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, H), w3[:, :, 0], padding=1) +
-          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, H), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, H)
-    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, H)
-    v = (ca.double().reshape(B, 2, T, 1, 1, 1) * y2 + cb.double().reshape(B, 2, T, 1, 1, 1) * y3).reshape(N, cout, H, H).float()
+    xs = x0.double().reshape(B, 2, T, cin, H, W)
+    clean = torch.cat([torch.ones(B, 2, cin, H, W, dtype=torch.float64), xs[:, 0]], dim=1)              # frames -2, -1, 0 .. T-1
+    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, W), w3[:, :, 0], padding=1) +
+          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, W), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, W)
+    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, W)
+    v = (ca.double().reshape(B, 2, T, 1, 1, 1) * y2 + cb.double().reshape(B, 2, T, 1, 1, 1) * y3).reshape(N, cout, H, W).float()
     if epi == "silu":
         z = bfr(v) * cs[:, :, None, None]                                  # (the activation sees the bf16-rounded conv output)
         ref = bfr(z * torch.sigmoid(z) / 0.596)
@@ -94,20 +105,26 @@ def test_gated_conv_train_forward_bf16_faithful(B, T, H, cin, cout, epi):
     else:
         ref = bfr(v)
     e = sd(nchw(y)[:, :cout], ref)
-    print("gated_conv_train bf16-faithful", (B, T, H, cin, cout, epi), e)
+    print("gated_conv_train bf16-faithful", (B, T, H, cin, cout, epi) if H == W else (B, T, H, W, cin, cout, epi), e)
     assert e <= TIGHT
+    return nchw(y)[:, :cout], ref
 
 
 @pytest.mark.parametrize("B,H,cin,cout", [(2, 16, 128, 128), (1, 8, 256, 256), (3, 32, 64, 64), (1, 64, 32, 32)])
 def test_gated_conv_one_frame_bf16_faithful(B, H, cin, cout):
     """The sampler's cached evaluation (edm2/conv.py:69,84-86) through the weight-streaming kernel, with the kept context product."""
+    _one_frame_bf16_faithful_case(B, H, H, cin, cout)
+
+
+def _one_frame_bf16_faithful_case(B, H, W, cin, cout):
+    """Body of test_gated_conv_one_frame_bf16_faithful on an H x W image; returns (got, ref)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(5 + cin)
     p2 = torch.nn.Parameter(torch.randn(cout, cin, 3, 3).to(DEV)); p3 = torch.nn.Parameter(torch.randn(cout, cin, 2, 3, 3).to(DEV))
     bank, (pw2, pw3) = make_bank([p2, p3])
     bank.prepare(training=False)
     w2, w3 = packed_weight(pw2, cout, cin, (3, 3)).double(), packed_weight(pw3, cout, cin, (2, 3, 3)).double()
-    x0, c0 = bfr(torch.randn(B, cin, H, H)), bfr(torch.randn(B, 2, cin, H, H))
+    x0, c0 = bfr(torch.randn(B, cin, H, W)), bfr(torch.randn(B, 2, cin, H, W))
     g = torch.rand(B) * 0.6 + 0.05
     pad = c0.permute(0, 1, 3, 4, 2).to(DEV, torch.bfloat16).contiguous()
     y3k = ops.gated_conv_ctx_product(pad, pw2, pw3, B)
@@ -117,8 +134,9 @@ def test_gated_conv_one_frame_bf16_faithful(B, H, cin, cout):
     e3 = sd(y3k.permute(0, 3, 1, 2)[:, :cout], y3)
     ref = bfr((ca.double().reshape(B, 1, 1, 1) * F.conv2d(x0.double(), w2, padding=1) + cb.double().reshape(B, 1, 1, 1) * y3).float())
     e = sd(nchw(y)[:, :cout], ref)
-    print("one-frame gated conv bf16-faithful", (B, H, cin, cout), "context product (fp32 store)", e3, "output", e)
+    print("one-frame gated conv bf16-faithful", (B, H, cin, cout) if H == W else (B, H, W, cin, cout), "context product (fp32 store)", e3, "output", e)
     assert e3 <= 2e-6 and e <= TIGHT
+    return nchw(y)[:, :cout], ref
 
 
 @pytest.mark.parametrize("kind,B,T,H,m", [("video", 2, 4, 8, 2), ("video", 1, 8, 16, 1), ("frame", 6, 1, 16, 2), ("video", 1, 16, 8, 4)])
@@ -181,6 +199,11 @@ def test_gated_conv_train_backward_bf16_faithful(B, T, H, cin, cout):
     backward kernels read: the bf16 incoming gradient, the bf16 raw output and context product the forward stored, and the
     bf16 context gradient dy3 = cb0 g[clean] + cb1 g[noised] the pre-pass writes (oniris_gconv_bwd_prep).  The weight gradient
     is not replayed here (its split-K slabs are rounded to bf16 one by one: test_gated_conv_train states its bound)."""
+    _gated_backward_bf16_faithful_case(B, T, H, H, cin, cout)
+
+
+def _gated_backward_bf16_faithful_case(B, T, H, W, cin, cout):
+    """Body of test_gated_conv_train_backward_bf16_faithful on an H x W image; returns (dx, dx_ref)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(8 + cin)
     p2 = torch.nn.Parameter(torch.randn(cout, cin, 3, 3).to(DEV)); p3 = torch.nn.Parameter(torch.randn(cout, cin, 2, 3, 3).to(DEV))
@@ -188,35 +211,39 @@ def test_gated_conv_train_backward_bf16_faithful(B, T, H, cin, cout):
     bank.prepare(training=True)
     w2, w3 = packed_weight(pw2, cout, cin, (3, 3)).double(), packed_weight(pw3, cout, cin, (2, 3, 3)).double()
     N = B * 2 * T
-    x0, g0 = bfr(torch.randn(N, cin, H, H)), bfr(torch.randn(N, cout, H, H))
+    x0, g0 = bfr(torch.randn(N, cin, H, W)), bfr(torch.randn(N, cout, H, W))
     ca0, cb0 = torch.rand(N) * 0.5 + 0.5, torch.rand(N) * 0.5
     x = nhwc(x0).requires_grad_(True)
     ca, cb = ca0.to(DEV).requires_grad_(True), cb0.to(DEV).requires_grad_(True)
     y = ops.gated_conv_train(x, None, pw2, pw3, B, T, coefs=(ca, cb))
     y.backward(nhwc(g0))
     # forward quantities as stored
-    xs = x0.double().reshape(B, 2, T, cin, H, H)
-    clean = torch.cat([torch.ones(B, 2, cin, H, H, dtype=torch.float64), xs[:, 0]], dim=1)
-    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, H), w3[:, :, 0], padding=1) +
-          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, H), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, H)
-    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, H)
+    xs = x0.double().reshape(B, 2, T, cin, H, W)
+    clean = torch.cat([torch.ones(B, 2, cin, H, W, dtype=torch.float64), xs[:, 0]], dim=1)
+    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, W), w3[:, :, 0], padding=1) +
+          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, W), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, W)
+    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, W)
     cav, cbv = ca0.double().reshape(B, 2, T, 1, 1, 1), cb0.double().reshape(B, 2, T, 1, 1, 1)
     raw_s, y3_s = bfr((cav * y2 + cbv * y3).float()).double(), bfr(y3.float()).double()       # what the forward wrote (bf16)
-    g = g0.double().reshape(B, 2, T, cout, H, H)
+    g = g0.double().reshape(B, 2, T, cout, H, W)
     # gate-coefficient gradients: d ca = <g, y2>, d cb = <g, y3> with y2 recovered from the stored pair
     dca_ref = (g * ((raw_s - cbv * y3_s) / cav)).sum(dim=(3, 4, 5)).reshape(N)
     dcb_ref = (g * y3_s).sum(dim=(3, 4, 5)).reshape(N)
     # context gradient as stored (bf16), then the data gradient
-    dy3 = bfr((cb0.reshape(B, 2, T, 1, 1, 1) * g0.reshape(B, 2, T, cout, H, H)).sum(dim=1)).double()      # (B, T, cout, H, W)
-    own = F.conv_transpose2d((cav * g).reshape(N, cout, H, H), w2, padding=1).reshape(B, 2, T, cin, H, H)
-    dpad = torch.cat([dy3, torch.zeros(B, 2, cout, H, H, dtype=torch.float64)], dim=1)                      # frames T, T+1: nothing
-    dctx = (F.conv_transpose2d(dpad[:, 2:T + 2].reshape(B * T, cout, H, H), w3[:, :, 0], padding=1) +
-            F.conv_transpose2d(dpad[:, 1:T + 1].reshape(B * T, cout, H, H), w3[:, :, 1], padding=1)).reshape(B, T, cin, H, H)
+    # (B, T, cout, H, W); in the kernel's own fp32 order -- acc = fma(cb[clean], g[clean], 0), acc = fma(cb[noised], g[noised], acc)
+    # (gconv_bwd_prep_kernel, csrc/weights.hip) -- so that the rounding to bf16 sees the same fp32 value, element by element
+    cbd, gd = cb0.double().reshape(B, 2, T, 1, 1, 1), g0.double().reshape(B, 2, T, cout, H, W)
+    dy3 = bfr((cbd[:, 1] * gd[:, 1] + (cbd[:, 0] * gd[:, 0]).float().double()).float()).double()
+    own = F.conv_transpose2d((cav * g).reshape(N, cout, H, W), w2, padding=1).reshape(B, 2, T, cin, H, W)
+    dpad = torch.cat([dy3, torch.zeros(B, 2, cout, H, W, dtype=torch.float64)], dim=1)                      # frames T, T+1: nothing
+    dctx = (F.conv_transpose2d(dpad[:, 2:T + 2].reshape(B * T, cout, H, W), w3[:, :, 0], padding=1) +
+            F.conv_transpose2d(dpad[:, 1:T + 1].reshape(B * T, cout, H, W), w3[:, :, 1], padding=1)).reshape(B, T, cin, H, W)
     own[:, 0] += dctx
-    dx_ref = bfr(own.reshape(N, cin, H, H).float())
+    dx_ref = bfr(own.reshape(N, cin, H, W).float())
     e = (sd(nchw(x.grad), dx_ref), sd(ca.grad, dca_ref), sd(cb.grad, dcb_ref))
-    print("gated_conv_train backward bf16-faithful", (B, T, H, cin, cout), "dx, dca, dcb", e)
+    print("gated_conv_train backward bf16-faithful", (B, T, H, cin, cout) if H == W else (B, T, H, W, cin, cout), "dx, dca, dcb", e)
     assert max(e) <= TIGHT
+    return nchw(x.grad), dx_ref
 
 
 @pytest.mark.parametrize("kind,B,T,H,m", [("video", 2, 4, 8, 2), ("video", 1, 8, 16, 1), ("frame", 6, 1, 16, 2), ("video", 1, 16, 8, 4)])
@@ -264,6 +291,11 @@ def test_gated_conv_train_backward_epilogues_bf16_faithful(B, T, H, cin, cout, e
     (networks_edm2.py:78-79) and mp_sum + clip (:87-93), the latter with the clip never reached (aliasing protocol: no dout is
     written, dgrad reads g with tb * ca) and reached (g masked in place).  Replayed on the stored bf16 tensors: raw conv output,
     context product, clipped output; dout and dy3 rounded to bf16 where the pre-pass stores them."""
+    _gated_backward_epilogues_bf16_faithful_case(B, T, H, H, cin, cout, epi)
+
+
+def _gated_backward_epilogues_bf16_faithful_case(B, T, H, W, cin, cout, epi):
+    """Body of test_gated_conv_train_backward_epilogues_bf16_faithful on an H x W image; returns (dx, dx_ref)."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(10 + cin + len(epi))
     p2 = torch.nn.Parameter(torch.randn(cout, cin, 3, 3).to(DEV)); p3 = torch.nn.Parameter(torch.randn(cout, cin, 2, 3, 3).to(DEV))
@@ -271,7 +303,7 @@ def test_gated_conv_train_backward_epilogues_bf16_faithful(B, T, H, cin, cout, e
     bank.prepare(training=True)
     w2, w3 = packed_weight(pw2, cout, cin, (3, 3)).double(), packed_weight(pw3, cout, cin, (2, 3, 3)).double()
     N = B * 2 * T
-    x0, g0 = bfr(torch.randn(N, cin, H, H)), bfr(torch.randn(N, cout, H, H))
+    x0, g0 = bfr(torch.randn(N, cin, H, W)), bfr(torch.randn(N, cout, H, W))
     ca0, cb0 = torch.rand(N) * 0.5 + 0.5, torch.rand(N) * 0.5
     x = nhwc(x0).requires_grad_(True)
     ca, cb = ca0.to(DEV).requires_grad_(True), cb0.to(DEV).requires_grad_(True)
@@ -281,20 +313,20 @@ def test_gated_conv_train_backward_epilogues_bf16_faithful(B, T, H, cin, cout, e
         cs = cs0.to(DEV).requires_grad_(True)
         y = ops.gated_conv_train(x, None, pw2, pw3, B, T, coefs=(ca, cb), cscale=cs)
     else:
-        r0 = bfr(torch.randn(N, cout, H, H))
+        r0 = bfr(torch.randn(N, cout, H, W))
         res = nhwc(r0).requires_grad_(True)
         y = ops.gated_conv_train(x, None, pw2, pw3, B, T, coefs=(ca, cb), res=res, ta=ta, tb=tb, clip=clip, grad_private=True)
     y.backward(nhwc(g0).clone())
     # forward quantities as stored
-    xs = x0.double().reshape(B, 2, T, cin, H, H)
-    clean = torch.cat([torch.ones(B, 2, cin, H, H, dtype=torch.float64), xs[:, 0]], dim=1)
-    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, H), w3[:, :, 0], padding=1) +
-          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, H), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, H)
-    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, H)
+    xs = x0.double().reshape(B, 2, T, cin, H, W)
+    clean = torch.cat([torch.ones(B, 2, cin, H, W, dtype=torch.float64), xs[:, 0]], dim=1)
+    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, W), w3[:, :, 0], padding=1) +
+          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, W), w3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, W)
+    y2 = F.conv2d(x0.double(), w2, padding=1).reshape(B, 2, T, cout, H, W)
     cav, cbv = ca0.double().reshape(B, 2, T, 1, 1, 1), cb0.double().reshape(B, 2, T, 1, 1, 1)
     v = cav * y2 + cbv * y3
     raw_s, y3_s = bfr(v.float()).double(), bfr(y3.float()).double()
-    g = g0.double().reshape(B, 2, T, cout, H, H)
+    g = g0.double().reshape(B, 2, T, cout, H, W)
     extra = {}
     if epi == "silu":
         c6 = cs0.double().reshape(B, 2, T, cout, 1, 1)
@@ -308,22 +340,27 @@ def test_gated_conv_train_backward_epilogues_bf16_faithful(B, T, H, cin, cout, e
         mask = (out_s.abs() < clip).double()
         assert (mask.mean().item() < 0.98) == (epi == "mpsum_clipped")
         dv = tb * g * mask
-        extra["dres"] = sd(nchw(res.grad), bfr((ta * g * mask).reshape(N, cout, H, H).float()))
+        extra["dres"] = sd(nchw(res.grad), bfr((ta * g * mask).reshape(N, cout, H, W).float()))
     dca_ref = (dv * ((raw_s - cbv * y3_s) / cav)).sum(dim=(3, 4, 5)).reshape(N)
     dcb_ref = (dv * y3_s).sum(dim=(3, 4, 5)).reshape(N)
-    dy3 = bfr((cbv * dv).sum(dim=1).float()).double()                                                        # (B, T, cout, H, W)
+    # (B, T, cout, H, W), in the kernel's own fp32 order (gconv_bwd_fused_kernel, csrc/weights.hip): dr = fp32(dv), acc = fma(cb[clean],
+    # dr[clean], 0), acc = fma(cb[noised], dr[noised], acc) -- so that the rounding to bf16 sees the same fp32 value, element by element
+    dr = dv.float().double()
+    dy3 = bfr((cbv[:, 1] * dr[:, 1] + (cbv[:, 0] * dr[:, 0]).float().double()).float()).double()
     if epi == "silu" or epi == "mpsum_clipped":
         # dout is a stored bf16 tensor (silu: written by the pre-pass; clipped: g masked in place, scaled by the coefficient)
         dsrc = dv if epi == "silu" else g * mask * tb
     else:
         dsrc = g * tb                                                                                         # read as g with tb * ca
-    own = F.conv_transpose2d((cav * dsrc).reshape(N, cout, H, H), w2, padding=1).reshape(B, 2, T, cin, H, H)
-    dpad = torch.cat([dy3, torch.zeros(B, 2, cout, H, H, dtype=torch.float64)], dim=1)
-    own[:, 0] += (F.conv_transpose2d(dpad[:, 2:T + 2].reshape(B * T, cout, H, H), w3[:, :, 0], padding=1) +
-                  F.conv_transpose2d(dpad[:, 1:T + 1].reshape(B * T, cout, H, H), w3[:, :, 1], padding=1)).reshape(B, T, cin, H, H)
-    e = dict(dx=sd(nchw(x.grad), bfr(own.reshape(N, cin, H, H).float())), dca=sd(ca.grad, dca_ref), dcb=sd(cb.grad, dcb_ref), **extra)
-    print("gated_conv_train backward epilogue bf16-faithful", (B, T, H, cin, cout, epi), e)
+    own = F.conv_transpose2d((cav * dsrc).reshape(N, cout, H, W), w2, padding=1).reshape(B, 2, T, cin, H, W)
+    dpad = torch.cat([dy3, torch.zeros(B, 2, cout, H, W, dtype=torch.float64)], dim=1)
+    own[:, 0] += (F.conv_transpose2d(dpad[:, 2:T + 2].reshape(B * T, cout, H, W), w3[:, :, 0], padding=1) +
+                  F.conv_transpose2d(dpad[:, 1:T + 1].reshape(B * T, cout, H, W), w3[:, :, 1], padding=1)).reshape(B, T, cin, H, W)
+    dx_ref = bfr(own.reshape(N, cin, H, W).float())
+    e = dict(dx=sd(nchw(x.grad), dx_ref), dca=sd(ca.grad, dca_ref), dcb=sd(cb.grad, dcb_ref), **extra)
+    print("gated_conv_train backward epilogue bf16-faithful", (B, T, H, cin, cout, epi) if H == W else (B, T, H, W, cin, cout, epi), e)
     assert max(e.values()) <= TIGHT
+    return nchw(x.grad), dx_ref
 
 
 @pytest.mark.usefixtures("nt_policy")
@@ -390,6 +427,11 @@ def test_gated_conv_weight_gradient_integer_exact(B, T, H, cin, cout, dens):
     coefficient or a slab rounding shows up at full size.  Compared with fp64 autograd through the reference's forced weight
     normalisation (conv.py:14-21); the bound is fp32 rounding of the normalisation backward alone.  Shapes: the streaming kernel of
     the 32-channel level (several segments), the LDS-DMA kernels for 16x16 and 8x8 tiles, ragged channel counts."""
+    _gated_wgrad_integer_exact_case(B, T, H, H, cin, cout, dens)
+
+
+def _gated_wgrad_integer_exact_case(B, T, H, W, cin, cout, dens, mark=None):
+    """Body of test_gated_conv_weight_gradient_integer_exact on an H x W image; mark('fwd') / mark('bwd') after the forward / backward launches."""
     from autoregressive_diffusion_amd import ops
     gen = torch.Generator().manual_seed(12 + cin + H)
     w2, w3 = torch.randn(cout, cin, 3, 3, generator=gen), torch.randn(cout, cin, 2, 3, 3, generator=gen)
@@ -397,30 +439,37 @@ def test_gated_conv_weight_gradient_integer_exact(B, T, H, cin, cout, dens):
     bank, (pw2, pw3) = make_bank([p2, p3])
     bank.prepare(training=True)
     N = B * 2 * T
-    x0, g0 = _ternary((N, cin, H, H), dens, gen), _ternary((N, cout, H, H), dens, gen)
+    x0, g0 = _ternary((N, cin, H, W), dens, gen), _ternary((N, cout, H, W), dens, gen)
     ca0 = torch.tensor([1.0, 2.0, 0.5])[torch.randint(0, 3, (N,), generator=gen)]
     cb0 = torch.tensor([1.0, 0.5])[torch.randint(0, 2, (N,), generator=gen)]
     x = nhwc(x0).requires_grad_(True)
+    if mark:
+        mark("start")
     y = ops.gated_conv_train(x, None, pw2, pw3, B, T, coefs=(ca0.to(DEV), cb0.to(DEV)))
+    if mark:
+        mark("fwd")
     y.backward(nhwc(g0))
+    if mark:
+        mark("bwd")
     bank.backward()
     # fp64 reference through the forced normalisation
     r2, r3 = w2.double().requires_grad_(True), w3.double().requires_grad_(True)
     e2, _ = O.weight_effective(r2, 1.0, training=True)
     e3, _ = O.weight_effective(r3, 1.0, training=True)
-    xs = x0.double().reshape(B, 2, T, cin, H, H)
-    clean = torch.cat([torch.ones(B, 2, cin, H, H, dtype=torch.float64), xs[:, 0]], dim=1)
-    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, H), e3[:, :, 0], padding=1) +
-          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, H), e3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, H)
-    y2 = F.conv2d(x0.double(), e2, padding=1).reshape(B, 2, T, cout, H, H)
+    xs = x0.double().reshape(B, 2, T, cin, H, W)
+    clean = torch.cat([torch.ones(B, 2, cin, H, W, dtype=torch.float64), xs[:, 0]], dim=1)
+    y3 = (F.conv2d(clean[:, 0:T].reshape(B * T, cin, H, W), e3[:, :, 0], padding=1) +
+          F.conv2d(clean[:, 1:T + 1].reshape(B * T, cin, H, W), e3[:, :, 1], padding=1)).reshape(B, 1, T, cout, H, W)
+    y2 = F.conv2d(x0.double(), e2, padding=1).reshape(B, 2, T, cout, H, W)
     v = ca0.double().reshape(B, 2, T, 1, 1, 1) * y2 + cb0.double().reshape(B, 2, T, 1, 1, 1) * y3
     (v * g0.double().reshape(v.shape)).sum().backward()
     rel64 = lambda a, b: ((a.double().cpu() - b).norm() / b.norm()).item()
     e = (rel64(p2.grad, r2.grad), rel64(p3.grad, r3.grad))
     worst = max(((p2.grad.double().cpu() - r2.grad).abs().max() / r2.grad.abs().max()).item(),
                 ((p3.grad.double().cpu() - r3.grad).abs().max() / r3.grad.abs().max()).item())
-    print("gated conv weight gradient, integer-exact inputs", (B, T, H, cin, cout), "rel L2 dW2, dW3", e, "worst element / max", worst)
+    print("gated conv weight gradient, integer-exact inputs", (B, T, H, cin, cout) if H == W else (B, T, H, W, cin, cout), "rel L2 dW2, dW3", e, "worst element / max", worst)
     assert max(e) <= 2e-6 and worst <= 1e-5
+    return e, worst
 
 
 @pytest.mark.parametrize("N,H,cin,cout,k,dens", [(16, 32, 128, 256, 1, 0.05), (9, 32, 64, 96, 1, 0.08), (64, 64, 32, 96, 1, 0.03), (12, 16, 64, 64, 3, 0.12),
@@ -428,6 +477,11 @@ def test_gated_conv_weight_gradient_integer_exact(B, T, H, cin, cout, dens):
 def test_plain_conv_weight_gradient_integer_exact(N, H, cin, cout, k, dens):
     """The same for MPConv (1x1 through the LDS-DMA GEMM weight-gradient kernel and the small-channel fallback, plain 3x3 of the 2-D
     steps, a linear layer): sparse ternary x and dy, fp64 autograd through the forced normalisation."""
+    _plain_wgrad_integer_exact_case(N, H, H, cin, cout, k, dens)
+
+
+def _plain_wgrad_integer_exact_case(N, H, W, cin, cout, k, dens, mark=None):
+    """Body of test_plain_conv_weight_gradient_integer_exact on an H x W image; mark: see _gated_wgrad_integer_exact_case."""
     from autoregressive_diffusion_amd import ops
     gen = torch.Generator().manual_seed(13 + cin + H)
     kk = (k, k) if H > 1 else ()
@@ -435,18 +489,25 @@ def test_plain_conv_weight_gradient_integer_exact(N, H, cin, cout, k, dens):
     p = torch.nn.Parameter(w.clone().to(DEV))
     bank, (pw,) = make_bank([p])
     bank.prepare(training=True)
-    x0, g0 = _ternary((N, cin, H, H), dens, gen), _ternary((N, cout, H, H), dens, gen)
+    x0, g0 = _ternary((N, cin, H, W), dens, gen), _ternary((N, cout, H, W), dens, gen)
     x = nhwc(x0).requires_grad_(True)
+    if mark:
+        mark("start")
     y = ops.conv(x, pw)
+    if mark:
+        mark("fwd")
     y.backward(nhwc(g0))
+    if mark:
+        mark("bwd")
     bank.backward()
     r = w.double().requires_grad_(True)
     e_, _ = O.weight_effective(r, 1.0, training=True)
     (F.conv2d(x0.double(), e_.reshape(cout, cin, k, k), padding=k // 2) * g0.double()).sum().backward()
     e = ((p.grad.double().cpu() - r.grad).norm() / r.grad.norm()).item()
     worst = ((p.grad.double().cpu() - r.grad).abs().max() / r.grad.abs().max()).item()
-    print("plain conv weight gradient, integer-exact inputs", (N, H, cin, cout, k), "rel L2", e, "worst element / max", worst)
+    print("plain conv weight gradient, integer-exact inputs", (N, H, cin, cout, k) if H == W else (N, H, W, cin, cout, k), "rel L2", e, "worst element / max", worst)
     assert e <= 2e-6 and worst <= 1e-5
+    return e, worst
 
 
 @pytest.mark.parametrize("B,P,m,nk,kind", [(1, 64, 4, 10, "decode"), (2, 64, 4, 40, "decode"), (1, 256, 2, 12, "decode"), (2, 64, 2, 6, "prefill"),
