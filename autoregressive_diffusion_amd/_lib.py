@@ -191,6 +191,20 @@ _SIGS = {
                                 c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "oniris_vae_latents": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int64, c_int64, c_int64, c_void_p]),
+    "oniris_vae_train_res_a": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_void_p, c_void_p]),
+    "oniris_vae_train_res_b": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_void_p]),
+    "oniris_vae_res_b_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "oniris_vae_res_a_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "oniris_vae_conv3_wgrad_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_int, c_void_p]),
+    "oniris_vae_slab_sum_bwd": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "oniris_vae_lin_dx_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p]),
+    "oniris_vae_lin_dw_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_void_p]),
 }
 EXPORTED = sorted(_SIGS)
 

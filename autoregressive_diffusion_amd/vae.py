@@ -1,5 +1,5 @@
-"""VAE on HIP kernels, both directions: RGB frames -> latents and generated latents -> RGB frames on the GPU (reference:
-edm2/vae/vae.py).
+"""VAE on HIP kernels: RGB frames -> latents, generated latents -> RGB frames, and the training forward / backward, on the GPU
+(reference: edm2/vae/vae.py).
 
 `VAE` has the reference's constructor, `kwargs` and state_dict keys (encoder and decoder), so a checkpoint of the reference's
 VAE loads here unchanged and round-trips.  Encoder and decoder run for inference, in fp32 like the reference: `encode`,
@@ -11,7 +11,9 @@ Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up`
 plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
 ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
 
-`forward` (VAE training) is not implemented here, and the encoder has no CPU path: use the reference's `edm2.vae` for those.
+`forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
+enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
+csrc/vae_train.hip (vae_train.py).  Nothing here has a CPU path: use the reference's `edm2.vae` for that.
 """
 import ctypes
 import inspect
@@ -21,10 +23,10 @@ import torch
 from torch import nn
 
 from . import _lib
-from .edm2.utils import BetterModule, MPFourier
+from .edm2.utils import BetterModule, MPFourier, bmult
 
 MAX_WIDTH = 64
-_REF = "the reference's edm2.vae (this package runs the VAE on HIP kernels only, for inference)"
+_REF = "the reference's edm2.vae (this package runs the VAE on HIP kernels only)"
 
 
 def _stream():
@@ -33,6 +35,13 @@ def _stream():
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def _has_tensor(cache):
+    """Whether a (nested) cache dict holds anything but None leaves."""
+    if isinstance(cache, dict):
+        return any(_has_tensor(v) for v in cache.values())
+    return cache is not None
 
 
 def _nch(c):
@@ -136,7 +145,7 @@ class EncoderDecoder(nn.Module):
 
 
 class VAE(BetterModule):
-    """The reference's VAE (vae.py:207-318) with its decoder on HIP kernels.  Supported: every decoder width <= 64, time and
+    """The reference's VAE (vae.py:207-318) on HIP kernels.  Supported: every decoder width <= 64, time and
     spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises NotImplementedError
     here (the Counter-Strike VAE, 512 channels, is out of scope)."""
 
@@ -162,9 +171,53 @@ class VAE(BetterModule):
         args, _, _, values = inspect.getargvalues(frame)
         self.kwargs = {arg: values[arg] for arg in args if arg != "self"}
 
-    # ---- not implemented here
-    def forward(self, x, t=0.1, cache=None):
-        raise NotImplementedError(f"VAE.forward (encode + decode, training): use {_REF}")
+    # ---- encode + mix + decode (vae.py:228-237)
+    def forward(self, x, t=0.1, cache=None, *, t_sample=None, noise=None):
+        """x (B, 3, T, H, W) in [-1, 1] -> (r_mean, r_logvar, mean, cache): mean = encode(x), t_b = rand(B) t,
+        z = mean (1 - t_b) + randn_like(mean) t_b, (r_mean, r_logvar) = decode(z, t_b); cache = {"encoder": ..., "decoder": ...}.
+        t_sample (B,) replaces rand(B) t and noise (the shape of mean) replaces randn_like(mean) (reproducible draws, like the
+        sampler's noise= / churn_noise=); otherwise they are drawn on x.device in the reference's order.
+
+        In training mode with grad enabled this is the differentiable path (vae_train.py, csrc/vae_train.hip): the three outputs
+        carry a grad_fn, and a loss on them followed by .backward() fills .grad of every VAE parameter that requires grad.  As in
+        the reference's training mode, the time prefix of every group-causal conv is the first g activated input frames,
+        detached, and every leaf of the returned cache is None; a cache with tensors in it raises ValueError (training through a
+        carried cache is not supported), and so does an x that requires grad (frames are data: no gradient is produced for them).
+
+        In eval mode or under torch.no_grad() it is encode -> mix -> decode on the inference kernels: real caches are carried
+        under cache["encoder"] / cache["decoder"] and the outputs have no grad_fn."""
+        self._check_frames("forward", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
+        B = x.shape[0]
+        if t_sample is not None and (t_sample.dim() != 1 or t_sample.shape[0] != B):
+            raise ValueError(f"VAE.forward: t_sample must be ({B},), got {tuple(t_sample.shape)}")
+        lat = (B, self.latent_channels, x.shape[2] // int(self.time_compression), x.shape[3] // int(self.spatial_compression),
+               x.shape[4] // int(self.spatial_compression))
+        if noise is not None and tuple(noise.shape) != lat:
+            raise ValueError(f"VAE.forward: noise must have the shape of mean {lat}, got {tuple(noise.shape)}")
+        dev = self._encoder_device("forward", x)
+        training = self.training and torch.is_grad_enabled()
+        cache = {} if cache is None else cache
+        if training and x.requires_grad:
+            raise ValueError("VAE.forward: x requires grad, but no gradient with respect to the frames is produced")
+        if training and _has_tensor(cache):
+            raise ValueError("VAE.forward: a non-empty cache on the training path (training through a carried cache is not supported)")
+        t_b = (torch.rand(B, device=dev, dtype=torch.float32) * t if t_sample is None
+               else t_sample.detach().to(device=dev, dtype=torch.float32))
+        if noise is not None:
+            noise = noise.detach().to(device=dev, dtype=torch.float32)
+        if training:
+            from . import vae_train
+            r_mean, r_logvar, mean = vae_train.run(self, x, t_b, noise)
+            leaves = lambda ed: {f"encoder_block_{i}": {f"res_block_{j}": {"conv3d_res0": None} for j in range(len(blk.res_blocks))}
+                                 for i, blk in enumerate(ed.encoder_blocks)}
+            return r_mean, r_logvar, mean, {"encoder": leaves(self.encoder), "decoder": leaves(self.decoder)}
+        with torch.no_grad():
+            mean, enc_cache = self.encode(x, cache.get("encoder"))
+            if noise is None:
+                noise = torch.randn_like(mean)
+            z = bmult(mean, 1 - t_b) + bmult(noise, t_b)
+            r_mean, r_logvar, dec_cache = self.decode(z, t_b, cache.get("decoder"))
+        return r_mean, r_logvar, mean, {"encoder": enc_cache, "decoder": dec_cache}
 
     # ---- packed device weights
     def _pack(self, device):

@@ -682,6 +682,52 @@ int oniris_vae_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t 
 int oniris_vae_latents(const float* x, int B, int T, int H, int W, int C, const float* mean, const float* std, float* out,
                        int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, oniris_stream_t stream);
 
+/* VAE training (reference: VAE.forward vae.py:228-237 in training mode), added within ABI 14, fp32 throughout, channels-last
+ * activations.  csrc/vae_train.hip.  The training forward runs the inference launches of the 1x1 stages (oniris_vae_down / _up /
+ * _out) and, per ResBlock, these two instead of oniris_vae_res_a / _res_b; it keeps one tensor per ResBlock beyond the block
+ * input x: a, the raw output of the group-causal conv.  y = SiLU(RMS(x) (1 + scale) + shift) and u = SiLU(RMS(a)) are recomputed
+ * wherever they are an operand.  Without a cache the time prefix of the group-causal conv is the first g frames of y, detached
+ * (vae.py:43-44): no gradient flows through it.
+ * oniris_vae_train_res_a: a = bias + conv_(2g,3,3)([first g frames of y] ++ y); x, a [B][T][H][W][C]; emb [B][2C] scale | shift or
+ *   NULL (the encoder); w / bias / (nch, gpt) packed as for oniris_vae_res_a, and summed in the same order: SiLU(RMS(a)) is bit
+ *   for bit what oniris_vae_res_a writes.
+ * oniris_vae_train_res_b: out = res + bias + conv_(3,3)(SiLU(RMS(a))); w / bias packed as for oniris_vae_res_b.
+ * oniris_vae_res_b_bwd: da = the adjoint of SiLU(RMS(.)) at a, applied to conv_(3,3)^T(dout); wd packed [9][C][nch] =
+ *   conv3d1.weight[co][ci][2 - ky][2 - kx] at [ky 3 + kx][co][ci] (zero for ci >= C).
+ * oniris_vae_res_a_bwd: dx = dout + the adjoint of SiLU(RMS(.)(1 + scale) + shift) at x, applied to conv_(2g,3,3)^T(da).  Frame
+ *   q g + r of y receives 2g frames of da, q g ... q g + 2g - 1 (zero beyond T): tap j < g is output frame gl = j of its own group
+ *   through time tap g + r, tap j >= g is output frame gl = j - g of the next group through time tap r.  wd packed
+ *   [g / gpt][2g][9][C][nch gpt] with [gq][j][ky 3 + kx][c][ci gpt + rl] = conv3d.weight[c g + gl][ci][kt][2 - ky][2 - kx], r =
+ *   gq gpt + rl.  emb_part (or NULL; needs emb): [n_part][B][2C] sums per workgroup of d scale | d shift, n_part =
+ *   ceil(H / 16) ceil(W / 16) T / gpt; their sum over n_part (oniris_vae_slab_sum_bwd) is d emb.
+ * oniris_vae_conv3_wgrad_bwd: weight and bias gradient of either conv.  causal = 1 (conv A): xin = x with emb, dA = da, slab
+ *   element [kt][gl][ky][kx][ci][c] = d conv3d.weight[c g + gl][ci][kt][ky][kx], then [gl][c] = d bias[c g + gl]; causal = 0 (conv
+ *   B, g = 1): xin = a, emb NULL, dA = dout.  slab [nslab][2g g 9 C C + g C] (conv B: [9 C C + C]) zeroed by the caller:
+ *   workgroup s adds the work items (b, time group, 16x16 tile) s, s + nslab, ... into slab s in that order.
+ * oniris_vae_slab_sum_bwd: out[e] = slab[0][e] + slab[1][e] + ... + slab[nslab - 1][e], in that order.
+ * oniris_vae_lin_dx_bwd / oniris_vae_lin_dw_bwd: the 1x1 stages as linear maps over the rows (b, t, h, w) of a coarse grid.  A view
+ *   (C, tc, sc) of a channels-last tensor [B][T tc][H sc][W sc][C] is the matrix [row][((tci sc + hci) sc + wci) C + c] (the
+ *   rearrangements of vae.py:157-164; tc = sc = 1: the tensor itself).  dx: dx_view[row][k] = sum_n dy_view[row][n] wc[n][k]
+ *   (wc [N][K]: the conv weight plus, where the stage has one, the matrix of the channel-area residual).  dw: slab [nslab][N][K + 1]
+ *   zeroed by the caller, [n][k] = sum_row dy_view[row][n] x_view[row][k] and [n][K] = sum_row dy_view[row][n] (the bias).
+ *   down: x_view = the input (Cin, tc, sc), dy plain; up: x plain, dy_view = the output (C, tc, sc); out: both plain.
+ * Every sum has a fixed order and nothing is accumulated with atomics: two runs give the same bits.                          */
+int oniris_vae_train_res_a(const float* x, const float* emb, const float* w, const float* bias, int B, int T, int H, int W, int C,
+                           int g, int nch, int gpt, float* a_out, oniris_stream_t stream);
+int oniris_vae_train_res_b(const float* a_in, const float* res, const float* w, const float* bias, int B, int T, int H, int W,
+                           int C, int nch, float* out, oniris_stream_t stream);
+int oniris_vae_res_b_bwd(const float* dout, const float* a_in, const float* wd, int B, int T, int H, int W, int C, int nch,
+                         float* da, oniris_stream_t stream);
+int oniris_vae_res_a_bwd(const float* da, const float* x, const float* emb, const float* dout, const float* wd, int B, int T,
+                         int H, int W, int C, int g, int nch, int gpt, float* dx, float* emb_part, oniris_stream_t stream);
+int oniris_vae_conv3_wgrad_bwd(const float* xin, const float* emb, const float* dA, int B, int T, int H, int W, int C, int g,
+                               int causal, float* slab, int nslab, oniris_stream_t stream);
+int oniris_vae_slab_sum_bwd(const float* slab, int nslab, int64_t n, float* out, oniris_stream_t stream);
+int oniris_vae_lin_dx_bwd(const float* dy, int Cy, int tcy, int scy, const float* wc, float* dx, int Cx, int tcx, int scx, int B,
+                          int T, int H, int W, oniris_stream_t stream);
+int oniris_vae_lin_dw_bwd(const float* x, int Cx, int tcx, int scx, const float* dy, int Cy, int tcy, int scy, int B, int T, int H,
+                          int W, float* slab, int nslab, oniris_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
