@@ -3,16 +3,13 @@
 // Per decoder block: oniris_vae_up (decompression 1x1 + 'up' rearrangement), per ResBlock oniris_vae_res_a (norm, FiLM,
 // SiLU, group-causal (2g,3,3) conv, norm, SiLU) and oniris_vae_res_b (3x3 conv + residual), then oniris_vae_out (final 1x1 +
 // channel-area residual; after the last block the mean / logvar split and, optionally, uint8 frames).  One
-// oniris_vae_temb per decode computes the FiLM scale / shift of every ResBlock.
+// oniris_vae_temb per decode computes the FiLM scale / shift of every ResBlock.  The two ResBlock launches are
+// vae_conv3_kernel<NCH, GPT, VAE_RES_A / VAE_RES_B> of csrc/vae_conv3.h, which the training forward shares.
 //
 // Every output is summed in a fixed order (time tap, row, column, input channel, then the bias) that depends on neither
 // T, nor the batch, nor how a sequence was cut into chunks: a streamed decode is bit-identical to the whole-sequence one.
-#include "common.h"
+#include "vae_conv3.h"
 #include "../../include/oniris.h"
-
-#define VAE_TILE 16
-#define VAE_HALO (VAE_TILE + 2)
-#define VAE_EPS 1e-4f
 
 // ---- t-embedding: emb[r][b][j] = bias_r[j] + sum_k W_r[j][k] * sqrt(2) cos(t_b freq_r[k] + phase_r[k]), j < 2 C_r
 // (MPFourier :139-150 of utils.py and ResBlock.t_cond, vae.py:76-80).  table[3 r .. 3 r + 2] = {parameter offset, 2 C_r,
@@ -64,147 +61,6 @@ __global__ __launch_bounds__(256) void vae_up_kernel(const float* __restrict__ x
     acc = fmaf(wr[ci], v, acc);
   }
   out[idx] = acc + bias[o];
-}
-
-// ---- the two 3x3 convolutions of a ResBlock (vae.py:56-93).  One workgroup = a 16x16 pixel tile (one thread per pixel) of
-// one output time step and one group of GPT output frames, every channel of them: the RMS norm of res A's epilogue is local
-// to the thread.  Per time tap the activated input frame (with its one-pixel halo, zero outside the image) is staged in
-// LDS, per stage of rows the packed weights; each input value read from LDS feeds NCH * GPT FMAs, each weight is a
-// broadcast read.
-//   MODE 0 (res A): out frame tau g + gq GPT + gl, channel c = SiLU(RMS(bias + sum_{kt < 2g, ky, kx, ci} w * a)), where a
-//     is frame tau g + kt of [g prefix frames ++ the T input frames], each activated as SiLU(RMS(x) (1 + scale) + shift);
-//     the prefix is the cache (already activated) or the first g input frames.  The workgroups of the last tau write the
-//     activated last g input frames to cache_out.
-//   MODE 1 (res B): out = res + bias + sum_{ky, kx, ci} w * u.
-// Weights packed [T/g groups = g / GPT][KT][9][C][NCH * GPT], output j = c GPT + gl (c >= C: zero); bias [g / GPT][NCH GPT].
-struct VaeConvParams {
-  const float* x;          // MODE 0: block input [B][T][H][W][C]; MODE 1: res A output u
-  const float* cache_in;   // MODE 0: [B][g][H][W][C] or NULL
-  float* cache_out;        // MODE 0: [B][g][H][W][C]
-  const float* emb;        // MODE 0: [B][2C] scale | shift
-  const float* w;
-  const float* bias;
-  const float* res;        // MODE 1: residual [B][T][H][W][C]
-  float* out;              // [B][T][H][W][C]
-  int T, H, W, C, g, rows_per_stage, tiles_x, ngq;
-};
-
-template <int NCH, int GPT, int MODE>
-__global__ __launch_bounds__(256) void vae_conv3_kernel(VaeConvParams a) {
-  constexpr int NACC = NCH * GPT;
-  extern __shared__ float smem[];
-  const int C = a.C, H = a.H, W = a.W, T = a.T, g = a.g;
-  const int CS = C | 1;                                      // odd pixel pitch: neighbouring pixels in different banks
-  float* tile = smem;                                        // [18 * 18][CS]
-  float* wsm = smem + VAE_HALO * VAE_HALO * CS;              // [rows_per_stage * 3][C][NACC]
-  const int tid = threadIdx.x, px = tid % VAE_TILE, py = tid / VAE_TILE;
-  const int tx0 = (blockIdx.x % a.tiles_x) * VAE_TILE, ty0 = (blockIdx.x / a.tiles_x) * VAE_TILE;
-  const int b = blockIdx.z;
-  const int tau = MODE == 0 ? (int)blockIdx.y / a.ngq : (int)blockIdx.y;
-  const int gq = MODE == 0 ? (int)blockIdx.y % a.ngq : 0;
-  const int KT = MODE == 0 ? 2 * g : 1;
-  const size_t frame = (size_t)H * W * C;
-
-  float acc[NACC];
-#pragma unroll
-  for (int j = 0; j < NACC; ++j) acc[j] = 0.f;
-
-  for (int kt = 0; kt < KT; ++kt) {
-    // stage frame f of the (prefix ++ input) sequence, activated (MODE 0), with halo
-    const int f = MODE == 0 ? tau * g + kt : tau;
-    for (int p = tid; p < VAE_HALO * VAE_HALO; p += 256) {
-      const int hy = p / VAE_HALO, hx = p % VAE_HALO;
-      const int y = ty0 + hy - 1, xx = tx0 + hx - 1;
-      float* dst = tile + p * CS;
-      if (y < 0 || y >= H || xx < 0 || xx >= W) {
-        for (int c = 0; c < C; ++c) dst[c] = 0.f;
-        continue;
-      }
-      const size_t pix = ((size_t)y * W + xx) * C;
-      if (MODE == 1) {
-        const float* src = a.x + ((size_t)b * T + f) * frame + pix;
-        for (int c = 0; c < C; ++c) dst[c] = src[c];
-        continue;
-      }
-      if (f < g && a.cache_in) {
-        const float* src = a.cache_in + ((size_t)b * g + f) * frame + pix;
-        for (int c = 0; c < C; ++c) dst[c] = src[c];
-        continue;
-      }
-      const float* src = a.x + ((size_t)b * T + (f < g ? f : f - g)) * frame + pix;
-      float ss = 0.f;
-      for (int c = 0; c < C; ++c) {
-        const float v = src[c];
-        dst[c] = v;
-        ss = fmaf(v, v, ss);
-      }
-      const float d = sqrtf(ss / (float)C + VAE_EPS);
-      const float* sc = a.emb + (size_t)b * 2 * C;
-      float* co = (f >= T && gq == 0 && hy >= 1 && hy <= VAE_TILE && hx >= 1 && hx <= VAE_TILE)
-                      ? a.cache_out + ((size_t)b * g + (f - T)) * frame + pix : nullptr;
-      for (int c = 0; c < C; ++c) {
-        float v = dst[c] / d;
-        v = v * (1.f + sc[c]) + sc[C + c];
-        v = v / (1.f + expf(-v));
-        dst[c] = v;
-        if (co) co[c] = v;
-      }
-    }
-    for (int ky0 = 0; ky0 < 3; ky0 += a.rows_per_stage) {
-      const int nw = a.rows_per_stage * 3 * C * NACC;        // a multiple of 4 (NACC >= 8)
-      const float4* src = (const float4*)(a.w + (((size_t)gq * KT + kt) * 9 + ky0 * 3) * C * NACC);
-      for (int i = tid; i < nw / 4; i += 256) ((float4*)wsm)[i] = src[i];
-      __syncthreads();
-      for (int kyl = 0; kyl < a.rows_per_stage; ++kyl)
-        for (int kx = 0; kx < 3; ++kx) {
-          const float* in = tile + ((py + ky0 + kyl) * VAE_HALO + px + kx) * CS;
-          const float* wr = wsm + (kyl * 3 + kx) * C * NACC;
-          for (int ci = 0; ci < C; ++ci) {
-            const float v = in[ci];
-            const float4* w4 = (const float4*)(wr + ci * NACC);
-#pragma unroll
-            for (int j4 = 0; j4 < NACC / 4; ++j4) {
-              const float4 wv = w4[j4];
-              acc[4 * j4 + 0] = fmaf(v, wv.x, acc[4 * j4 + 0]);
-              acc[4 * j4 + 1] = fmaf(v, wv.y, acc[4 * j4 + 1]);
-              acc[4 * j4 + 2] = fmaf(v, wv.z, acc[4 * j4 + 2]);
-              acc[4 * j4 + 3] = fmaf(v, wv.w, acc[4 * j4 + 3]);
-            }
-          }
-        }
-      __syncthreads();
-    }
-  }
-
-  const int y = ty0 + py, xx = tx0 + px;
-  if (y >= H || xx >= W) return;
-  const size_t pix = ((size_t)y * W + xx) * C;
-  const float* bias = a.bias + (size_t)gq * NACC;
-#pragma unroll
-  for (int j = 0; j < NACC; ++j) acc[j] += bias[j];
-  if (MODE == 1) {
-    const float* r = a.res + ((size_t)b * T + tau) * frame + pix;
-    float* o = a.out + ((size_t)b * T + tau) * frame + pix;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) o[c] = r[c] + acc[c];
-    return;
-  }
-#pragma unroll
-  for (int gl = 0; gl < GPT; ++gl) {
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) ss = fmaf(acc[c * GPT + gl], acc[c * GPT + gl], ss);
-    const float d = sqrtf(ss / (float)C + VAE_EPS);
-    float* o = a.out + ((size_t)b * T + (size_t)tau * g + gq * GPT + gl) * frame + pix;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) {
-        const float v = acc[c * GPT + gl] / d;
-        o[c] = v / (1.f + expf(-v));
-      }
-  }
 }
 
 // ---- out: final 1x1 conv Cin -> Cout (with bias) + interpolate_channels(x, Cout) (F.interpolate mode='area' over the
@@ -271,71 +127,23 @@ extern "C" int oniris_vae_up(const float* x, int64_t sb, int64_t st, int64_t sh,
   return ONIRIS_OK;
 }
 
-template <int NCH, int GPT, int MODE>
-static int vae_conv3_launch(const VaeConvParams& p, int B, int grid_y, hipStream_t stream) {
-  constexpr int NACC = NCH * GPT;
-  const size_t tile = (size_t)VAE_HALO * VAE_HALO * (p.C | 1) * sizeof(float);
-  VaeConvParams a = p;
-  a.rows_per_stage = tile + 9 * (size_t)p.C * NACC * sizeof(float) <= 64 * 1024 ? 3 : 1;
-  const size_t bytes = tile + (size_t)a.rows_per_stage * 3 * p.C * NACC * sizeof(float);
-  ONIRIS_CHECK_ARG(bytes <= 160 * 1024, "vae conv: %zu bytes of LDS", bytes);
-  if (bytes > 64 * 1024) {
-    static bool raised = false;
-    if (!raised) {
-      hipError_t e = hipFuncSetAttribute((const void*)vae_conv3_kernel<NCH, GPT, MODE>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        oniris_set_error("vae conv: raising the LDS limit failed: %s", hipGetErrorString(e));
-        return ONIRIS_ELAUNCH;
-      }
-      raised = true;
-    }
-  }
-  const dim3 grid(a.tiles_x * cdiv(p.H, VAE_TILE), grid_y, B);
-  ONIRIS_KLAUNCH((vae_conv3_kernel<NCH, GPT, MODE>), grid, dim3(256), bytes, stream, a);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
-}
-
-// the (NCH, GPT) pairs that are instantiated: NCH in {8, 16, 32, 64} channels (C <= NCH), GPT output frames per thread with
-// NCH * GPT <= 32 (64 for NCH = 64, GPT = 1)
-#define VAE_CONV3_CASES(MODE)                                                         \
-  if (nch == 8 && gpt == 1) return vae_conv3_launch<8, 1, MODE>(p, B, grid_y, s);     \
-  if (nch == 8 && gpt == 2) return vae_conv3_launch<8, 2, MODE>(p, B, grid_y, s);     \
-  if (nch == 8 && gpt == 4) return vae_conv3_launch<8, 4, MODE>(p, B, grid_y, s);     \
-  if (nch == 16 && gpt == 1) return vae_conv3_launch<16, 1, MODE>(p, B, grid_y, s);   \
-  if (nch == 16 && gpt == 2) return vae_conv3_launch<16, 2, MODE>(p, B, grid_y, s);   \
-  if (nch == 32 && gpt == 1) return vae_conv3_launch<32, 1, MODE>(p, B, grid_y, s);   \
-  if (nch == 64 && gpt == 1) return vae_conv3_launch<64, 1, MODE>(p, B, grid_y, s);
-
 extern "C" int oniris_vae_res_a(const float* x, const float* cache_in, float* cache_out, const float* emb, const float* w,
                                 const float* bias, int B, int T, int H, int W, int C, int g, int nch, int gpt, float* out,
                                 oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && cache_out && emb && w && bias && out, "vae_res_a: null pointer");
   ONIRIS_CHECK_ARG(cache_in != cache_out && (const float*)out != x, "vae_res_a: cache_out / out alias an input");
-  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C <= nch && g >= 1 && T >= g && T % g == 0 &&
-                       gpt >= 1 && g % gpt == 0 && (long long)(T / g) * (g / gpt) <= 65535,
-                   "vae_res_a: bad sizes (B %d T %d H %d W %d C %d g %d nch %d gpt %d)", B, T, H, W, C, g, nch, gpt);
-  VaeConvParams p{x, cache_in, cache_out, emb, w, bias, nullptr, out, T, H, W, C, g, 3, cdiv(W, VAE_TILE), g / gpt};
-  const int grid_y = (T / g) * (g / gpt);
-  hipStream_t s = (hipStream_t)stream;
-  VAE_CONV3_CASES(0)
-  oniris_set_error("vae_res_a: no kernel for %d channels (capacity %d) with %d frames per thread", C, nch, gpt);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_GROUPED("vae_res_a");
+  VaeConv3Params p{x, cache_in, cache_out, emb, w, bias, nullptr, nullptr, out, nullptr, T, H, W, C, g};
+  return vae_conv3_dispatch<VAE_RES_A>("vae_res_a", p, B, nch, gpt, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_res_b(const float* u, const float* res, const float* w, const float* bias, int B, int T, int H, int W,
                                 int C, int nch, float* out, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(u && res && w && bias && out, "vae_res_b: null pointer");
   ONIRIS_CHECK_ARG((const float*)out != u, "vae_res_b: out aliases u");
-  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T <= 65535 && H > 0 && W > 0 && C > 0 && C <= nch,
-                   "vae_res_b: bad sizes (B %d T %d H %d W %d C %d nch %d)", B, T, H, W, C, nch);
-  VaeConvParams p{u, nullptr, nullptr, nullptr, w, bias, res, out, T, H, W, C, 1, 3, cdiv(W, VAE_TILE), 1};
-  const int gpt = 1, grid_y = T;
-  hipStream_t s = (hipStream_t)stream;
-  VAE_CONV3_CASES(1)
-  oniris_set_error("vae_res_b: no kernel for %d channels (capacity %d)", C, nch);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_PLAIN("vae_res_b");
+  VaeConv3Params p{u, nullptr, nullptr, nullptr, w, bias, res, nullptr, out, nullptr, T, H, W, C, 1};
+  return vae_conv3_dispatch<VAE_RES_B>("vae_res_b", p, B, nch, 1, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout,

@@ -1,8 +1,8 @@
 // VAE encoder (reference: edm2/vae/vae.py EncoderDecoder(type='encoder') :96-204, VAE.encode :239-241), inference only,
 // fp32 throughout: the way into and out of the ResBlocks.  The ResBlocks themselves are the decoder's oniris_vae_res_a /
-// oniris_vae_res_b (csrc/vae.hip) with a zero scale | shift buffer: the encoder passes t = None (vae.py:78-82) and
-// v * (1 + 0) + 0 is exact.  Per encoder block one oniris_vae_down launch and two per ResBlock; one oniris_vae_latents
-// launch at latent resolution per encode.
+// oniris_vae_res_b (csrc/vae.hip, csrc/vae_conv3.h) with a zero scale | shift buffer: the encoder passes t = None
+// (vae.py:78-82) and v * (1 + 0) + 0 is exact.  Per encoder block one oniris_vae_down launch and two per ResBlock; one
+// oniris_vae_latents launch at latent resolution per encode.
 //
 // Every output is summed in a fixed order (rearranged channel k ascending, then the bias, then the area residual) that
 // depends on neither T, nor the batch, nor how a sequence was cut into chunks.

@@ -16,238 +16,11 @@
 // output group and from the next one only -- the causality of the forward mirrored, with a zero suffix in place of the prefix.
 //
 // Every sum has a fixed order and no floating-point atomic is used: two runs give bit-identical outputs and gradients.  The
-// forward accumulates exactly like vae_conv3_kernel (time tap, row, column, input channel, then the bias) and activates with the
-// same expressions, so the encoder's training forward is bit-identical to the inference one.
-#include "common.h"
+// ResBlock's forward and data-gradient launches are vae_conv3_kernel<NCH, GPT, VT_FWD_A / VT_FWD_B / VT_DG_B / VT_DG_A> of
+// csrc/vae_conv3.h, the kernel of the inference forward: staging, accumulation (time tap, row, column, input channel, then the
+// bias) and activation are the same source, so the encoder's training forward is bit-identical to the inference one.
+#include "vae_conv3.h"
 #include "../../include/oniris.h"
-
-#define VT_TILE 16
-#define VT_HALO (VT_TILE + 2)
-#define VT_EPS 1e-4f
-
-enum { VT_FWD_A = 0, VT_FWD_B = 1, VT_DG_B = 2, VT_DG_A = 3 };
-
-// SiLU(RMS(src) (1 + scale) + shift) of one pixel's C channels into dst (sc NULL: no scale / shift), in the arithmetic of
-// vae_conv3_kernel's staging and epilogue
-__device__ __forceinline__ void vt_activate(const float* __restrict__ src, float* __restrict__ dst, int C,
-                                            const float* __restrict__ sc) {
-  float ss = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float v = src[c];
-    dst[c] = v;
-    ss = fmaf(v, v, ss);
-  }
-  const float d = sqrtf(ss / (float)C + VT_EPS);
-  for (int c = 0; c < C; ++c) {
-    float v = dst[c] / d;
-    if (sc) v = v * (1.f + sc[c]) + sc[C + c];
-    dst[c] = v / (1.f + expf(-v));
-  }
-}
-
-__device__ __forceinline__ float vt_dsilu(float v) {           // SiLU'(v) = s (1 + v (1 - s)), s = sigmoid(v)
-  const float s = 1.f / (1.f + expf(-v));
-  return s * (1.f + v * (1.f - s));
-}
-
-// ---- the four 3x3 tile kernels: the loop of vae_conv3_kernel (one thread per pixel of a 16x16 tile, every output channel of
-// GPT frames in registers, one staged frame and its weights in LDS per time tap), with other operands and epilogues.
-//   VT_FWD_A  taps kt < 2g: frame tau g + kt of [first g frames ++ the T frames] of x, activated; out: a, frames tau g + gq GPT + gl
-//   VT_FWD_B  one tap: frame tau of a, activated without scale / shift; out = aux (the residual) + bias + conv
-//   VT_DG_B   one tap: frame tau of dout; weights [9 flipped][co][ci]; out: da (aux = a)
-//   VT_DG_A   taps j < 2g: frame q g + j of da (zero beyond T); weights [g / GPT][2g][9 flipped][c][ci GPT + rl] where tap j < g is
-//             output frame gl = j of group q through time tap g + r, and tap j >= g is gl = j - g of group q + 1 through time
-//             tap r (r = gq GPT + rl, the position of the input frame inside its group); out: dx of frames q g + r (aux = x,
-//             aux2 = dout); part (or NULL): [gridDim.y gridDim.x][B][2C] sums over the workgroup of d scale | d shift
-struct VtConvParams {
-  const float* x;
-  const float* emb;        // [B][2C] scale | shift, or NULL
-  const float* w;
-  const float* bias;
-  const float* aux;
-  const float* aux2;
-  float* out;
-  float* part;
-  int T, H, W, C, g, rows_per_stage, tiles_x, ngq;
-};
-
-template <int NCH, int GPT, int MODE>
-__global__ __launch_bounds__(256) void vt_conv3_kernel(VtConvParams a) {
-  constexpr int NACC = NCH * GPT;
-  constexpr bool GROUPED = MODE == VT_FWD_A || MODE == VT_DG_A;
-  extern __shared__ float smem[];
-  const int C = a.C, H = a.H, W = a.W, T = a.T, g = a.g;
-  const int CS = C | 1;
-  float* tile = smem;                                        // [18 * 18][CS]
-  float* wsm = smem + VT_HALO * VT_HALO * CS;                // [rows_per_stage * 3][C][NACC]
-  const int tid = threadIdx.x, px = tid % VT_TILE, py = tid / VT_TILE;
-  const int tx0 = (blockIdx.x % a.tiles_x) * VT_TILE, ty0 = (blockIdx.x / a.tiles_x) * VT_TILE;
-  const int b = blockIdx.z;
-  const int tau = GROUPED ? (int)blockIdx.y / a.ngq : (int)blockIdx.y;
-  const int gq = GROUPED ? (int)blockIdx.y % a.ngq : 0;
-  const int KT = GROUPED ? 2 * g : 1;
-  const size_t frame = (size_t)H * W * C;
-  const float* sc = a.emb ? a.emb + (size_t)b * 2 * C : nullptr;
-
-  float acc[NACC];
-#pragma unroll
-  for (int j = 0; j < NACC; ++j) acc[j] = 0.f;
-
-  for (int kt = 0; kt < KT; ++kt) {
-    int f;                                                   // the frame of a.x this tap reads, -1: zeros
-    if (MODE == VT_FWD_A) {
-      f = tau * g + kt;
-      f = f < g ? f : f - g;
-    } else if (MODE == VT_DG_A) {
-      f = tau * g + kt;
-      if (f >= T) f = -1;
-    } else {
-      f = tau;
-    }
-    for (int p = tid; p < VT_HALO * VT_HALO; p += 256) {
-      const int hy = p / VT_HALO, hx = p % VT_HALO;
-      const int y = ty0 + hy - 1, xx = tx0 + hx - 1;
-      float* dst = tile + p * CS;
-      if (f < 0 || y < 0 || y >= H || xx < 0 || xx >= W) {
-        for (int c = 0; c < C; ++c) dst[c] = 0.f;
-        continue;
-      }
-      const float* src = a.x + ((size_t)b * T + f) * frame + ((size_t)y * W + xx) * C;
-      if (MODE == VT_FWD_A) {
-        vt_activate(src, dst, C, sc);
-      } else if (MODE == VT_FWD_B) {
-        vt_activate(src, dst, C, nullptr);
-      } else {
-        for (int c = 0; c < C; ++c) dst[c] = src[c];
-      }
-    }
-    for (int ky0 = 0; ky0 < 3; ky0 += a.rows_per_stage) {
-      const int nw = a.rows_per_stage * 3 * C * NACC;        // a multiple of 4 (NACC >= 8)
-      const float4* src = (const float4*)(a.w + (((size_t)gq * KT + kt) * 9 + ky0 * 3) * C * NACC);
-      for (int i = tid; i < nw / 4; i += 256) ((float4*)wsm)[i] = src[i];
-      __syncthreads();
-      for (int kyl = 0; kyl < a.rows_per_stage; ++kyl)
-        for (int kx = 0; kx < 3; ++kx) {
-          const float* in = tile + ((py + ky0 + kyl) * VT_HALO + px + kx) * CS;
-          const float* wr = wsm + (kyl * 3 + kx) * C * NACC;
-          for (int ci = 0; ci < C; ++ci) {
-            const float v = in[ci];
-            const float4* w4 = (const float4*)(wr + ci * NACC);
-#pragma unroll
-            for (int j4 = 0; j4 < NACC / 4; ++j4) {
-              const float4 wv = w4[j4];
-              acc[4 * j4 + 0] = fmaf(v, wv.x, acc[4 * j4 + 0]);
-              acc[4 * j4 + 1] = fmaf(v, wv.y, acc[4 * j4 + 1]);
-              acc[4 * j4 + 2] = fmaf(v, wv.z, acc[4 * j4 + 2]);
-              acc[4 * j4 + 3] = fmaf(v, wv.w, acc[4 * j4 + 3]);
-            }
-          }
-        }
-      __syncthreads();
-    }
-  }
-
-  const int y = ty0 + py, xx = tx0 + px;
-  const bool inside = y < H && xx < W;
-  const size_t pix = inside ? ((size_t)y * W + xx) * C : 0;
-
-  if (MODE == VT_FWD_A || MODE == VT_FWD_B) {
-    if (!inside) return;
-    const float* bias = a.bias + (size_t)gq * NACC;
-#pragma unroll
-    for (int j = 0; j < NACC; ++j) acc[j] += bias[j];
-    if (MODE == VT_FWD_B) {
-      const float* r = a.aux + ((size_t)b * T + tau) * frame + pix;
-      float* o = a.out + ((size_t)b * T + tau) * frame + pix;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (c < C) o[c] = r[c] + acc[c];
-      return;
-    }
-#pragma unroll
-    for (int gl = 0; gl < GPT; ++gl) {
-      float* o = a.out + ((size_t)b * T + (size_t)tau * g + gq * GPT + gl) * frame + pix;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (c < C) o[c] = acc[c * GPT + gl];
-    }
-    return;
-  }
-
-  if (MODE == VT_DG_B) {                                     // acc = du; da = (dr - r mean(dr r)) / d, dr = du SiLU'(r), r = a / d
-    if (!inside) return;
-    const float* ap = a.aux + ((size_t)b * T + tau) * frame + pix;
-    float* o = a.out + ((size_t)b * T + tau) * frame + pix;
-    float ss = 0.f;
-    for (int c = 0; c < C; ++c) ss = fmaf(ap[c], ap[c], ss);
-    const float d = sqrtf(ss / (float)C + VT_EPS);
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) {
-        const float r = ap[c] / d;
-        acc[c] *= vt_dsilu(r);
-        m = fmaf(acc[c], r, m);
-      }
-    m /= (float)C;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) o[c] = (acc[c] - (ap[c] / d) * m) / d;
-    return;
-  }
-
-  // VT_DG_A: acc[ci GPT + rl] = dy of frame q g + gq GPT + rl.  With n = x / d, v = n (1 + scale) + shift:  dv = dy SiLU'(v),
-  // d scale += dv n, d shift += dv, dn = dv (1 + scale), dx = (dn - n mean(dn n)) / d + dout.  No thread leaves before the
-  // wave sums; a pixel outside the image contributes zero.
-  float* red = smem;                                         // [4 waves][2C], free after the last barrier of the loop
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int rl = 0; rl < GPT; ++rl) {
-    const size_t off = ((size_t)b * T + (size_t)tau * g + gq * GPT + rl) * frame + pix;
-    const float* xp = a.aux + off;
-    float ss = 0.f;
-    if (inside)
-      for (int c = 0; c < C; ++c) ss = fmaf(xp[c], xp[c], ss);
-    const float d = sqrtf(ss / (float)C + VT_EPS);
-    float m = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-      if (c < C) {
-        float dv = 0.f, n = 0.f, s1 = 0.f;
-        if (inside) {
-          n = xp[c] / d;
-          s1 = sc ? 1.f + sc[c] : 1.f;
-          const float v = sc ? n * s1 + sc[C + c] : n;
-          dv = acc[c * GPT + rl] * vt_dsilu(v);
-        }
-        const float dn = dv * s1;
-        acc[c * GPT + rl] = dn;
-        m = fmaf(dn, n, m);
-        if (a.part) {
-          const float ps = wave_sum(dv * n), ph = wave_sum(dv);
-          if (lane == 0) {
-            red[wave * 2 * C + c] = (rl == 0 ? 0.f : red[wave * 2 * C + c]) + ps;
-            red[wave * 2 * C + C + c] = (rl == 0 ? 0.f : red[wave * 2 * C + C + c]) + ph;
-          }
-        }
-      }
-    m /= (float)C;
-    if (inside) {
-      const float* go = a.aux2 + off;
-      float* o = a.out + off;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (c < C) o[c] = (acc[c * GPT + rl] - (xp[c] / d) * m) / d + go[c];
-    }
-  }
-  if (a.part) {
-    __syncthreads();
-    if (tid < 2 * C) {
-      const float s = ((red[tid] + red[2 * C + tid]) + red[4 * C + tid]) + red[6 * C + tid];
-      a.part[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * gridDim.z + b) * 2 * C + tid] = s;
-    }
-  }
-}
 
 // ---- weight and bias gradient of a 3x3 conv of a ResBlock.  dW[kt][gl][ky][kx][ci][c] = sum over b, tau, pixel of
 // dA[frame tau g + gl][pixel][c] * in[frame(tau, kt)][pixel + (ky - 1, kx - 1)][ci] and db[gl][c] = sum dA, where `in` is the
@@ -271,7 +44,7 @@ __global__ __launch_bounds__(256) void vt_wgrad3_kernel(VtWgradParams a) {
   const int C = a.C, H = a.H, W = a.W, T = a.T, g = a.g;
   const int CS = C | 1;
   float* tile = smem;                                        // [18 * 18][CS]  the activated operand with its halo
-  float* dt = smem + VT_HALO * VT_HALO * CS;                 // [256][C]       one frame of dA
+  float* dt = smem + VAE_HALO * VAE_HALO * CS;               // [256][C]       one frame of dA
   const int tid = threadIdx.x;
   const size_t frame = (size_t)H * W * C;
   const int NE = 9 * C * C;
@@ -282,28 +55,18 @@ __global__ __launch_bounds__(256) void vt_wgrad3_kernel(VtWgradParams a) {
     const int t_i = item % tiles;
     const int tau = (item / tiles) % a.ntau;
     const int b = item / (tiles * a.ntau);
-    const int tx0 = (t_i % a.tiles_x) * VT_TILE, ty0 = (t_i / a.tiles_x) * VT_TILE;
+    const int tx0 = (t_i % a.tiles_x) * VAE_TILE, ty0 = (t_i / a.tiles_x) * VAE_TILE;
     const float* sc = a.emb ? a.emb + (size_t)b * 2 * C : nullptr;
     for (int kt = 0; kt < a.KT; ++kt) {
-      int f = tau;
-      if (a.causal) {
-        f = tau * g + kt;
-        f = f < g ? f : f - g;
-      }
-      for (int p = tid; p < VT_HALO * VT_HALO; p += 256) {
-        const int hy = p / VT_HALO, hx = p % VT_HALO;
-        const int y = ty0 + hy - 1, xx = tx0 + hx - 1;
-        float* dst = tile + p * CS;
-        if (y < 0 || y >= H || xx < 0 || xx >= W) {
-          for (int c = 0; c < C; ++c) dst[c] = 0.f;
-          continue;
-        }
-        vt_activate(a.xin + ((size_t)b * T + f) * frame + ((size_t)y * W + xx) * C, dst, C, sc);
-      }
+      const int fp = a.causal ? tau * g + kt : tau;          // causal: a frame of the (prefix ++ input) sequence
+      const int f = a.causal && fp >= g ? fp - g : fp;
+      vae_stage_halo(tile, ty0, tx0, H, W, C, true, [&](float* dst, size_t pix, bool) {
+        vae_activate(a.xin + ((size_t)b * T + f) * frame + pix, dst, C, sc, nullptr);
+      });
       for (int gl = 0; gl < g; ++gl) {
         const int fo = a.causal ? tau * g + gl : tau;
         {
-          const int y = ty0 + tid / VT_TILE, xx = tx0 + tid % VT_TILE;
+          const int y = ty0 + tid / VAE_TILE, xx = tx0 + tid % VAE_TILE;
           float* dst = dt + tid * C;
           if (y < H && xx < W) {
             const float* src = a.dA + ((size_t)b * T + fo) * frame + ((size_t)y * W + xx) * C;
@@ -327,12 +90,12 @@ __global__ __launch_bounds__(256) void vt_wgrad3_kernel(VtWgradParams a) {
             const int e = e0 + 256 * k < NE ? e0 + 256 * k : 0;
             const int kyx = e / (C * C), ci = (e / C) % C;
             co[k] = e % C;
-            io[k] = ((kyx / 3) * VT_HALO + kyx % 3) * CS + ci;
+            io[k] = ((kyx / 3) * VAE_HALO + kyx % 3) * CS + ci;
             acc[k] = 0.f;
           }
           const int nk = (NE - e0 + 255) / 256;              // how many of the eight exist for this thread
           for (int p = 0; p < 256; ++p) {
-            const float* in = tile + ((p >> 4) * VT_HALO + (p & 15)) * CS;
+            const float* in = tile + ((p >> 4) * VAE_HALO + (p & 15)) * CS;
             const float* dd = dt + p * C;
 #pragma unroll
             for (int k = 0; k < 8; ++k)
@@ -447,90 +210,29 @@ __global__ __launch_bounds__(256) void vt_lin_dw_kernel(const float* __restrict_
 }
 
 // ---- host side
-template <int NCH, int GPT, int MODE>
-static int vt_conv3_launch(const VtConvParams& p, int B, int grid_y, hipStream_t stream) {
-  constexpr int NACC = NCH * GPT;
-  const size_t tile = (size_t)VT_HALO * VT_HALO * (p.C | 1) * sizeof(float);
-  VtConvParams a = p;
-  a.rows_per_stage = tile + 9 * (size_t)p.C * NACC * sizeof(float) <= 64 * 1024 ? 3 : 1;
-  const size_t bytes = tile + (size_t)a.rows_per_stage * 3 * p.C * NACC * sizeof(float);
-  ONIRIS_CHECK_ARG(bytes <= 160 * 1024, "vae training conv: %zu bytes of LDS", bytes);
-  if (bytes > 64 * 1024) {
-    static bool raised = false;
-    if (!raised) {
-      hipError_t e = hipFuncSetAttribute((const void*)vt_conv3_kernel<NCH, GPT, MODE>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        oniris_set_error("vae training conv: raising the LDS limit failed: %s", hipGetErrorString(e));
-        return ONIRIS_ELAUNCH;
-      }
-      raised = true;
-    }
-  }
-  const dim3 grid(a.tiles_x * cdiv(p.H, VT_TILE), grid_y, B);
-  ONIRIS_KLAUNCH((vt_conv3_kernel<NCH, GPT, MODE>), grid, dim3(256), bytes, stream, a);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
-}
-
-// the (NCH, GPT) pairs of the inference kernels (csrc/vae.hip)
-#define VT_CONV3_CASES(MODE)                                                         \
-  if (nch == 8 && gpt == 1) return vt_conv3_launch<8, 1, MODE>(p, B, grid_y, s);     \
-  if (nch == 8 && gpt == 2) return vt_conv3_launch<8, 2, MODE>(p, B, grid_y, s);     \
-  if (nch == 8 && gpt == 4) return vt_conv3_launch<8, 4, MODE>(p, B, grid_y, s);     \
-  if (nch == 16 && gpt == 1) return vt_conv3_launch<16, 1, MODE>(p, B, grid_y, s);   \
-  if (nch == 16 && gpt == 2) return vt_conv3_launch<16, 2, MODE>(p, B, grid_y, s);   \
-  if (nch == 32 && gpt == 1) return vt_conv3_launch<32, 1, MODE>(p, B, grid_y, s);   \
-  if (nch == 64 && gpt == 1) return vt_conv3_launch<64, 1, MODE>(p, B, grid_y, s);
-#define VT_CONV3_CASES_1(MODE)                                                       \
-  if (nch == 8) return vt_conv3_launch<8, 1, MODE>(p, B, grid_y, s);                 \
-  if (nch == 16) return vt_conv3_launch<16, 1, MODE>(p, B, grid_y, s);               \
-  if (nch == 32) return vt_conv3_launch<32, 1, MODE>(p, B, grid_y, s);               \
-  if (nch == 64) return vt_conv3_launch<64, 1, MODE>(p, B, grid_y, s);
-
-#define VT_CHECK_GROUPED(what)                                                                                            \
-  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0 && C <= nch && g >= 1 && T >= g && T % g == 0 &&        \
-                       gpt >= 1 && g % gpt == 0 && (long long)(T / g) * (g / gpt) <= 65535,                               \
-                   what ": bad sizes (B %d T %d H %d W %d C %d g %d nch %d gpt %d)", B, T, H, W, C, g, nch, gpt)
-#define VT_CHECK_PLAIN(what)                                                                               \
-  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T <= 65535 && H > 0 && W > 0 && C > 0 && C <= nch,      \
-                   what ": bad sizes (B %d T %d H %d W %d C %d nch %d)", B, T, H, W, C, nch)
-
 extern "C" int oniris_vae_train_res_a(const float* x, const float* emb, const float* w, const float* bias, int B, int T, int H,
                                       int W, int C, int g, int nch, int gpt, float* a_out, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && w && bias && a_out && (const float*)a_out != x, "vae_train_res_a: null or aliased pointer");
-  VT_CHECK_GROUPED("vae_train_res_a");
-  VtConvParams p{x, emb, w, bias, nullptr, nullptr, a_out, nullptr, T, H, W, C, g, 3, cdiv(W, VT_TILE), g / gpt};
-  const int grid_y = (T / g) * (g / gpt);
-  hipStream_t s = (hipStream_t)stream;
-  VT_CONV3_CASES(VT_FWD_A)
-  oniris_set_error("vae_train_res_a: no kernel for %d channels (capacity %d) with %d frames per thread", C, nch, gpt);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_GROUPED("vae_train_res_a");
+  VaeConv3Params p{x, nullptr, nullptr, emb, w, bias, nullptr, nullptr, a_out, nullptr, T, H, W, C, g};
+  return vae_conv3_dispatch<VT_FWD_A>("vae_train_res_a", p, B, nch, gpt, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_train_res_b(const float* a_in, const float* res, const float* w, const float* bias, int B, int T,
                                       int H, int W, int C, int nch, float* out, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(a_in && res && w && bias && out && (const float*)out != a_in, "vae_train_res_b: null or aliased pointer");
-  VT_CHECK_PLAIN("vae_train_res_b");
-  VtConvParams p{a_in, nullptr, w, bias, res, nullptr, out, nullptr, T, H, W, C, 1, 3, cdiv(W, VT_TILE), 1};
-  const int grid_y = T;
-  hipStream_t s = (hipStream_t)stream;
-  VT_CONV3_CASES_1(VT_FWD_B)
-  oniris_set_error("vae_train_res_b: no kernel for %d channels (capacity %d)", C, nch);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_PLAIN("vae_train_res_b");
+  VaeConv3Params p{a_in, nullptr, nullptr, nullptr, w, bias, res, nullptr, out, nullptr, T, H, W, C, 1};
+  return vae_conv3_dispatch<VT_FWD_B>("vae_train_res_b", p, B, nch, 1, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_res_b_bwd(const float* dout, const float* a_in, const float* wd, int B, int T, int H, int W, int C,
                                     int nch, float* da, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(dout && a_in && wd && da && (const float*)da != dout && (const float*)da != a_in,
                    "vae_res_b_bwd: null or aliased pointer");
-  VT_CHECK_PLAIN("vae_res_b_bwd");
-  VtConvParams p{dout, nullptr, wd, nullptr, a_in, nullptr, da, nullptr, T, H, W, C, 1, 3, cdiv(W, VT_TILE), 1};
-  const int grid_y = T;
-  hipStream_t s = (hipStream_t)stream;
-  VT_CONV3_CASES_1(VT_DG_B)
-  oniris_set_error("vae_res_b_bwd: no kernel for %d channels (capacity %d)", C, nch);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_PLAIN("vae_res_b_bwd");
+  VaeConv3Params p{dout, nullptr, nullptr, nullptr, wd, nullptr, a_in, nullptr, da, nullptr, T, H, W, C, 1};
+  return vae_conv3_dispatch<VT_DG_B>("vae_res_b_bwd", p, B, nch, 1, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_res_a_bwd(const float* da, const float* x, const float* emb, const float* dout, const float* wd, int B,
@@ -538,13 +240,9 @@ extern "C" int oniris_vae_res_a_bwd(const float* da, const float* x, const float
                                     oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(da && x && dout && wd && dx && (const float*)dx != da, "vae_res_a_bwd: null or aliased pointer");
   ONIRIS_CHECK_ARG(!emb_part || emb, "vae_res_a_bwd: emb_part without emb");
-  VT_CHECK_GROUPED("vae_res_a_bwd");
-  VtConvParams p{da, emb, wd, nullptr, x, dout, dx, emb_part, T, H, W, C, g, 3, cdiv(W, VT_TILE), g / gpt};
-  const int grid_y = (T / g) * (g / gpt);
-  hipStream_t s = (hipStream_t)stream;
-  VT_CONV3_CASES(VT_DG_A)
-  oniris_set_error("vae_res_a_bwd: no kernel for %d channels (capacity %d) with %d frames per thread", C, nch, gpt);
-  return ONIRIS_EUNSUPPORTED;
+  VAE_CONV3_CHECK_GROUPED("vae_res_a_bwd");
+  VaeConv3Params p{da, nullptr, nullptr, emb, wd, nullptr, x, dout, dx, emb_part, T, H, W, C, g};
+  return vae_conv3_dispatch<VT_DG_A>("vae_res_a_bwd", p, B, nch, gpt, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_conv3_wgrad_bwd(const float* xin, const float* emb, const float* dA, int B, int T, int H, int W, int C,
@@ -556,24 +254,14 @@ extern "C" int oniris_vae_conv3_wgrad_bwd(const float* xin, const float* emb, co
   VtWgradParams p;
   p.xin = xin; p.emb = emb; p.dA = dA; p.slab = slab;
   p.B = B; p.T = T; p.H = H; p.W = W; p.C = C; p.g = g; p.KT = causal ? 2 * g : 1; p.causal = causal;
-  p.tiles_x = cdiv(W, VT_TILE); p.tiles_y = cdiv(H, VT_TILE); p.ntau = causal ? T / g : T;
+  p.tiles_x = cdiv(W, VAE_TILE); p.tiles_y = cdiv(H, VAE_TILE); p.ntau = causal ? T / g : T;
   const long long nitems = (long long)B * p.ntau * p.tiles_x * p.tiles_y;
   ONIRIS_CHECK_ARG(nitems <= 0x7fffffffLL, "vae_conv3_wgrad_bwd: %lld work items", nitems);
   p.nitems = (int)nitems;
   p.nslab = nslab;
   p.slab_size = (long long)p.KT * g * 9 * C * C + (long long)g * C;
-  const size_t bytes = ((size_t)VT_HALO * VT_HALO * (C | 1) + (size_t)256 * C) * sizeof(float);
-  if (bytes > 64 * 1024) {
-    static bool raised = false;
-    if (!raised) {
-      hipError_t e = hipFuncSetAttribute((const void*)vt_wgrad3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) {
-        oniris_set_error("vae_conv3_wgrad_bwd: raising the LDS limit failed: %s", hipGetErrorString(e));
-        return ONIRIS_ELAUNCH;
-      }
-      raised = true;
-    }
-  }
+  const size_t bytes = ((size_t)VAE_HALO * VAE_HALO * (C | 1) + (size_t)256 * C) * sizeof(float);
+  if (int rc = vae_raise_lds<vt_wgrad3_kernel>(bytes, "vae_conv3_wgrad_bwd")) return rc;
   ONIRIS_KLAUNCH(vt_wgrad3_kernel, dim3(nslab), dim3(256), bytes, (hipStream_t)stream, p);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;

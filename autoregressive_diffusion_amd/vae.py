@@ -6,7 +6,7 @@ VAE loads here unchanged and round-trips.  Encoder and decoder run for inference
 `encode_long_sequence`, `frames_to_latents` and the streaming form `encode_frames`; `decode`, `latents_to_frames` and the
 streaming form `decode_frames`.  Both are causal in time -- every group-causal conv keeps the last g activated frames of its
 input as a cache (vae.py:18-53) -- so encoding or decoding a sequence chunk by chunk through the cache gives exactly what the
-whole sequence gives (bit-identical here: csrc/vae.hip and csrc/vae_encoder.hip sum every output in a fixed order).
+whole sequence gives (bit-identical here: csrc/vae*.hip and csrc/vae_conv3.h sum every output in a fixed order).
 Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up` launch, two per ResBlock, one `out` launch,
 plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
 ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
@@ -50,15 +50,21 @@ def _nch(c):
 
 
 def _gpt(c, g):
-    """Output frames per thread of res A: the largest power of two that divides g with nch * gpt <= 32 (csrc/vae.hip)."""
+    """Output frames per thread of res A: the largest power of two that divides g with nch * gpt <= 32 (csrc/vae_conv3.h)."""
     gpt = 1
     while gpt * 2 <= 4 and g % (gpt * 2) == 0 and _nch(c) * gpt * 2 <= 32:
         gpt *= 2
     return gpt
 
 
+def _area_windows(K, N):
+    """The windows (s0, s1) = [floor(o K / N), ceil((o + 1) K / N)) of F.interpolate mode='area' from K to N channels
+    (interpolate_channels, vae.py:136-141), one per output channel o."""
+    return [((o * K) // N, -((-(o + 1) * K) // N)) for o in range(N)]
+
+
 def _pack_res(rb, C, g, f32):
-    """The two convolutions of a ResBlock in the layouts of vae_conv3_kernel (csrc/vae.hip)."""
+    """The two convolutions of a ResBlock in the layouts of vae_conv3_kernel (csrc/vae_conv3.h)."""
     nch, gpt = _nch(C), _gpt(C, g)
     w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gq gpt + gl
     w = w.reshape(C, g // gpt, gpt, C, 2 * g, 3, 3).permute(1, 4, 5, 6, 3, 0, 2)   # gq, kt, ky, kx, ci, c, gl
@@ -221,7 +227,7 @@ class VAE(BetterModule):
 
     # ---- packed device weights
     def _pack(self, device):
-        """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip, rebuilt when a parameter changed."""
+        """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip and vae_conv3.h, rebuilt when one changed."""
         params = list(self.decoder.parameters()) + list(self.decoder.buffers())
         sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
         pk = self.__dict__.get("_oniris_vae_pack")
@@ -252,6 +258,29 @@ class VAE(BetterModule):
         self.__dict__["_oniris_vae_pack"] = pk
         return pk
 
+    # ---- the ResBlocks of one block, for both sides
+    @staticmethod
+    def _res_blocks(side, i, bk, x, cache, emb_of, s):
+        """x (B, T, H, W, C) through the ResBlocks of packed block bk (block i of `side`) with the block's entry of the incoming
+        cache; emb_of(rb): the address of a ResBlock's FiLM scale | shift.  Returns (x, the block's entry of the new cache)."""
+        B, T, H, W, C = x.shape
+        g, new_cache = bk["g"], {}
+        for j, rb in enumerate(bk["res"]):
+            cin = cache.get(f"res_block_{j}", {}).get("conv3d_res0")
+            if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != x.device or cin.dtype != torch.float32):
+                raise ValueError(f"VAE {side} cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
+                                 f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
+            cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=x.device)
+            u = torch.empty_like(x)
+            _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb_of(rb), _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g,
+                                                 bk["nch"], bk["gpt"], _p(u), s), "vae_res_a")
+            xn = torch.empty_like(x)
+            _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
+                       "vae_res_b")
+            x = xn
+            new_cache[f"res_block_{j}"] = {"conv3d_res0": cout}
+        return x, new_cache
+
     # ---- the decoder
     def _run(self, x, strides, t, cache, in_affine=False, want="moments"):
         """x: latents addressed by element strides (b, t, h, w, c); returns ((mean, logvar) | frames, cache)."""
@@ -276,29 +305,14 @@ class VAE(BetterModule):
         H, W = h, w_
         nblk = len(pk["blocks"])
         for i, bk in enumerate(pk["blocks"]):
-            C, g, tc, sc = bk["C"], bk["g"], bk["tc"], bk["sc"]
+            C, tc, sc = bk["C"], bk["tc"], bk["sc"]
             up = torch.empty(B, T * tc, H * sc, W * sc, C, dtype=torch.float32, device=dev)
             _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]),
                                               tc, sc, _p(up), s), "vae_up")
             x, T, H, W = up, T * tc, H * sc, W * sc
             scale = shift = None
-            bc = cache.get(f"encoder_block_{i}", {})
-            nbc = new_cache[f"encoder_block_{i}"] = {}
-            for j, rb in enumerate(bk["res"]):
-                cin = bc.get(f"res_block_{j}", {}).get("conv3d_res0")
-                if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != dev or cin.dtype != torch.float32):
-                    raise ValueError(f"VAE decoder cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
-                                     f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
-                cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=dev)
-                u = torch.empty_like(x)
-                _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb.data_ptr() + 4 * B * rb["emb_off"],
-                                                     _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g, bk["nch"], bk["gpt"], _p(u), s),
-                           "vae_res_a")
-                xn = torch.empty_like(x)
-                _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
-                           "vae_res_b")
-                x = xn
-                nbc[f"res_block_{j}"] = {"conv3d_res0": cout}
+            x, new_cache[f"encoder_block_{i}"] = self._res_blocks("decoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
+                                                                  lambda rb: emb.data_ptr() + 4 * B * rb["emb_off"], s)
             Cout = bk["Cout"]
             if i < nblk - 1:
                 y = torch.empty(B, T, H, W, Cout, dtype=torch.float32, device=dev)
@@ -351,7 +365,7 @@ class VAE(BetterModule):
 
     # ---- the encoder
     def _pack_encoder(self, device):
-        """fp32 copies of the encoder's parameters on `device` in the layouts of csrc/vae_encoder.hip and csrc/vae.hip, rebuilt
+        """fp32 copies of the encoder's parameters on `device` in the layouts of csrc/vae_encoder.hip and csrc/vae_conv3.h, rebuilt
         when a parameter changed.  pk["params"] names every state_dict entry that went into it."""
         params = list(self.encoder.parameters())
         sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
@@ -372,8 +386,7 @@ class VAE(BetterModule):
                 bd = torch.ones(2, g4, **f32)                  # the bias | the window lengths
                 bd[0] = 0
                 bd[0, :C] = blk.compression_block.bias.detach().to(**f32)
-                for o in range(C):
-                    s0, s1 = (o * K) // C, -((-(o + 1) * K) // C)
+                for o, (s0, s1) in enumerate(_area_windows(K, C)):
                     wd[s0:s1, 1, o] = 1
                     bd[1, o] = s1 - s0
                 pre = f"encoder.encoder_blocks.{i}."
@@ -420,28 +433,14 @@ class VAE(BetterModule):
         new_cache = {}
         u8 = x.dtype == torch.uint8
         for i, bk in enumerate(pk["blocks"]):
-            C, g, tc, sc = bk["C"], bk["g"], bk["tc"], bk["sc"]
+            C, tc, sc = bk["C"], bk["tc"], bk["sc"]
             T, H, W = T // tc, H // sc, W // sc
             y = torch.empty(B, T, H, W, C, dtype=torch.float32, device=dev)
             _lib.check(_lib.lib.oniris_vae_down(_p(x), int(u8), *strides, B, T, H, W, bk["Cin"], tc, sc, int(normalize), _p(bk["wd"]),
                                                 _p(bk["bd"]), C, _p(y), s), "vae_down")
             x, strides, u8, normalize = y, y.stride()[:4] + (1,), False, False
-            bc = cache.get(f"encoder_block_{i}", {})
-            nbc = new_cache[f"encoder_block_{i}"] = {}
-            for j, rb in enumerate(bk["res"]):
-                cin = bc.get(f"res_block_{j}", {}).get("conv3d_res0")
-                if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != dev or cin.dtype != torch.float32):
-                    raise ValueError(f"VAE encoder cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
-                                     f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
-                cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=dev)
-                u = torch.empty_like(x)
-                _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), _p(zeros), _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g,
-                                                     bk["nch"], bk["gpt"], _p(u), s), "vae_res_a")
-                xn = torch.empty_like(x)
-                _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
-                           "vae_res_b")
-                x = xn
-                nbc[f"res_block_{j}"] = {"conv3d_res0": cout}
+            x, new_cache[f"encoder_block_{i}"] = self._res_blocks("encoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
+                                                                  lambda rb: _p(zeros), s)
         if want == "latents":
             out = torch.empty(B, T, C, H, W, dtype=torch.float32, device=dev)
             sb, st, scc, sh, sw = out.stride()

@@ -1,15 +1,16 @@
 """The differentiable path of `vae.VAE.forward`: one autograd Function per stage of the VAE, each a few launches of csrc/vae_train.hip
-(backward, and the ResBlock's training forward) and of the inference kernels (the forward of the 1x1 stages), so that the
-encoder's training forward is bit-identical to `VAE.encode`.  Activations travel between the stages channels-last
-[B][T][H][W][C] fp32.  What stays in torch is plumbing at parameter or latent size: the t-embedding (MPFourier -> t_cond, under
-autograd), the mix of mean and noise, the permutations between the kernels' weight layouts and the parameters' and the
-channels-first <-> channels-last copies at the two ends (include/oniris.h: oniris_vae_train_*, oniris_vae_*_bwd).
+(backward, and the ResBlock's training forward: the tile kernel of csrc/vae_conv3.h, which inference runs too) and of the
+inference kernels (the forward of the 1x1 stages), so that the encoder's training forward is bit-identical to `VAE.encode`.
+Activations travel between the stages channels-last [B][T][H][W][C] fp32.  What stays in torch is plumbing at parameter or latent
+size: the t-embedding (MPFourier -> t_cond, under autograd), the mix of mean and noise, the permutations between the kernels'
+weight layouts and the parameters' and the channels-first <-> channels-last copies at the two ends (include/oniris.h:
+oniris_vae_train_*, oniris_vae_*_bwd).
 
 Gradients are summed in a fixed order into a bounded number of partial slabs and then over the slabs; nothing uses atomics."""
 import torch
 
 from . import _lib
-from .vae import _gpt, _nch, _p, _stream
+from .vae import _area_windows, _gpt, _nch, _p, _stream
 
 _SLAB_BYTES = 64 << 20          # the most memory one launch's partial slabs may take
 _area_cache = {}
@@ -26,8 +27,7 @@ def _area(K, N, device):
     m = _area_cache.get(key)
     if m is None:
         m = torch.zeros(N, K, dtype=torch.float32)
-        for o in range(N):
-            s0, s1 = (o * K) // N, -((-(o + 1) * K) // N)
+        for o, (s0, s1) in enumerate(_area_windows(K, N)):
             m[o, s0:s1] = 1.0 / (s1 - s0)
         m = _area_cache[key] = m.to(device)
     return m

@@ -631,7 +631,8 @@ int oniris_attn_f32_bwd(const OnirisAttnF32Args* args, oniris_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * VAE decoder (reference: edm2/vae/vae.py EncoderDecoder(type='decoder') :167-204 and VAE.decode / latents_to_frames
- * :253-318), inference, fp32 throughout.  Activations channels-last fp32 [B][T][H][W][C], C <= 64.  csrc/vae.hip.
+ * :253-318), inference, fp32 throughout.  Activations channels-last fp32 [B][T][H][W][C], C <= 64.  csrc/vae.hip; the 3x3
+ * tile kernel of oniris_vae_res_a / _res_b is csrc/vae_conv3.h.
  * oniris_vae_temb: the FiLM scale | shift of every ResBlock for one decode, emb[r][b][2 C_r] = t_cond(MPFourier(t_b))
  * (vae.py:76-80); table [3 n_res_blocks] int32 = {offset of block r's freqs[2C] | phases[2C] | W[2C][2C] | bias[2C] in params,
  * 2 C_r, offset of block r in emb divided by B}.
@@ -683,7 +684,7 @@ int oniris_vae_latents(const float* x, int B, int T, int H, int W, int C, const 
                        int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, oniris_stream_t stream);
 
 /* VAE training (reference: VAE.forward vae.py:228-237 in training mode), added within ABI 14, fp32 throughout, channels-last
- * activations.  csrc/vae_train.hip.  The training forward runs the inference launches of the 1x1 stages (oniris_vae_down / _up /
+ * activations.  csrc/vae_train.hip (the 3x3 tile kernel: csrc/vae_conv3.h).  The training forward runs the inference launches of the 1x1 stages (oniris_vae_down / _up /
  * _out) and, per ResBlock, these two instead of oniris_vae_res_a / _res_b; it keeps one tensor per ResBlock beyond the block
  * input x: a, the raw output of the group-causal conv.  y = SiLU(RMS(x) (1 + scale) + shift) and u = SiLU(RMS(a)) are recomputed
  * wherever they are an operand.  Without a cache the time prefix of the group-causal conv is the first g frames of y, detached

@@ -90,6 +90,7 @@ def test_every_width_against_the_restatement():
     outs, grads, _ = _step(vae, x.to(DEV), ts.to(DEV), noise.to(DEV))
     ref_outs, ref_grads = RT.grads({k: v.cpu() for k, v in vae.state_dict().items()}, vae.kwargs, x, ts, noise)
     _compare(outs, grads, ref_outs, ref_grads, "widths 32/64/8")
+    assert torch.equal(outs["mean"].detach(), vae.encode(x.to(DEV))[0])
 
 
 def test_autograd_contract():
