@@ -78,6 +78,15 @@ def test_g16_on_the_hip_path():
         assert b.grad is None, n
 
 
+def step_against_the_restatement(vae, x, ts, noise, what, ref=None):
+    """One training step of `vae` (on the GPU, in training mode) on CPU inputs against the restatement in float64 on the CPU (or
+    its ready result `ref`), with the bounds of G16; mean is bit for bit what encode gives."""
+    outs, grads, _ = _step(vae, x.to(DEV), ts.to(DEV), noise.to(DEV))
+    ref_outs, ref_grads = ref or RT.grads({k: v.cpu() for k, v in vae.state_dict().items()}, vae.kwargs, x, ts, noise)
+    _compare(outs, grads, ref_outs, ref_grads, what)
+    assert torch.equal(outs["mean"].detach(), vae.encode(x.to(DEV))[0])
+
+
 def test_every_width_against_the_restatement():
     """channels [3, 32, 64, 8]: encoder widths 32 / 64 / 8 at g = 4 / 2 / 1, decoder widths 8 / 64 / 32 at g = 1 / 2 / 4, K = 256
     and 512 into the compressions -- with G16 every (channel capacity, frames per thread) pair of the training path -- against
@@ -87,10 +96,7 @@ def test_every_width_against_the_restatement():
     g = torch.Generator().manual_seed(1612)
     x = torch.rand(2, 3, 8, 8, 12, generator=g) * 2 - 1
     ts, noise = torch.rand(2, generator=g) * 0.1, torch.randn(2, 8, 2, 2, 3, generator=g)
-    outs, grads, _ = _step(vae, x.to(DEV), ts.to(DEV), noise.to(DEV))
-    ref_outs, ref_grads = RT.grads({k: v.cpu() for k, v in vae.state_dict().items()}, vae.kwargs, x, ts, noise)
-    _compare(outs, grads, ref_outs, ref_grads, "widths 32/64/8")
-    assert torch.equal(outs["mean"].detach(), vae.encode(x.to(DEV))[0])
+    step_against_the_restatement(vae, x, ts, noise, "widths 32/64/8")
 
 
 def test_autograd_contract():

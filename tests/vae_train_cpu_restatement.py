@@ -24,11 +24,13 @@ def _area_channels(x, cout):
     return torch.stack(outs, dim=1)
 
 
-def _res_block(sd, q, x, g, t):
-    """vae.py:74-93 in training mode without a cache."""
+def _res_block(sd, q, x, g, t, emb=None):
+    """vae.py:74-93 in training mode without a cache.  emb (B, 2C): a ready scale | shift in place of the one computed from t."""
     B, C, T, H, W = x.shape
     y = _rms(x)
-    if t is not None:
+    if emb is not None:
+        y = y * (1 + emb[:, :C, None, None, None]) + emb[:, C:, None, None, None]
+    elif t is not None:
         four = torch.cos(t.float()[:, None] * sd[q + "fourier_cond.freqs"][None].float() +      # MPFourier works in fp32
                          sd[q + "fourier_cond.phases"][None].float()) * math.sqrt(2)            # whatever t is (utils.py:145-150)
         four = four.to(t.dtype)
@@ -42,6 +44,28 @@ def _res_block(sd, q, x, g, t):
     return x + F.conv3d(y, sd[q + "conv3d1.weight"], sd[q + "conv3d1.bias"], padding=(0, 1, 1))
 
 
+def down(x, weight, bias, tc, sc):
+    """vae.py:157-161, :109-122: 'b c (t tc) (h hc) (w wc) -> b (tc hc wc c) t h w', the compression conv plus the channel-area
+    residual of the rearranged input."""
+    B, C, T, H, W = x.shape
+    T, H, W = T // tc, H // sc, W // sc
+    x = x.reshape(B, C, T, tc, H, sc, W, sc).permute(0, 3, 5, 7, 1, 2, 4, 6).reshape(B, tc * sc * sc * C, T, H, W)
+    return F.conv3d(x, weight, bias) + _area_channels(x, weight.shape[0])
+
+
+def up(x, weight, bias, tc, sc):
+    """vae.py:96-133, :148-164: the decompression conv, then 'b (tc hc wc c) t h w -> b c (t tc) (h hc) (w wc)'."""
+    C = x.shape[1]
+    x = F.conv3d(x, weight, bias)
+    B, _, T, H, W = x.shape
+    return x.reshape(B, tc, sc, sc, C, T, H, W).permute(0, 4, 5, 1, 6, 2, 7, 3).reshape(B, C, T * tc, H * sc, W * sc)
+
+
+def out(x, weight, bias):
+    """vae.py:128-141: the final conv plus the channel-area residual."""
+    return F.conv3d(x, weight, bias) + _area_channels(x, weight.shape[0])
+
+
 def forward(sd, kwargs, x, t_sample, noise):
     """x (B, 3, T, H, W), t_sample (B,), noise (the shape of mean) -> (r_mean, r_logvar, mean) of VAE.forward in training mode
     with t_b = t_sample and randn_like(mean) = noise."""
@@ -52,10 +76,7 @@ def forward(sd, kwargs, x, t_sample, noise):
     groups = [int(g) for g in np.cumprod(tcs)[::-1]]
     for i, (Cout, tc, sc, g) in enumerate(zip(channels[1:], tcs, scs, groups)):
         p = f"encoder.encoder_blocks.{i}."
-        B, C, T, H, W = x.shape
-        T, H, W = T // tc, H // sc, W // sc
-        x = x.reshape(B, C, T, tc, H, sc, W, sc).permute(0, 3, 5, 7, 1, 2, 4, 6).reshape(B, tc * sc * sc * C, T, H, W)
-        x = F.conv3d(x, sd[p + "compression_block.weight"], sd[p + "compression_block.bias"]) + _area_channels(x, Cout)
+        x = down(x, sd[p + "compression_block.weight"], sd[p + "compression_block.bias"], tc, sc)
         for j in range(n_res):
             x = _res_block(sd, p + f"res_blocks.{j}.", x, g, None)
     mean = x
@@ -70,12 +91,10 @@ def forward(sd, kwargs, x, t_sample, noise):
     groups = [int(g) for g in np.cumprod(tcs)]
     for i, (C, Cout, tc, sc, g) in enumerate(zip(channels[:-1], outs, tcs, scs, groups)):
         p = f"decoder.encoder_blocks.{i}."
-        x = F.conv3d(x, sd[p + "decompression_block.weight"], sd[p + "decompression_block.bias"])
-        B, _, T, H, W = x.shape
-        x = x.reshape(B, tc, sc, sc, C, T, H, W).permute(0, 4, 5, 1, 6, 2, 7, 3).reshape(B, C, T * tc, H * sc, W * sc)
+        x = up(x, sd[p + "decompression_block.weight"], sd[p + "decompression_block.bias"], tc, sc)
         for j in range(n_res):
             x = _res_block(sd, p + f"res_blocks.{j}.", x, g, t)
-        x = F.conv3d(x, sd[p + "final_conv.weight"], sd[p + "final_conv.bias"]) + _area_channels(x, Cout)
+        x = out(x, sd[p + "final_conv.weight"], sd[p + "final_conv.bias"])
     r_mean, r_logvar = x.split(x.shape[1] // 2, dim=1)
     return r_mean, r_logvar * torch.exp(sd["decoder.logvar_multiplier"]), mean
 
