@@ -60,10 +60,7 @@ __global__ __launch_bounds__(256) void conv1x1_few_kernel(const ConvDev d) {
         if (act_mine && pvalid && c < Cin) {
           bf16x8 av;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float z = bf2f(o[k]);
-            av[k] = f2bf(z * sigmoid_fast(z) * (1.0f / 0.596f));
-          }
+          for (int k = 0; k < 8; ++k) av[k] = f2bf(conv_silu(bf2f(o[k])));
           *(bf16x8*)((bf16*)a.act_out + prow * Cin + c) = av;
         }
       }
@@ -87,11 +84,7 @@ __global__ __launch_bounds__(256) void conv1x1_few_kernel(const ConvDev d) {
   if (a.epi == ONIRIS_EPI_MPSUM) {
     const bf16x4 rv = *(const bf16x4*)((const bf16*)a.res + o);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float z = a.ta * bf2f(rv[t]) + a.tb * v[t];
-      if (a.clip > 0.f) z = fminf(fmaxf(z, -a.clip), a.clip);
-      v[t] = z;
-    }
+    for (int t = 0; t < 4; ++t) v[t] = conv_mpsum(bf2f(rv[t]), v[t], a.ta, a.tb, a.clip);
   }
   bf16x4 ov;
 #pragma unroll

@@ -11,7 +11,7 @@
 // blocks) are consecutive in a workgroup's run, so the activation chunk is re-read from L2, not HBM.
 // Rows are 128 bytes, unpadded (the DMA image is lane-linear); the 16-byte pieces are XOR-swizzled on the source side
 // with (row >> 1) & 7, which makes the 16-row groups of a ds_read_b128 conflict-free (same scheme as the attention
-// K tile).  Epilogues: none / mp_sum(+clip) with optional raw output, as conv_kernels.h; <ACTB>: ONIRIS_EPI_ACT_BWD.
+// K tile).  Epilogues: none / mp_sum(+clip) with optional raw output (conv_parts.h); <ACTB>: ONIRIS_EPI_ACT_BWD.
 #pragma once
 #include "conv_kernels.h"
 #include "lds_dma.h"
@@ -43,11 +43,8 @@ __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
   // this workgroup's contiguous run of tiles inside its XCD's range (tile = position tile * ncb + channel block)
   int tl, tl_hi, tl_step;
   {
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7;
-    const int q = ntiles >> 3, rr = ntiles & 7;
-    const int lo = (xcd < rr) ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q;
-    tl_hi = lo + q + ((xcd < rr) ? 1 : 0);
-    tl_step = (nwg - xcd + 7) >> 3;
+    int lo;
+    conv_xcd_range(ntiles, lo, tl_hi, tl_step);
     const int cnt = tl_hi - lo, per = (cnt + tl_step - 1) / tl_step;        // contiguous sub-runs: channel blocks of
     tl = lo + (blockIdx.x >> 3) * per;                                      // one position tile stay together
     tl_hi = (tl + per < tl_hi) ? tl + per : tl_hi;
@@ -147,15 +144,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const long long prow = m0 + wp * 64 + m * 32;            // first position of this 32-position block
-      auto put = [&](int nt, const float (&v)[16]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) o[k] = f2bf(v[4 * g + k]);
-          *(bf16x4*)(ep + r * EROW + (nt * 32 + 8 * g + 4 * h) * 2) = o;
-        }
-      };
+      auto put = [&](int nt, const float (&v)[16]) __attribute__((always_inline)) { conv_stage_row(ep + r * EROW, nt * 32, h, v); };
       auto flush = [&](bf16* dst) __attribute__((always_inline)) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
@@ -212,11 +201,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_glds_kernel(const ConvDev d) {
             for (int k = 0; k < 4; ++k) rv[k] = f2bf(0.f);
             if (valid && co < Cout) rv = *(const bf16x4*)((const bf16*)a.res + obase + co);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              float o = a.ta * bf2f(rv[k]) + a.tb * acc[m][nt][4 * g + k];
-              if (a.clip > 0.f) o = fminf(fmaxf(o, -a.clip), a.clip);
-              v[4 * g + k] = o;
-            }
+            for (int k = 0; k < 4; ++k) v[4 * g + k] = conv_mpsum(bf2f(rv[k]), acc[m][nt][4 * g + k], a.ta, a.tb, a.clip);
           }
           put(nt, v);
         }

@@ -212,11 +212,7 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
   } else {
     // ------------------------------------------------------------------------------------------------ compute waves
     const int r = lane & 31, h = lane >> 5;
-    // lane -> position inside a 32-position half (4 patch rows x 8): a 16-lane read group takes patch rows (0,2) / (1,3),
-    // i.e. halo rows 24 = 8 (mod 16) apart (conv_glds.h, PW == 8)
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    const int pr = ((k >> 3) * 2 + (ga ? 0 : 1)) * 8 + (k & 7);
+    const int pr = conv_lane_pos<8>(r);            // lane -> position inside a 32-position half (4 patch rows x 8)
     int xa[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) xa[m] = (4 * m + (pr >> 3)) * HW_ + (pr & 7);          // halo row of tap (0, 0)
@@ -340,11 +336,7 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
         const uint2 t2 = make_uint2(epre0, epre1);
         const bf16x4 rv = __builtin_bit_cast(bf16x4, t2);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float t = a.ta * bf2f(rv[i]) + a.tb * v[i];
-          if (a.clip > 0.f) t = fminf(fmaxf(t, -a.clip), a.clip);
-          ov[i] = f2bf(t);
-        }
+        for (int i = 0; i < 4; ++i) ov[i] = f2bf(conv_mpsum(bf2f(rv[i]), v[i], a.ta, a.tb, a.clip));
         *(bf16x4*)((bf16*)a.out + o) = ov;
       } else {
 #pragma unroll
@@ -355,10 +347,7 @@ __global__ __launch_bounds__(512, 2) void conv_eval1_kernel(const ConvDev d) {
                                __builtin_bit_cast(float, epre3)};
           bf16x4 o2;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float z = bf2f(ov[i]) * cv[i];             // the activation sees the bf16-rounded y
-            o2[i] = f2bf(z * sigmoid_fast(z) * (1.f / 0.596f));
-          }
+          for (int i = 0; i < 4; ++i) o2[i] = f2bf(conv_emb_silu(v[i], cv[i]));
           *(bf16x4*)((bf16*)a.out2 + o) = o2;
         }
       }

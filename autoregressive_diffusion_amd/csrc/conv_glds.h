@@ -1,7 +1,7 @@
 // Gated causal 3x3 convolution, DART training layout (S = 2 slots + 2 context frames), LDS-DMA variant for gfx950.
 //
 // Same math and HBM layout as conv_kernels.h (implicit GEMM, D[co][position], own / ctx0 / ctx1 phases per 32-channel
-// chunk), different staging:
+// chunk; lane map, work distribution and epilogue arithmetic: conv_parts.h), different staging:
 //   * the halo image and the weight slab of a phase go global -> LDS with `global_load_lds_dwordx4` (no VGPR staging,
 //     no ds_write pass); the two LDS buffers alternate, so the DMA of phase i+1 runs under the MFMAs of phase i and
 //     there is ONE barrier per phase;
@@ -82,20 +82,12 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
   const int wp = wave % NWP, wc = wave / NWP;             // position group / channel group of this wave
   const int H = a.H, W = a.W, T = a.T, Cin = a.Cin, HWp = a.H * a.W;
 
-  // ---- this workgroup's run of tiles.  Workgroup ids go round-robin over the 8 XCDs; XCD k owns the CONTIGUOUS tile
-  // range [lo, hi) (channel block fastest, then x, y, frame, batch) and its workgroups stride through it together, so
-  // the blocks that share an activation halo (other channel blocks, neighbouring tiles, the next two frames whose
-  // context this frame is) run at the same time on the same L2.
+  // ---- this workgroup's run of tiles: its XCD's contiguous range of tile ids (channel block fastest, then x, y, frame,
+  // batch), which the XCD's workgroups stride through together (conv_xcd_range)
   const int ntiles = d.ntx * d.nty * d.ntt * a.B * d.ncob;
   int tl, tl_hi, tl_step;
-  {
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7;
-    const int q = ntiles >> 3, rr = ntiles & 7;
-    const int lo = (xcd < rr) ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q;
-    tl_hi = lo + q + ((xcd < rr) ? 1 : 0);
-    tl_step = (nwg - xcd + 7) >> 3;
-    tl = lo + (blockIdx.x >> 3);
-  }
+  conv_xcd_range(ntiles, tl, tl_hi, tl_step);
+  tl += blockIdx.x >> 3;
   if (tl >= tl_hi) return;
   struct Tile { int co0, x0, y0, t0, b; };
   auto decode = [&](int id) __attribute__((always_inline)) {
@@ -108,17 +100,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
     return t;
   };
 
-  // lane -> position inside a 32-position tile (see conv_kernels.h: 16-lane read groups get 16 consecutive halo rows)
-  int pr = r;
-  if constexpr (PW == 16) {
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    pr = (ga ? 0 : 16) + k;
-  } else {                                                // PW == 8: a read group takes patch rows (0,2) resp. (1,3)
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    pr = ((k >> 3) * 2 + (ga ? 0 : 1)) * 8 + (k & 7);
-  }
+  const int pr = conv_lane_pos<PW>(r);                    // lane -> position inside a 32-position tile
   int arow[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
@@ -419,15 +401,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
 #pragma unroll
           for (int i = 0; i < 16; ++i) v[i] = CTX ? __builtin_fmaf(cctx, accc[m][nt][i], cown * acc[s][m][nt][i]) : cown * acc[s][m][nt][i];
         };
-        auto put = [&](int nt, const float (&v)[16]) __attribute__((always_inline)) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            bf16x4 o;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = f2bf(v[4 * g + k]);
-            *(bf16x4*)(ep + pr * EROW + (nt * 32 + 8 * g + 4 * h) * 2) = o;
-          }
-        };
+        auto put = [&](int nt, const float (&v)[16]) __attribute__((always_inline)) { conv_stage_row(ep + pr * EROW, nt * 32, h, v); };
         float v[16];
         if (a.epi == ONIRIS_EPI_MPSUM) {     // (the res loads queue behind the DMA just issued: vmcnt is in order)
           if (a.out2) {                      // raw conv output (needed for d gate)
@@ -448,14 +422,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
               for (int k = 0; k < 4; ++k) rv[k] = f2bf(0.f);
               if (co < a.Cout && lvalid) rv = *(const bf16x4*)((const bf16*)a.res + obase + co);
 #pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                float o = a.ta * bf2f(rv[k]) + a.tb * v[4 * g + k];
-                if (a.clip > 0.f) {
-                  o = fminf(fmaxf(o, -a.clip), a.clip);
-                  clip_hit |= !(fabsf(bf2f(f2bf(o))) < a.clip);     // (what the backward's mask tests: the STORED value)
-                }
-                v[4 * g + k] = o;
-              }
+              for (int k = 0; k < 4; ++k) v[4 * g + k] = conv_mpsum(bf2f(rv[k]), v[4 * g + k], a.ta, a.tb, a.clip, clip_hit);
             }
             put(nt, v);
           }
@@ -468,16 +435,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
               raw(nt, v);
-#pragma unroll
-              for (int g = 0; g < 4; ++g) {
-                const float4 ev = *(const float4*)(stg + ((s * FT + lft) * BN + wc * NT * 32 + nt * 32 + 8 * g + 4 * h) * 4);
-                const float cvv[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                  const float z = bf2f(f2bf(v[4 * g + k])) * cvv[k];     // the activation sees the bf16-rounded y
-                  v[4 * g + k] = z * sigmoid_fast(z) * (1.f / 0.596f);
-                }
-              }
+              conv_emb_silu16(v, stg, (s * FT + lft) * BN + wc * NT * 32 + nt * 32, h);
               put(nt, v);
             }
             flush((bf16*)a.out2, blk);
@@ -494,9 +452,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8) ? 2 : 1) void conv_glds_kernel(c
         }
       }
     }
-    if (a.clip_flag && __builtin_amdgcn_ballot_w64(clip_hit) != 0ull) {      // (practically never: OnirisConvArgs.clip_flag)
-      if (lane == 0) atomicOr(a.clip_flag, 1);
-    }
+    conv_report_clip(a.clip_flag, clip_hit, lane);
     CSTAMP(6)
     if (!more) break;
     cur = nxt;

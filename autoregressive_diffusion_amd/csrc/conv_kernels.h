@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "../../include/oniris.h"
+#include "conv_parts.h"
 
 template <int PW_, int NPOS_ = 128>
 struct Patch {
@@ -128,15 +129,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
     co0 = (bid / a.B) * BN;
   }
 
-  // ---- this lane's position.  For 16-wide patches the 32 positions of a wave (2 patch rows x 16 px) are dealt to
-  // the lanes so that each 16-lane group of a ds_read_b128 ({0-3,12-15,20-27} / {4-11,16-19,28-31}) reads 16
-  // CONSECUTIVE halo rows: with 80-byte rows that is conflict-free (the natural order is 2-way on every read).
+  // ---- this lane's position (16-wide patches: dealt so that the fragment reads are conflict-free, conv_lane_pos)
   int pr = r;
-  if constexpr (TAPS == 9 && PW == 16) {
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    pr = (ga ? 0 : 16) + k;
-  }
+  if constexpr (TAPS == 9 && PW == 16) pr = conv_lane_pos<16>(r);
   const int p = wave * 32 + pr;
   int ft = 0, py = 0, px = 0, arow = p;
   if constexpr (TAPS == 9) {
@@ -283,10 +278,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
             if (act_mine && a.act_out && q < T * HWp && c < Cin) {
               bf16x8 av;
 #pragma unroll
-              for (int k = 0; k < 8; ++k) {
-                const float z = bf2f(o[k]);
-                av[k] = f2bf(z * sigmoid_fast(z) * (1.0f / 0.596f));
-              }
+              for (int k = 0; k < 8; ++k) av[k] = f2bf(conv_silu(bf2f(o[k])));
               *(bf16x8*)((bf16*)a.act_out + ((size_t)(b * S + s) * T * HWp + q) * Cin + c) = av;
             }
           }
@@ -474,14 +466,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
     // helper: write v (as bf16) into the wave tile
     auto stage = [&]() __attribute__((always_inline)) {
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) o[k] = f2bf(v[nt][4 * g + k]);
-          *(bf16x4*)(ep + pr * EROW + (nt * 32 + 8 * g + 4 * h) * 2) = o;
-        }
+      for (int nt = 0; nt < NT; ++nt) conv_stage_row(ep + pr * EROW, nt * 32, h, v[nt]);
     };
     if constexpr (ACTB) {
       // the rounded dgrad goes through the wave's transpose tile; the adjoint of mp_cat + mp_silu is applied to each 16-byte piece
@@ -513,11 +498,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
           for (int k = 0; k < 4; ++k) rv[k] = f2bf(0.f);
           if (valid && co < a.Cout) rv = *(const bf16x4*)((const bf16*)a.res + obase + co);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            float o = a.ta * bf2f(rv[k]) + a.tb * v[nt][4 * g + k];
-            if (a.clip > 0.f) o = fminf(fmaxf(o, -a.clip), a.clip);
-            v[nt][4 * g + k] = o;
-          }
+          for (int k = 0; k < 4; ++k) v[nt][4 * g + k] = conv_mpsum(bf2f(rv[k]), v[nt][4 * g + k], a.ta, a.tb, a.clip);
         }
     }
     stage();
@@ -532,10 +513,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8) ? 2 : 2) void conv_fwd_kernel(co
           if (valid && co < a.Cout) ev = *(const float4*)((const float*)a.escale + (size_t)n * (a.escale_pitch ? a.escale_pitch : a.Cout) + co);
           const float cvv[4] = {ev.x, ev.y, ev.z, ev.w};
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float z = bf2f(f2bf(v[nt][4 * g + k])) * cvv[k];     // the activation sees the bf16-rounded y
-            v[nt][4 * g + k] = z * sigmoid_fast(z) * (1.f / 0.596f);
-          }
+          for (int k = 0; k < 4; ++k) v[nt][4 * g + k] = conv_emb_silu(v[nt][4 * g + k], cvv[k]);
         }
       stage();
       flush((bf16*)a.out2, blk);

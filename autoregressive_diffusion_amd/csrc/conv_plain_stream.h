@@ -5,14 +5,14 @@
 // LDS-DMA (both frames' halos + the weight slab, re-copied for every tile) in front of 36 MFMAs per wave and an epilogue
 // that stops all eight waves -- 0.44 of its HBM roofline.  The level is HBM-bound by a factor of three (0.5-0.8 GB per
 // launch against 31 us of MFMA work at B = 8), so what matters is bytes in flight and that nothing waits for anything else.
-// Here (the forward half of conv_stream.h without its context ring):
+// Here (the forward half of conv_stream.h without its context ring; what the two have in common is in conv_parts.h):
 //   * a workgroup (4 waves, an 8x16-pixel tile, TWO per CU: they share no barrier and drift apart) owns one spatial tile
 //     and WALKS the frames of a segment; per frame it copies ONE halo image (10 x 18 pixels, 11.25 KB) into a four-slot
 //     ring, three frames ahead (counted vmcnt: the stores of the previous epilogues drain under the next frames);
 //   * the weights (9 taps x 32 x 32) live in REGISTERS for the whole walk, 18 fragments per wave; wave w computes pixel rows
 //     2w, 2w + 1 of the tile: 18 MFMAs per frame in two independent chains, one LDS fragment read per MFMA, no exchange
 //     between the waves;
-//   * epilogues as conv_stream.h / conv_glds.h (none | emb-scale + SiLU | mp_sum + clip with the clip report), lane =
+//   * epilogues none | emb-scale + SiLU | mp_sum + clip with the clip report (the arithmetic: conv_parts.h), lane =
 //     position, bf16 results transposed through the wave's own LDS tile, 16-byte stores (non-temporal on big tensors).
 // Same operand rounding (bf16 operands, fp32 accumulation); the summation order over (tap, k) is the tile kernel's with the
 // two k-steps of a tap in separate chains, joined at the end.
@@ -29,7 +29,7 @@ struct ConvPlainStreamDev {
 __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPlainStreamDev d) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TAPS = 9, KS = 2, NST = TAPS * KS, HW_ = 18, HALO = 10 * HW_, HBUF = 12288, NRING = 4, DEPTH = 3;
-  constexpr int EROW = 80, STGB = 32 * EROW;
+  constexpr int STGB = 32 * CONV_STREAM_EROW;
   constexpr int STG = NRING * HBUF, ESC = STG + 4 * STGB, LDS_BYTES = ESC + NRING * 128;     // emb-scale rows [ring slot][32] fp32
   static_assert(HALO * 64 <= HBUF && 2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
@@ -42,25 +42,15 @@ __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPla
   const int frame_elems = HWp * Cin;
 
   // ---- this workgroup's (tile, segment); workgroup ids go round-robin over the XCDs: XCD k takes a contiguous range of units
-  int u;
-  {
-    const int n = gridDim.x, xcd = blockIdx.x & 7, q = n >> 3, rr = n & 7;
-    u = ((xcd < rr) ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (blockIdx.x >> 3);
-  }
+  int u = conv_xcd_unit();
   const int x0 = (u % d.ntx) * 16; u /= d.ntx;
   const int y0 = (u % d.nty) * 8;
   const int seg = u / d.nty;
   const int n_lo = seg * d.seglen, n_hi = min(d.nfr, n_lo + d.seglen), nfr = n_hi - n_lo;
   if (nfr <= 0) return;
 
-  // ---- lane -> position inside the wave's 32-position tile (2 pixel rows x 16; conv_kernels.h: 16-lane read groups take 16
-  // consecutive halo rows)
-  int pr;
-  {
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    pr = (ga ? 0 : 16) + k;
-  }
+  // ---- lane -> position inside the wave's 32-position tile (2 pixel rows x 16)
+  const int pr = conv_lane_pos<16>(r);
   int xaddr[TAPS];
 #pragma unroll
   for (int tap = 0; tap < TAPS; ++tap) {
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPla
   }
 
   // ---- DMA descriptors: 720 pieces of 16 B per halo image, three per thread
-  constexpr int OOB = (int)0x80000000;
+  constexpr int OOB = CONV_STREAM_OOB;
   int hv[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -98,43 +88,14 @@ __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPla
 
   // ---- weights -> registers (once): lane (r = co row, h = 8-channel group of the k-step)
   bf16x8 wreg[NST];
-  {
-    const bf16* wsrc = (const bf16*)a.w_own;
-#pragma unroll
-    for (int i = 0; i < NST; ++i)
-      wreg[i] = *(const bf16x8*)(wsrc + ((size_t)(i / KS) * a.CoutP + r) * a.CinP + (i % KS) * 16 + h * 8);
-  }
-#pragma unroll
-  for (int i = 0; i < NST; ++i) asm volatile("" : "+v"(wreg[i]));        // consumed before any LDS-DMA is in flight
+  conv_stream_weights(wreg, (const bf16*)a.w_own, a, r, h);
 
   // ---- epilogue inputs (see conv_stream.h: nothing in the frame loop is an ordinary vector load)
   const int ppy = 2 * uw + (pr >> 4), ppx = pr & 15;                     // pixel of this lane's output position inside the 8x16 tile
   const int pix = (y0 + ppy) * W + x0 + ppx;
-  const i32x4 rs_r = make_rsrc(mps ? a.res : (const void*)oniris_fill_rows, mps ? d.nfr * HWp * Cout * 2 : 0);
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-  u32x2 resq[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) { resq[g][0] = 0u; resq[g][1] = 0u; }
-  int rvoff[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) rvoff[g] = (8 * g + 4 * h < Cout) ? (pix * Cout + 8 * g + 4 * h) * 2 : OOB;
-  auto load_res = [&](int f) __attribute__((always_inline)) {
-    const int so = __builtin_amdgcn_readfirstlane((f * HWp * Cout) * 2);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=v"(resq[g]) : "v"(rvoff[g]), "s"(rs_r), "s"(so) : "memory");
-  };
-  auto wait_vm = [&](int n) __attribute__((always_inline)) {             // s_waitcnt vmcnt(n), n wave-uniform
-    if (n > 40) n = 40;                                                   // (waiting for more than asked is always correct)
-    switch (n) {
-#define PSW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-      PSW(0) PSW(1) PSW(2) PSW(3) PSW(4) PSW(5) PSW(6) PSW(7) PSW(8) PSW(9) PSW(10) PSW(11) PSW(12) PSW(13) PSW(14) PSW(15) PSW(16) PSW(17)
-      PSW(18) PSW(19) PSW(20) PSW(21) PSW(22) PSW(23) PSW(24) PSW(25) PSW(26) PSW(27) PSW(28) PSW(29) PSW(30) PSW(31) PSW(32) PSW(33)
-      PSW(34) PSW(35) PSW(36) PSW(37) PSW(38) PSW(39)
-      default: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-#undef PSW
-    }
-  };
+  ConvStreamRes res;
+  res.init(mps ? a.res : (const void*)oniris_fill_rows, mps ? d.nfr * HWp * Cout * 2 : 0, pix, Cout, h);
+  constexpr int VM_SAT = 40;                                             // where the counted waits saturate
 
   // ---- prologue copies: the first DEPTH frames of the segment
 #pragma unroll 1
@@ -155,12 +116,12 @@ __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPla
       const int steps_behind = min(i, DEPTH - 1);                         // full steps issued after frame f's copies ... at most
       younger += steps_behind * (n_res + n_st);
       if (i >= DEPTH) younger += n_st;                                    // the stores of step i-DEPTH, issued right after f's copies
-      wait_vm(younger);
+      conv_wait_vm<VM_SAT>(younger);
     }
     __syncthreads();                       // ... everybody's have; and everybody is done with frame f - 1 (its ring slot is free)
     typedef const __attribute__((address_space(4))) float cfloat_t;
     const float cown = a.coef_own ? ((cfloat_t*)(size_t)a.coef_own)[f] : 1.f;
-    if (mps) load_res(f);                  // (in front of the copies: waited for by count, see the epilogue)
+    if (mps) res.load((f * HWp * Cout) * 2);     // (in front of the copies: waited for by count, conv_parts.h)
     const bool has_next = i + DEPTH < nfr;
     if (has_next) issue(f + DEPTH);
 
@@ -189,71 +150,20 @@ __global__ __launch_bounds__(256, 2) void conv_plain_stream_kernel(const ConvPla
 
     // ---- epilogue (lane = position; bf16 results transposed through the wave's LDS tile)
     const size_t blk = (size_t)f * HWp;
-    auto put = [&](const float (&vv)[16]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = f2bf(vv[4 * g + k]);
-        *(bf16x4*)(ep + pr * EROW + (8 * g + 4 * h) * 2) = o;
-      }
-    };
-    auto flush = [&](bf16* dst) __attribute__((always_inline)) {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int id = it * 64 + lane, row = id >> 2, part = id & 3;
-        const size_t px_ = (size_t)(y0 + 2 * uw + (row >> 4)) * W + x0 + (row & 15);
-        if (part * 8 < Cout) {
-          const u32x4 v_ = *(const u32x4*)(ep + row * EROW + part * 16);
-          u32x4* o_ = (u32x4*)(dst + (blk + px_) * Cout + part * 8);
-          if (d.nt) __builtin_nontemporal_store(v_, o_); else *o_ = v_;
-        }
-      }
-    };
+    ConvStreamOut out;
+    out.ep = ep; out.lane = lane; out.pr = pr; out.h = h;
+    out.y = y0 + 2 * uw; out.x = x0;
+    out.W = W; out.Cout = Cout; out.nontemporal = d.nt != 0;
     if (mps) {
-      // the residual loads of this step are older than its copies: n_dma younger instructions may still be in flight
-      wait_vm(has_next ? n_dma : 0);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(resq[g]));
-      float o[16];
-      bool clip_hit = false;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const bf16x4 rv = __builtin_bit_cast(bf16x4, resq[g]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float q = a.ta * bf2f(rv[k]) + a.tb * v[4 * g + k];
-          if (a.clip > 0.f) {
-            q = fminf(fmaxf(q, -a.clip), a.clip);
-            clip_hit |= !(fabsf(bf2f(f2bf(q))) < a.clip);         // (what the backward's mask tests: the STORED value)
-          }
-          o[4 * g + k] = q;
-        }
-      }
-      if (a.out2) { put(v); flush((bf16*)a.out2); }
-      put(o);
-      flush((bf16*)a.out);
-      if (a.clip_flag && __builtin_amdgcn_ballot_w64(clip_hit) != 0ull) {    // (practically never: OnirisConvArgs.clip_flag)
-        if (lane == 0) atomicOr(a.clip_flag, 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // one more op in the vmcnt stream than the counted waits know
-      }
+      conv_stream_mpsum<VM_SAT>(a, res, out, v, blk, has_next ? n_dma : 0, [] {});
       continue;
     }
-    put(v);
-    flush((bf16*)a.out);
+    out.put(v);
+    out.flush((bf16*)a.out, blk);
     if (emb) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 ev = *(const float4*)(smem + ESC + (f & (NRING - 1)) * 128 + (8 * g + 4 * h) * 4);
-        const float cvv[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float z = bf2f(f2bf(v[4 * g + k])) * cvv[k];     // the activation sees the bf16-rounded y
-          v[4 * g + k] = z * sigmoid_fast(z) * (1.f / 0.596f);
-        }
-      }
-      put(v);
-      flush((bf16*)a.out2);
+      conv_emb_silu16(v, smem + ESC + (f & (NRING - 1)) * 128, 0, h);
+      out.put(v);
+      out.flush((bf16*)a.out2, blk);
     }
   }
 #endif

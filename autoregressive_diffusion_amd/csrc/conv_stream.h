@@ -12,7 +12,9 @@
 //     own-frame slab and compute both slots of their 32 positions, wave 2 / 3 holds the slab of context frame t-2 / t-1 and
 //     computes its product for both position tiles -- 36 MFMAs per wave and frame, one LDS fragment read per MFMA;
 //   * the partial products meet through LDS (six arrays of 16 floats per lane), then wave w finishes slot w >> 1 of tile
-//     w & 1 (waves 2,3 also the un-gated context product y3): same epilogue arithmetic as conv_glds.h.
+//     w & 1 (waves 2,3 also the un-gated context product y3); the epilogue arithmetic is conv_parts.h's, as in every
+//     forward kernel.  What this kernel shares with conv_plain_stream.h (weights into registers, the residual loads, the
+//     counted waits, the staging tile and its flush, the mp_sum epilogue) is there too.
 // Bit-compatible INPUT rounding (bf16 operands, fp32 accumulation); the summation order over (tap, k) equals the tile
 // kernel's per product, the own + context combination is the same fma.
 #pragma once
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TAPS = 9, KS = 2, NST = TAPS * KS, HW_ = 18, HALO = 6 * 18, HBUF = 7168;     // 108 rows x 64 B, padded to 112
   constexpr int NXS0 = ALIAS ? 4 : 2, NCTX = ALIAS ? 0 : 3;
-  constexpr int EROW = 80, STGB = 32 * EROW;
+  constexpr int STGB = 32 * CONV_STREAM_EROW;
   constexpr int XS0 = 0, XS1 = NXS0 * HBUF, CTXR = XS1 + 2 * HBUF, EXCH = CTXR + NCTX * HBUF;
   // six exchange arrays of 16 x 64 floats; the forward kernel has room for a separate staging tile per wave, the dgrad
   // kernel (one more halo ring) stages through the exchange arrays behind a third barrier
@@ -62,11 +64,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
 
   // ---- this workgroup's (sequence, tile, segment); workgroup ids go round-robin over the XCDs: XCD k takes a contiguous
   // range of units, so tiles that share halo rows sit behind the same L2
-  int u;
-  {
-    const int n = gridDim.x, xcd = blockIdx.x & 7, q = n >> 3, rr = n & 7;
-    u = ((xcd < rr) ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (blockIdx.x >> 3);
-  }
+  int u = conv_xcd_unit();
   const int seg = u % d.nseg; u /= d.nseg;
   const int x0 = (u % d.ntx) * 16; u /= d.ntx;
   const int y0 = (u % d.nty) * 4;
@@ -74,13 +72,8 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
   const int t_lo = seg * d.seglen, t_hi = min(T, t_lo + d.seglen), nfr = t_hi - t_lo;
   const int dir = d.dir, ts = (dir > 0) ? t_lo : t_hi - 1;
 
-  // ---- lane -> position inside a 32-position tile (conv_kernels.h: 16-lane read groups take 16 consecutive halo rows)
-  int pr;
-  {
-    const bool ga = (r < 4) || (r >= 12 && r < 16) || (r >= 20 && r < 28);
-    const int k = ga ? ((r < 4) ? r : (r < 16) ? r - 8 : r - 12) : ((r < 12) ? r - 4 : (r < 20) ? r - 8 : r - 16);
-    pr = (ga ? 0 : 16) + k;
-  }
+  // ---- lane -> position inside a 32-position tile (2 pixel rows x 16)
+  const int pr = conv_lane_pos<16>(r);
   // fragment addresses of the two MFMA streams of this wave: own waves read the SAME tile from two buffers (slot 0 / 1),
   // context waves read BOTH tiles from one buffer
   int xaddrA[TAPS], xaddrB[TAPS];
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
   }
 
   // ---- DMA descriptors: 432 pieces of 16 B per halo image
-  constexpr int OOB = (int)0x80000000;
+  constexpr int OOB = CONV_STREAM_OOB;
   int hv[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -129,14 +122,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
 
   // ---- weights -> registers (once): lane (r = co row, h = 8-channel group of the k-step)
   bf16x8 wreg[NST];
-  {
-    const bf16* wsrc = ctxw ? (const bf16*)a.w_ctx + (size_t)(uw - 2) * TAPS * a.CoutP * a.CinP : (const bf16*)a.w_own;
-#pragma unroll
-    for (int i = 0; i < NST; ++i)
-      wreg[i] = *(const bf16x8*)(wsrc + ((size_t)(i / KS) * a.CoutP + r) * a.CinP + (i % KS) * 16 + h * 8);
-  }
-#pragma unroll
-  for (int i = 0; i < NST; ++i) asm volatile("" : "+v"(wreg[i]));    // consumed before any LDS-DMA is in flight
+  conv_stream_weights(wreg, ctxw ? (const bf16*)a.w_ctx + (size_t)(uw - 2) * TAPS * a.CoutP * a.CinP : (const bf16*)a.w_own, a, r, h);
 
   // ---- per-frame epilogue inputs.  NOTHING in the frame loop is an ordinary vector load: the vmcnt stream of a wave
   // holds its LDS-DMA copies and its epilogue stores only, and the wait at the top of a step is COUNTED -- it lets the stores
@@ -151,40 +137,15 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
   const bool emb = a.epi == ONIRIS_EPI_EMB_SILU, mps = a.epi == ONIRIS_EPI_MPSUM;
   const int epitch = a.escale_pitch ? a.escale_pitch : Cout;
   const i32x4 rs_e = make_rsrc(a.escale ? a.escale : (const void*)oniris_fill_rows, emb ? (int)(((size_t)a.B * 2 * T - 1) * epitch + Cout) * 4 : 0);
-  const i32x4 rs_r = make_rsrc(mps ? (const bf16*)a.res + (size_t)b * 2 * T * HWp * Cout : (const bf16*)oniris_fill_rows,
-                               mps ? 2 * T * HWp * Cout * 2 : 0);
   // piece (lane & 7) of slot (lane >> 3)'s row: the slot goes into the per-lane offset, the frame into the uniform one
   const int evoff = (lane < 16 && (lane & 7) * 4 < Cout) ? ((lane >> 3) * T * epitch) * 4 + (lane & 7) * 16 : OOB;
   auto issue_esc = [&](int f) __attribute__((always_inline)) {       // wave 0, lanes 0..15: [slot][32] floats of frame f
     if (lane < 16) dma16(rs_e, evoff, ((b * 2 * T + f) * epitch) * 4, lds0 + ESC + (f & 1) * 256);
   };
-  typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-  u32x2 resq[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) { resq[g][0] = 0u; resq[g][1] = 0u; }
-  int rvoff[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) rvoff[g] = (8 * g + 4 * h < Cout) ? (pix * Cout + 8 * g + 4 * h) * 2 : OOB;
-  auto load_res = [&](int f) __attribute__((always_inline)) {
-    const int so = __builtin_amdgcn_readfirstlane(((uslot * T + f) * HWp * Cout) * 2);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=v"(resq[g]) : "v"(rvoff[g]), "s"(rs_r), "s"(so) : "memory");
-  };
-  auto wait_vm = [&](int n) __attribute__((always_inline)) {         // s_waitcnt vmcnt(n), n wave-uniform, 0..9
-    switch (n) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-      case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    }
-  };
+  ConvStreamRes res;
+  res.init(mps ? (const bf16*)a.res + (size_t)b * 2 * T * HWp * Cout : (const bf16*)oniris_fill_rows, mps ? 2 * T * HWp * Cout * 2 : 0,
+           pix, Cout, h);
+  constexpr int VM_SAT = 9;                                          // where the counted waits saturate
   // instruction counts of this wave (wave-uniform): copies per frame, stores per epilogue
   const int per_halo = (uw < 3) ? 2 : 1;                             // the second piece of a halo image ends inside wave 2
   const int n_dma = (ALIAS ? 2 : 3) * per_halo + ((emb && uw == 0) ? 1 : 0);
@@ -206,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
   for (int i = 0; i < nfr; ++i) {
     const int t = ts + i * dir, tn = t + dir;
     SSTAMP(7)
-    wait_vm(i ? n_st : 0);                 // this wave's copies of frame t have landed (its last epilogue's stores may still drain)
+    conv_wait_vm<VM_SAT>(i ? n_st : 0);    // this wave's copies of frame t have landed (its last epilogue's stores may still drain)
     SSTAMP(0)
     __syncthreads();                       // ... everybody's have; and everybody is done with the previous step
     SSTAMP(1)
@@ -217,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
     typedef const __attribute__((address_space(4))) float cfloat_t;
     const float cown = a.coef_own ? ((cfloat_t*)(size_t)a.coef_own)[nfrm] : 1.f;
     const float cctx = a.coef_ctx ? ((cfloat_t*)(size_t)a.coef_ctx)[nfrm] : 1.f;
-    if (mps) load_res(t);                  // (in front of the copies: waited for by count, see the epilogue)
+    if (mps) res.load(((uslot * T + t) * HWp * Cout) * 2);     // (in front of the copies: waited for by count, conv_parts.h)
     if (has_next) {
       issue_x(tn);
       if (!ALIAS) issue_ctx(tn + a.coff1);
@@ -287,84 +248,29 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const ConvStreamDev
     if (!ALIAS) __syncthreads();           // dgrad: the staging tiles ARE the exchange arrays
     // ---- epilogue of slot `sl`, tile `pt` (lane = position; bf16 results transposed through the wave's LDS tile)
     const size_t blk = ((size_t)(b * 2 + sl) * T + t) * HWp;
-    auto put = [&](const float (&vv)[16]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = f2bf(vv[4 * g + k]);
-        *(bf16x4*)(ep + pr * EROW + (8 * g + 4 * h) * 2) = o;
-      }
-    };
-    auto flush_row = [&](bf16* dst, size_t fblk, int it) __attribute__((always_inline)) {      // pixel row `it` of the tile
-      const int id = it * 64 + lane, row = id >> 2, part = id & 3;
-      const size_t px_ = (size_t)(y0 + 2 * pt + (row >> 4)) * W + x0 + (row & 15);
-      if (part * 8 < Cout) {
-        const u32x4 v_ = *(const u32x4*)(ep + row * EROW + part * 16);
-        u32x4* o_ = (u32x4*)(dst + (fblk + px_) * Cout + part * 8);
-        if (d.nt) __builtin_nontemporal_store(v_, o_); else *o_ = v_;
-      }
-    };
-    auto flush = [&](bf16* dst, size_t fblk) __attribute__((always_inline)) {
-      flush_row(dst, fblk, 0);
-      flush_row(dst, fblk, 1);
-    };
+    ConvStreamOut out;
+    out.ep = ep; out.lane = lane; out.pr = pr; out.h = h;
+    out.y = y0 + 2 * pt; out.x = x0;
+    out.W = W; out.Cout = Cout; out.nontemporal = d.nt != 0;
     // the un-gated context product y3 (shared by both slots, kept for d(gate)): every wave has it for its tile -- the wave
     // that finishes slot 0 stores the tile's first pixel row, the one that finishes slot 1 the second (the stores are what
     // an epilogue waits for: three tensors on one pair of waves and two on the other cost 10 % of the launch)
     auto store_y3 = [&]() __attribute__((always_inline)) {
-      put(cx);
-      flush_row((bf16*)a.ctx_out, ((size_t)b * T + t) * HWp, sl);
+      out.put(cx);
+      out.flush_row((bf16*)a.ctx_out, ((size_t)b * T + t) * HWp, sl);
     };
     if (mps) {
-      // the residual loads of this step are older than its copies: n_dma younger instructions may still be in flight
-      wait_vm(has_next ? n_dma : 0);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(resq[g]));
-      float o[16];
-      bool clip_hit = false;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const bf16x4 rv = __builtin_bit_cast(bf16x4, resq[g]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float q = a.ta * bf2f(rv[k]) + a.tb * v[4 * g + k];
-          if (a.clip > 0.f) {
-            q = fminf(fmaxf(q, -a.clip), a.clip);
-            clip_hit |= !(fabsf(bf2f(f2bf(q))) < a.clip);         // (what the backward's mask tests: the STORED value)
-          }
-          o[4 * g + k] = q;
-        }
-      }
-      if (a.ctx_out) store_y3();
-      if (a.out2) { put(v); flush((bf16*)a.out2, blk); }
-      put(o);
-      flush((bf16*)a.out, blk);
-      if (a.clip_flag && __builtin_amdgcn_ballot_w64(clip_hit) != 0ull) {    // (practically never: OnirisConvArgs.clip_flag)
-        if (lane == 0) atomicOr(a.clip_flag, 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // one more op in the vmcnt stream than the counted waits know
-      }
+      conv_stream_mpsum<VM_SAT>(a, res, out, v, blk, has_next ? n_dma : 0, [&] { if (a.ctx_out) store_y3(); });
       SSTAMP(6)
       continue;
     }
     if (a.ctx_out) store_y3();
-    {
-      put(v);
-      flush((bf16*)a.out, blk);
-      if (a.epi == ONIRIS_EPI_EMB_SILU) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 ev = *(const float4*)(smem + ESC + (t & 1) * 256 + (sl * 32 + 8 * g + 4 * h) * 4);
-          const float cvv[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float z = bf2f(f2bf(v[4 * g + k])) * cvv[k];     // the activation sees the bf16-rounded y
-            v[4 * g + k] = z * sigmoid_fast(z) * (1.f / 0.596f);
-          }
-        }
-        put(v);
-        flush((bf16*)a.out2, blk);
-      }
+    out.put(v);
+    out.flush((bf16*)a.out, blk);
+    if (emb) {
+      conv_emb_silu16(v, smem + ESC + (t & 1) * 256, sl * 32, h);
+      out.put(v);
+      out.flush((bf16*)a.out2, blk);
     }
     SSTAMP(6)
   }
