@@ -205,6 +205,18 @@ _SIGS = {
                                       c_int, c_void_p]),
     "oniris_vae_lin_dw_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_int, c_void_p]),
+    "oniris_disc_conv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "oniris_disc_stats_finalize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                           c_void_p, c_void_p]),
+    "oniris_disc_blur": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "oniris_disc_blur_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "oniris_disc_bn_bwd_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "oniris_disc_part_sum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "oniris_disc_bn_bwd_dx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int,
+                                      c_void_p]),
+    "oniris_disc_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_void_p]),
 }
 EXPORTED = sorted(_SIGS)
 

@@ -729,6 +729,48 @@ int oniris_vae_lin_dx_bwd(const float* dy, int Cy, int tcy, int scy, const float
 int oniris_vae_lin_dw_bwd(const float* x, int Cx, int tcx, int scx, const float* dy, int Cy, int tcy, int scy, int B, int T, int H,
                           int W, float* slab, int nslab, oniris_stream_t stream);
 
+/* VAE discriminator, the per-frame half (reference: edm2/vae/discriminator.py Discriminator2D :70-111, DiscriminatorBlock2D :11-67,
+ * BlurPooling2D :154-178), added within ABI 14.  fp32 throughout, channels-last [N][H][W][C]; the caller allocates every buffer
+ * and nothing synchronises.  csrc/disc.hip, csrc/disc_conv3.h.  A channel count is 1..8 or a multiple of 32.
+ * The prologue (pro_s, pro_t, both or neither): the operand is a = lrelu_0.2(x pro_s[c] + pro_t[c]) -- BatchNorm with s = gamma rstd,
+ * t = beta - mean s, then LeakyReLU(0.2) -- formed while x is staged; zero padding applies to a, not to x.
+ * oniris_disc_conv: out[n][y][x][co] = bias[co] + sum_{tap, ci} w[tap][ci][co] a[n][y + ky - 1][x + kx - 1][ci], taps = 9 (tap =
+ *   3 ky + kx) or 1, on v_mfma_f32_32x32x2_f32; w packed [taps][CinP][CoutP], CinP = 8 for Cin <= 8 else Cin, CoutP = Cout rounded
+ *   up to a multiple of 32, zero in the padding; bias [Cout] or NULL.  res (or NULL): out = (out + res) res_scale.  part (or
+ *   NULL; Cout % 32 == 0): [N ceil(H / 16) ceil(W / 16)][4][Cout], per 16x16 tile of the stored values the count, a centre (the tile's
+ *   mean rounded to fp32), and the sums of (v - centre)^2 and of v - centre: the tile's (count, mean, M2) with the mean held
+ *   as centre + S1 / count, so that the fp32 rounding of a mean far from 0 stays out of the between-tile term.  The data gradient
+ *   is the same call on w'[8 - tap][co][ci].
+ * oniris_disc_stats_finalize: the partials [P][4][C] combined by Chan's formula in double in a fixed order -> stats [5][C] = mean | biased var |
+ *   s = gamma rstd | t = beta - mean s | rstd = 1 / sqrt(var + eps); running_mean / running_var (both or NULL) move by momentum
+ *   towards the mean and the unbiased variance, as nn.BatchNorm2d does in training mode.
+ * oniris_disc_blur: out [N][Ho][Wo][C], Ho = (H - 1) / 2 + 1: the [1,2,1] x [1,2,1] / 16 filter at stride 2, padding 1, of a.
+ *   oniris_disc_blur_bwd: its transpose, dy [N][Ho][Wo][C] -> dx [N][H][W][C], gathered per input position.
+ * oniris_disc_bn_bwd_reduce: dz = da lrelu'(z s + t), xhat = (z - mean) rstd; part [ceil(npix / 1024)][2][C] = per workgroup
+ *   sum dz | sum dz xhat.  oniris_disc_part_sum: out[e] = sum_p part[p][e] (n elements per partial) in a fixed tree order; of
+ *   those partials it is d beta | d gamma.
+ * oniris_disc_bn_bwd_dx: dx = s (dz - sums[c] / npix - xhat sums[C + c] / npix) + add_scale add (add or NULL); eval != 0: dx =
+ *   s dz + add_scale add (running statistics: no dependence through the batch), sums may be NULL.
+ * oniris_disc_wgrad: slab [nslab][taps Cin Cout + Cout]: [tap][ci][co] = sum_pos a[pos + tap][ci] dy[pos][co], then [co] =
+ *   sum_pos dy[pos][co]; workgroup s sums the work items (image, 16x16 tile) s, s + nslab, ... in that order into slab s and
+ *   writes all of it; oniris_vae_slab_sum_bwd sums the slabs.
+ * Every sum has a fixed order and nothing is accumulated with atomics: two runs give the same bits.                          */
+int oniris_disc_conv(const float* x, const float* w, const float* bias, const float* pro_s, const float* pro_t, const float* res,
+                     float res_scale, float* out, float* part, int N, int H, int W, int Cin, int Cout, int taps,
+                     oniris_stream_t stream);
+int oniris_disc_stats_finalize(const float* part, int P, int C, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float momentum, float eps, float* stats, oniris_stream_t stream);
+int oniris_disc_blur(const float* x, const float* pro_s, const float* pro_t, float* out, int N, int H, int W, int C,
+                     oniris_stream_t stream);
+int oniris_disc_blur_bwd(const float* dy, float* dx, int N, int H, int W, int C, oniris_stream_t stream);
+int oniris_disc_bn_bwd_reduce(const float* da, const float* z, const float* stats, float* part, int64_t npix, int C,
+                              oniris_stream_t stream);
+int oniris_disc_part_sum(const float* part, int P, int n, float* out, oniris_stream_t stream);
+int oniris_disc_bn_bwd_dx(const float* da, const float* z, const float* stats, const float* sums, const float* add, float add_scale,
+                          float* dx, int64_t npix, int C, int eval, oniris_stream_t stream);
+int oniris_disc_wgrad(const float* x, const float* pro_s, const float* pro_t, const float* dy, float* slab, int nslab, int N, int H,
+                      int W, int Cin, int Cout, int taps, oniris_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
