@@ -8,7 +8,10 @@ LeakyReLU never exist as tensors: a conv emits per-tile (count, centre, S2, S1) 
 per-channel scale s and shift t, and the consumer (the next conv, or the blur pool) applies lrelu(x s + t) while it stages its operand.
 What stays in torch: the NCHW <-> channels-last copies at the two ends and permutations at parameter size.
 
-`Discriminator3D` is plain torch.nn code in this version (see its docstring); `MixedDiscriminator` joins the two as the reference does.
+`Discriminator3D`, the spatio-temporal half, runs on HIP kernels as well when model and input are on the GPU (oniris_disc3d_*,
+csrc/disc3d.hip, csrc/disc_conv3d.h): the same structure on [N][T][H][W][C], a 27-tap conv being the sum over kt of 9-tap convs of
+neighbouring planes, GroupNorm(32) in place of BatchNorm with scale and shift per (sample, channel), a stride-2 stem and a 3-D blur
+pool; with CPU tensors it stays plain torch.nn code.  `MixedDiscriminator` joins the two as the reference does.
 
 Gradients are summed in a fixed order into a bounded number of partial slabs and then over the slabs; nothing uses atomics, two runs
 give the same bits."""
@@ -343,6 +346,253 @@ class Discriminator2D(nn.Module):
         return y.permute(0, 3, 1, 2)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the 3-D half: launches on channels-last fp32 tensors (N, T, H, W, C) of the GPU
+
+GROUPS = 32
+
+
+def _nslab3(work, size):
+    """Partial slabs for a 27-tap weight gradient: as _nslab, without its floor of 64 -- one launch stays within _SLAB_BYTES."""
+    return int(max(1, min(work, _MAX_SLABS, _SLAB_BYTES // (4 * size))))
+
+
+def _half(n):
+    return (n - 1) // 2 + 1
+
+
+def pack_weight3(w):
+    """nn.Conv3d weight (Cout, Cin, 3, 3, 3) -> the forward layout [27][CinP][CoutP] of oniris_disc3d_conv."""
+    Cout, Cin = w.shape[:2]
+    out = torch.zeros(27, _padc(Cin), -(-Cout // 32) * 32, dtype=torch.float32, device=w.device)
+    out[:, :Cin, :Cout] = w.detach().float().permute(2, 3, 4, 1, 0).reshape(27, Cin, Cout)
+    return out
+
+
+def pack_weight3_dgrad(w, scale=1.0):
+    """nn.Conv3d weight -> the layout of the stride-1 data gradient: the conv Cout -> Cin on w'[26 - tap][co][ci] (times `scale`)."""
+    Cout, Cin = w.shape[:2]
+    out = torch.zeros(27, _padc(Cout), -(-Cin // 32) * 32, dtype=torch.float32, device=w.device)
+    out[:, :Cout, :Cin] = w.detach().float().flip(2, 3, 4).permute(2, 3, 4, 0, 1).reshape(27, Cout, Cin) * scale
+    return out
+
+
+def conv3(x, wp, bias, Cout, stride=1, pro=None, res=None, res_scale=1.0, stats=False):
+    """oniris_disc3d_conv: x (N, T, H, W, Cin), wp packed -> (out (N, T', H', W', Cout), per-tile statistics (N, P, 4, Cout) or None)."""
+    N, T, H, W, Cin = x.shape
+    To, Ho, Wo = ((T - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    out = torch.empty(N, To, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    part = torch.empty(N, To * -(-Ho // 16) * -(-Wo // 16), 4, Cout, dtype=torch.float32, device=x.device) if stats else None
+    s, t = (None, None) if pro is None else pro
+    _lib.check(_lib.lib.oniris_disc3d_conv(_p(x), _p(wp), _p(bias), _p(s), _p(t), _p(res), res_scale, _p(out), _p(part), N, T, H, W,
+                                           Cin, Cout, stride, _stream()), "disc3d_conv")
+    return out, part
+
+
+def stem_dgrad3(dy, wp, T, H, W, Cin):
+    """oniris_disc3d_stem_dgrad: dy (N, T', H', W', Cout), wp = pack_weight3(conv_in.weight) -> dx (N, T, H, W, Cin)."""
+    N, Cout = dy.shape[0], dy.shape[-1]
+    dx = torch.empty(N, T, H, W, Cin, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib.oniris_disc3d_stem_dgrad(_p(dy), _p(wp), _p(dx), N, T, H, W, Cin, Cout, _stream()), "disc3d_stem_dgrad")
+    return dx
+
+
+def wgrad3(x, dy, stride=1, pro=None):
+    """oniris_disc3d_wgrad + the slab sum -> (d weight in nn.Conv3d's layout (Cout, Cin, 3, 3, 3), d bias (Cout,))."""
+    N, T, H, W, Cin = x.shape
+    _, To, Ho, Wo, Cout = dy.shape
+    n = 27 * Cin * Cout + Cout
+    nslab = _nslab3(N * To * -(-Ho // 16) * -(-Wo // 16), n)
+    slab = torch.empty(nslab, n, dtype=torch.float32, device=x.device)
+    s, t = (None, None) if pro is None else pro
+    _lib.check(_lib.lib.oniris_disc3d_wgrad(_p(x), _p(s), _p(t), _p(dy), _p(slab), nslab, N, T, H, W, Cin, Cout, stride, _stream()),
+               "disc3d_wgrad")
+    r = torch.empty(n, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.oniris_vae_slab_sum_bwd(_p(slab), nslab, n, _p(r), _stream()), "vae_slab_sum_bwd")
+    return r[:n - Cout].view(3, 3, 3, Cin, Cout).permute(4, 3, 0, 1, 2), r[n - Cout:]
+
+
+def gn_finalize(part, gamma, beta, eps=1e-5):
+    """oniris_disc3d_gn_finalize: partials (N, P, 4, C) -> stats (5, N, C): mean, biased var, s, t, rstd per (sample, channel)."""
+    N, P, _, C = part.shape
+    stats = torch.empty(5, N, C, dtype=torch.float32, device=part.device)
+    _lib.check(_lib.lib.oniris_disc3d_gn_finalize(_p(part), N, P, C, _p(gamma), _p(beta), eps, _p(stats), _stream()),
+               "disc3d_gn_finalize")
+    return stats
+
+
+def blur3(x, pro=None):
+    N, T, H, W, C = x.shape
+    out = torch.empty(N, _half(T), _half(H), _half(W), C, dtype=torch.float32, device=x.device)
+    s, t = (None, None) if pro is None else pro
+    _lib.check(_lib.lib.oniris_disc3d_blur(_p(x), _p(s), _p(t), _p(out), N, T, H, W, C, _stream()), "disc3d_blur")
+    return out
+
+
+def blur3_bwd(dy, T, H, W):
+    N, C = dy.shape[0], dy.shape[-1]
+    dx = torch.empty(N, T, H, W, C, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib.oniris_disc3d_blur_bwd(_p(dy), _p(dx), N, T, H, W, C, _stream()), "disc3d_blur_bwd")
+    return dx
+
+
+def gn_bwd(da, z, stats, gamma, add=None, add_scale=1.0, want_dx=True):
+    """GroupNorm + LeakyReLU backward at z (N, T, H, W, C): -> (dx or None, sums (2, C) = d beta | d gamma)."""
+    N, C = z.shape[0], z.shape[-1]
+    npix = z.numel() // (N * C)
+    P = -(-npix // 1024)
+    part = torch.empty(N, P, 2 * C, dtype=torch.float32, device=z.device)
+    _lib.check(_lib.lib.oniris_disc3d_gn_bwd_reduce(_p(da), _p(z), _p(stats), _p(part), N, npix, C, _stream()), "disc3d_gn_bwd_reduce")
+    nsum = torch.empty(N, 2 * C, dtype=torch.float32, device=z.device)
+    mm = torch.empty(2, N, GROUPS, dtype=torch.float32, device=z.device)
+    _lib.check(_lib.lib.oniris_disc3d_gn_bwd_finalize(_p(part), N, P, C, _p(gamma), npix, _p(nsum), _p(mm), _stream()),
+               "disc3d_gn_bwd_finalize")
+    sums = torch.empty(2, C, dtype=torch.float32, device=z.device)
+    _lib.check(_lib.lib.oniris_disc_part_sum(_p(nsum), N, 2 * C, _p(sums), _stream()), "disc_part_sum")
+    dx = None
+    if want_dx:
+        dx = torch.empty_like(z)
+        _lib.check(_lib.lib.oniris_disc3d_gn_bwd_dx(_p(da), _p(z), _p(stats), _p(gamma), _p(mm), _p(add), add_scale, _p(dx), N, npix, C,
+                                                    _stream()), "disc3d_gn_bwd_dx")
+    return dx, sums
+
+
+def _planes(x):
+    """(N, T, H, W, C) -> the N T planes (N T, H, W, C) the 2-D entry points take (the 1x1x1 shortcut convs)."""
+    return x.reshape(-1, *x.shape[2:])
+
+
+def _gn_check(x):
+    N, T, H, W, C = x.shape
+    if N * (C // GROUPS) * T * H * W == 1:
+        raise ValueError("Expected more than 1 value per channel when training (GroupNorm)")
+
+
+class Stem3D(torch.autograd.Function):
+    """conv_in: x (N, T, H, W, Cin) -> (the stride-2 conv + bias, the statistics partials of it)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        out, part = conv3(x, pack_weight3(weight), _f32(bias), weight.shape[0], stride=2, stats=True)
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(part)
+        return out, part
+
+    @staticmethod
+    def backward(ctx, dout, _dpart):
+        x, weight = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = wgrad3(x, dout, stride=2)
+        if ctx.needs_input_grad[0]:
+            dx = stem_dgrad3(dout, pack_weight3(weight), *x.shape[1:])
+        return dx, dw, db
+
+
+class Head3D(torch.autograd.Function):
+    """conv_out: x (N, T, H, W, C) -> the 27-tap conv + bias (N, T, H, W, 2), no normalisation in front (as in the reference)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        out, _ = conv3(x, pack_weight3(weight), _f32(bias), weight.shape[0])
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = wgrad3(x, dout)
+        if ctx.needs_input_grad[0]:
+            dx = conv3(dout, pack_weight3_dgrad(weight), None, weight.shape[1])[0]
+        return dx, dw, db
+
+
+class Block3D(torch.autograd.Function):
+    """A DiscriminatorBlock3D: x (N, T, H, W, Cin) and the statistics partials of x -> ((conv2(..) + shortcut(x)) / sqrt 2, partials).
+    The shortcut is blur + 1x1x1 conv in a downsampling block and a 1x1x1 conv in the final one."""
+
+    @staticmethod
+    def forward(ctx, x, part, g1, b1, w1, c1, g2, b2, w2, c2, ws, bs, down, stats_out, eps1, eps2):
+        x = x.contiguous()
+        N, T, H, W, Cin = x.shape
+        Cout = w1.shape[0]
+        _gn_check(x)
+        st1 = gn_finalize(part, _f32(g1), _f32(b1), eps1)
+        h1, part1 = conv3(x, pack_weight3(w1), _f32(c1), Cout, pro=(st1[2], st1[3]), stats=True)
+        _gn_check(h1)
+        st2 = gn_finalize(part1, _f32(g2), _f32(b2), eps2)
+        wsp = pack_weight(ws.reshape(Cout, Cin, 1, 1))
+        if down:
+            b0 = blur3(x)
+            sc = conv(_planes(b0), wsp, _f32(bs), Cout, 1)[0]
+            pooled = blur3(h1, pro=(st2[2], st2[3]))
+            out, part_o = conv3(pooled, pack_weight3(w2), _f32(c2), Cout, res=sc, res_scale=_SCALE, stats=stats_out)
+            ctx.save_for_backward(x, h1, st1, st2, g1, g2, w1, w2, ws, pooled, b0)
+        else:
+            sc = conv(_planes(x), wsp, _f32(bs), Cout, 1)[0]
+            out, part_o = conv3(h1, pack_weight3(w2), _f32(c2), Cout, pro=(st2[2], st2[3]), res=sc, res_scale=_SCALE,
+                                stats=stats_out)
+            ctx.save_for_backward(x, h1, st1, st2, g1, g2, w1, w2, ws)
+        ctx.down = down
+        ctx.mark_non_differentiable(*(() if part_o is None else (part_o,)))
+        return out, part_o
+
+    @staticmethod
+    def backward(ctx, dout, _dpart):
+        x, h1, st1, st2, g1, g2, w1, w2, ws = ctx.saved_tensors[:9]
+        need = ctx.needs_input_grad
+        dout = dout.contiguous()
+        N, T, H, W, Cin = x.shape
+        Cout = w1.shape[0]
+        dx = dg1 = db1 = dw1 = dc1 = dg2 = db2 = dw2 = dc2 = dws = dbs = None
+        # conv2 and what it read
+        if ctx.down:
+            pooled, b0 = ctx.saved_tensors[9:]
+            if need[8] or need[9]:
+                dw2, dc2 = (g * _SCALE for g in wgrad3(pooled, dout))
+            da2 = blur3_bwd(conv3(dout, pack_weight3_dgrad(w2, _SCALE), None, Cout)[0], T, H, W)
+        else:
+            if need[8] or need[9]:
+                dw2, dc2 = (g * _SCALE for g in wgrad3(h1, dout, pro=(st2[2], st2[3])))
+            da2 = conv3(dout, pack_weight3_dgrad(w2, _SCALE), None, Cout)[0]
+        # norm2 + LeakyReLU
+        dh1, sums2 = gn_bwd(da2, h1, st2, _f32(g2))
+        if need[6]:
+            dg2 = sums2[1].clone()
+        if need[7]:
+            db2 = sums2[0].clone()
+        # conv1: its bias sits in front of a GroupNorm; where a group is one channel, the norm subtracts that channel's mean
+        one = Cout == GROUPS
+        if need[4] or (need[5] and not one):
+            dw1, dc1 = wgrad3(x, dh1, pro=(st1[2], st1[3]))
+        if need[5] and one:
+            dc1 = torch.zeros(Cout, dtype=torch.float32, device=x.device)       # exactly zero, nothing computed
+        # norm1 + LeakyReLU, plus the shortcut's share of dx
+        if need[0] or need[2] or need[3]:
+            da1 = conv3(dh1, pack_weight3_dgrad(w1), None, Cin)[0]
+            add = None
+            if need[0]:
+                wsd = pack_weight_dgrad(ws.reshape(Cout, Cin, 1, 1), _SCALE)
+                add = conv(_planes(dout), wsd, None, Cin, 1)[0].view(*dout.shape[:4], Cin)
+                if ctx.down:
+                    add = blur3_bwd(add, T, H, W)
+            dx, sums1 = gn_bwd(da1, x, st1, _f32(g1), add, 1.0, want_dx=need[0])
+            if need[2]:
+                dg1 = sums1[1].clone()
+            if need[3]:
+                db1 = sums1[0].clone()
+        if need[10] or need[11]:
+            dws, dbs = wgrad(_planes(b0 if ctx.down else x), _planes(dout), 1)
+            dws, dbs = (dws * _SCALE).reshape(ws.shape), dbs * _SCALE
+        return dx, None, dg1, db1, dw1, dc1, dg2, db2, dw2, dc2, dws, dbs, None, None, None, None
+
+
 class DiscriminatorBlock3D(nn.Module):
     def __init__(self, in_channels, out_channels, add_downsample=True):
         super().__init__()
@@ -364,9 +614,22 @@ class DiscriminatorBlock3D(nn.Module):
 
 
 class Discriminator3D(nn.Module):
-    """The reference's Discriminator3D (discriminator.py:242-283) as plain torch.nn code: it runs on torch ops, on any device, and
-    is NOT on HIP kernels in this version -- by FLOPs it is the smaller half (about 20 k MAC per input pixel against 65 k for
-    the 2-D half).  Porting it (GroupNorm instead of BatchNorm, 27-tap convs) is the open follow-up."""
+    """The reference's Discriminator3D (discriminator.py:242-283).  With model and input on the GPU it runs on HIP kernels, forward
+    and backward (include/oniris.h: oniris_disc3d_*, csrc/disc3d.hip, csrc/disc_conv3d.h); with CPU tensors it is plain torch.nn
+    code in the tensors' dtype.
+
+    Native domain: in_channels 1..8; every width a multiple of 32 up to 256, any sequence of them (the final block's shortcut is a
+    1x1x1 conv); any T, H, W >= 1; input (N, C, T, H, W), computed in fp32 -> logits (N, 2, T', H', W'), every extent halved
+    len(widths) times by (n - 1) // 2 + 1 (conv_in has stride 2).  Anything else on the GPU raises NotImplementedError.  A
+    GroupNorm over a single value raises the ValueError torch raises.  GroupNorm(32) and LeakyReLU never exist as tensors: a conv
+    emits per-tile statistics of what it stores, a finalize launch turns them into per-(sample, channel) scale and shift, and the
+    consumer applies lrelu(x s + t) while it stages its operand.  `conv_norm_out` exists and is unused, as in the reference: its
+    gradients stay None.
+
+    Gradients: of the input and of every used parameter; what nobody asked for (requires_grad, needs_input_grad) is not computed.
+    Where `blocks.i.conv1` has 32 output channels, every group of the GroupNorm behind it is one channel and the norm subtracts
+    that channel's mean: the bias gradient is exactly zero and zeros are returned without computing anything.  At wider groups it
+    is not zero and is computed."""
 
     def __init__(self, in_channels=3, block_out_channels=(64,)):
         super().__init__()
@@ -379,19 +642,47 @@ class Discriminator3D(nn.Module):
             cin = c
         self.conv_norm_out = nn.GroupNorm(32, widths[-1])
         self.conv_out = nn.Conv3d(widths[-1], 2, kernel_size=3, padding=1)
+        self.widths = widths
 
-    def forward(self, x):
+    def _native_domain(self):
+        cin = self.conv_in.in_channels
+        if not 1 <= cin <= 8:
+            raise NotImplementedError(f"Discriminator3D: in_channels {cin}: the HIP kernels take 1..8")
+        if any(c % 32 or not 32 <= c <= MAX_WIDTH for c in self.widths):
+            raise NotImplementedError(f"Discriminator3D: widths {self.widths}: the HIP kernels take multiples of 32 up to {MAX_WIDTH}")
+
+    def forward_torch(self, x):
+        """The reference's forward as plain torch.nn code, in the tensors' dtype, on any device."""
         x = self.conv_in(x)
         for blk in self.blocks:
             x = blk(x)
         return self.conv_out(x)
 
+    def forward(self, x):
+        if not x.is_cuda and not self.conv_in.weight.is_cuda:
+            return self.forward_torch(x)
+        if not (x.is_cuda and self.conv_in.weight.is_cuda):
+            raise NotImplementedError("Discriminator3D: model and input must be on the same device (both on the GPU for the HIP "
+                                      "kernels, both on the CPU for the torch code)")
+        self._native_domain()
+        if x.dim() != 5 or x.shape[1] != self.conv_in.in_channels:
+            raise ValueError(f"Discriminator3D: input {tuple(x.shape)}, expected (N, {self.conv_in.in_channels}, T, H, W)")
+        y = x.float().permute(0, 2, 3, 4, 1)
+        y, part = Stem3D.apply(y, self.conv_in.weight, self.conv_in.bias)
+        for i, blk in enumerate(self.blocks):
+            down = i < len(self.blocks) - 1
+            sc = blk.shortcut[1] if down else blk.shortcut[0]
+            y, part = Block3D.apply(y, part, blk.norm1.weight, blk.norm1.bias, blk.conv1.weight, blk.conv1.bias, blk.norm2.weight,
+                                    blk.norm2.bias, blk.conv2.weight, blk.conv2.bias, sc.weight, sc.bias, down, down, blk.norm1.eps,
+                                    blk.norm2.eps)
+        y = Head3D.apply(y, self.conv_out.weight, self.conv_out.bias)
+        return y.permute(0, 4, 1, 2, 3)
+
 
 class MixedDiscriminator(nn.Module):
     """The reference's MixedDiscriminator (discriminator.py:286-329): a per-frame critic and a spatio-temporal one over the same clip,
-    their logits concatenated along time.  `discriminator2d` is the native `Discriminator2D`; `discriminator3d` stays on torch ops in
-    this version (`Discriminator3D`), the open follow-up.  As in the reference, `block_out_channels` is accepted and the halves are
-    built with widths (64, 64, 64) and (64, 64)."""
+    their logits concatenated along time.  On the GPU both halves run on HIP kernels (`Discriminator2D`, `Discriminator3D`).  As in
+    the reference, `block_out_channels` is accepted and the halves are built with widths (64, 64, 64) and (64, 64)."""
 
     def __init__(self, in_channels=6, block_out_channels=(64, 32)):
         super().__init__()

@@ -771,6 +771,52 @@ int oniris_disc_bn_bwd_dx(const float* da, const float* z, const float* stats, c
 int oniris_disc_wgrad(const float* x, const float* pro_s, const float* pro_t, const float* dy, float* slab, int nslab, int N, int H,
                       int W, int Cin, int Cout, int taps, oniris_stream_t stream);
 
+/* VAE discriminator, the spatio-temporal half (reference: edm2/vae/discriminator.py Discriminator3D :242-283, DiscriminatorBlock3D
+ * :181-239, BlurPooling3D), added within ABI 14.  fp32 throughout, channels-last [N][T][H][W][C]; the caller allocates every buffer
+ * and nothing synchronises.  csrc/disc3d.hip, csrc/disc_conv3d.h.  A channel count is 1..8 or a multiple of 32; a strided extent is
+ * no = (n - 1) / stride + 1.  The 1x1x1 shortcut convs are oniris_disc_conv / oniris_disc_wgrad over the N T planes.
+ * The prologue (pro_s, pro_t [N][Cin], both or neither): the operand is a = lrelu_0.2(x pro_s[n][c] + pro_t[n][c]) -- GroupNorm(32)
+ * with s[n][c] = gamma[c] rstd[n][g], t[n][c] = beta[c] - mean[n][g] s[n][c], then LeakyReLU(0.2) -- formed while x is staged; zero
+ * padding applies to a, not to x.
+ * oniris_disc3d_conv: out[n][t][y][x][co] = bias[co] + sum_{tap, ci} w[tap][ci][co] a[n][t S + kt - 1][y S + ky - 1][x S + kx - 1][ci],
+ *   tap = 9 kt + 3 ky + kx, S = stride 1 or 2, on v_mfma_f32_32x32x2_f32 as the sum over kt of 9-tap convs (planes outside 0..T-1
+ *   are skipped); w packed [27][CinP][CoutP] as for oniris_disc_conv; bias, res / res_scale as there.  Stride 2 (the stem): Cin
+ *   1..8, Cout % 32 == 0, no prologue, no residual.  part (or NULL; Cout % 32 == 0): [N To ceil(Ho / 16) ceil(Wo / 16)][4][Cout],
+ *   per 16x16 tile of one output plane (count, centre, S2, S1) as oniris_disc_conv emits them; a tile never spans two samples.
+ *   The data gradient at stride 1 is the same call on w'[26 - tap][co][ci].
+ * oniris_disc3d_stem_dgrad: the data gradient at stride 2, dy [N][To][Ho][Wo][Cout] -> dx [N][T][H][W][Cin], Cin 1..8, w in the
+ *   FORWARD layout [27][8][Cout]: one thread per input element sums its (output position, tap) pairs, taps ascending, in plain FMAs.
+ * oniris_disc3d_wgrad: slab [nslab][27 Cin Cout + Cout]: [tap][ci][co] = sum_pos a[pos S + tap][ci] dy[pos][co], then [co] =
+ *   sum_pos dy[pos][co]; workgroup s sums the work items (sample, output plane, 16x16 tile) s, s + nslab, ... in that order into
+ *   slab s and writes all of it; oniris_vae_slab_sum_bwd sums the slabs.
+ * oniris_disc3d_gn_finalize: the partials [N][P][4][C] of a conv (P per sample) combined per (sample, group of C / 32 channels) by
+ *   Chan's formula in double in a fixed order -> stats [5][N][C] = mean | biased var | s | t | rstd = 1 / sqrt(var + eps).
+ * oniris_disc3d_gn_bwd_reduce: dz = da lrelu'(z s + t), xhat = (z - mean) rstd, z [N][npix][C]; part [N][ceil(npix / 1024)][2][C]
+ *   = per workgroup sum dz | sum dz xhat.  oniris_disc3d_gn_bwd_finalize: sums [N][2][C] = the per-sample channel sums of those (their
+ *   sum over n, by oniris_disc_part_sum, is d beta | d gamma) and mm [2][N][32] = the group means of gamma dz | gamma dz xhat.
+ * oniris_disc3d_gn_bwd_dx: dx = rstd (gamma dz - mm[0][n][g] - xhat mm[1][n][g]) + add_scale add (add or NULL).
+ * oniris_disc3d_blur: out [N][To][Ho][Wo][C]: the [1,2,1]^3 / 64 filter at stride 2, padding 1, of a (prologue [N][C] or NULL).
+ *   oniris_disc3d_blur_bwd: its transpose, gathered per input position.
+ * Every sum has a fixed order and nothing is accumulated with atomics: two runs give the same bits.                          */
+int oniris_disc3d_conv(const float* x, const float* w, const float* bias, const float* pro_s, const float* pro_t, const float* res,
+                       float res_scale, float* out, float* part, int N, int T, int H, int W, int Cin, int Cout, int stride,
+                       oniris_stream_t stream);
+int oniris_disc3d_wgrad(const float* x, const float* pro_s, const float* pro_t, const float* dy, float* slab, int nslab, int N, int T,
+                        int H, int W, int Cin, int Cout, int stride, oniris_stream_t stream);
+int oniris_disc3d_stem_dgrad(const float* dy, const float* w, float* dx, int N, int T, int H, int W, int Cin, int Cout,
+                             oniris_stream_t stream);
+int oniris_disc3d_gn_finalize(const float* part, int N, int P, int C, const float* gamma, const float* beta, float eps, float* stats,
+                              oniris_stream_t stream);
+int oniris_disc3d_gn_bwd_reduce(const float* da, const float* z, const float* stats, float* part, int N, int64_t npix, int C,
+                                oniris_stream_t stream);
+int oniris_disc3d_gn_bwd_finalize(const float* part, int N, int P, int C, const float* gamma, int64_t npix, float* sums, float* mm,
+                                  oniris_stream_t stream);
+int oniris_disc3d_gn_bwd_dx(const float* da, const float* z, const float* stats, const float* gamma, const float* mm,
+                            const float* add, float add_scale, float* dx, int N, int64_t npix, int C, oniris_stream_t stream);
+int oniris_disc3d_blur(const float* x, const float* pro_s, const float* pro_t, float* out, int N, int T, int H, int W, int C,
+                       oniris_stream_t stream);
+int oniris_disc3d_blur_bwd(const float* dy, float* dx, int N, int T, int H, int W, int C, oniris_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
