@@ -229,6 +229,15 @@ _SIGS = {
                                         c_int64, c_int, c_void_p]),
     "oniris_disc3d_blur": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "oniris_disc3d_blur_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "oniris_vae_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, C.POINTER(c_int),
+                                    c_void_p]),
+    "oniris_vae_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "oniris_vae_loss_topk_keys": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "oniris_vae_loss_topk_count": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, C.POINTER(c_int), c_void_p]),
+    "oniris_vae_loss_topk_select": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "oniris_vae_loss_topk_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                         c_void_p, c_int, c_void_p]),
 }
 EXPORTED = sorted(_SIGS)
 

@@ -26,7 +26,7 @@ typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
 int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
-                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided.  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
+                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
 /* Measurement aid: arm a pair of HIP events (hipEvent_t created with timing); the next MFMA conv / weight-gradient /
@@ -816,6 +816,52 @@ int oniris_disc3d_gn_bwd_dx(const float* da, const float* z, const float* stats,
 int oniris_disc3d_blur(const float* x, const float* pro_s, const float* pro_t, float* out, int N, int T, int H, int W, int C,
                        oniris_stream_t stream);
 int oniris_disc3d_blur_bwd(const float* dy, float* dx, int N, int T, int H, int W, int C, oniris_stream_t stream);
+
+/* VAE training losses (reference: edm2/utils.py GaussianLoss :209-210, F.l1_loss, F.mse_loss, edm2/vae/utils.py worst_k_percent_loss
+ * :54-68), added within ABI 14.  fp32 throughout; the caller allocates every buffer and nothing synchronises.  csrc/vae_loss.hip.
+ * Layout (every entry point that takes nd / size / stride): the launch loops over nd <= 5 dimensions, outermost first, of size[k]
+ *   elements (host arrays); stride [tensors][nd] (host) holds the ELEMENT strides of every tensor operand in that loop order, inputs
+ *   first, then outputs, in the order of the signature (a NULL operand keeps its row, which is then ignored); the caller picks the
+ *   loop order (any permutation of the logical dimensions: the losses are sums over all elements) and may merge dimensions.  A strided
+ *   dimension has at most 2^31 - 4097 elements; counts and offsets are 64-bit.  stride == NULL: every operand is a flat 16-byte-aligned
+ *   array of the product of the sizes, read and written 16 bytes per lane.  max_blocks caps the workgroups (each loops over tiles of
+ *   1024 elements with the grid stride).
+ * oniris_vae_loss_fwd: `which` = 1 Gaussian | 2 L1 | 4 MSE.  part [blocks][3], blocks <= max_blocks returned through *blocks (host):
+ *   per workgroup (sum of ((logvar + d^2 expf(-logvar)) / 2 + 0.918) | sum |d| | sum d^2) / n with d = mean - target, a sum that is
+ *   switched off is written as 0 and logvar may then be NULL; the sum over the workgroups in fixed order is oniris_disc_part_sum
+ *   with n = 3.  A lane adds at most 64 terms in a row, the chunks meet pairwise, lanes and waves in a fixed tree.
+ * oniris_vae_loss_bwd: cot_* = the upstream cotangents of the three means (device scalars; NULL = that loss takes no part).  Writes,
+ *   where the pointer is not NULL, dmean = (cot_gauss d expf(-logvar) + cot_l1 sign(d) + 2 cot_mse d) / n with sign(0) = 0,
+ *   dlogvar = cot_gauss (1 - d^2 expf(-logvar)) / (2 n), dtarget = -dmean.  Stride rows: mean, logvar, target, dmean, dlogvar, dtarget.
+ * Worst-k%: the mean of the k largest e = (recon - target)^2 (difference and product rounded separately) by a radix select over the
+ *   keys = bit pattern of e with the sign bit cleared (NaN sorts above +inf), digits of 11 | 10 | 10 bits, n < 2^32.
+ *   Work space, zeroed by the caller before the first call: hist [2048 + 1024 + 1024] and state [3] (unsigned): the key prefix fixed
+ *   so far | the elements above it | the elements that match it.
+ *   oniris_vae_loss_topk_keys: writes e [n] (flat, in loop order) and adds the histogram of key >> 20 into hist [2048].
+ *   oniris_vae_loss_topk_select (one workgroup; digit 0, 1, 2 on hist + 0, + 2048, + 3072): scans the histogram from the top bin and
+ *     fixes the digit.  After digit 2 state = (threshold key, count_gt, count_eq) and loss [1] = (sum of e over key > threshold +
+ *     (k - count_gt) e_k) / k in double, where the sum is part [P] of the last count pass plus count x value over the bins above.
+ *   oniris_vae_loss_topk_count: the histogram of the next 10 bits over the elements that match state's prefix (last = 0: bits 19..10
+ *     given the top 11; last = 1: bits 9..0 given the top 21, and part [blocks] = per workgroup the sum of e over the elements ABOVE
+ *     the 21-bit prefix).
+ *   oniris_vae_loss_topk_bwd: drecon = g (2 / k) w d, dtarget = -drecon (where not NULL), d = recon - target, w = 1 for key >
+ *     threshold, (k - count_gt) / count_eq for key == threshold (every tied element gets the same share), 0 below; g = the upstream
+ *     cotangent (device scalar).  Stride rows: recon, target, drecon, dtarget.
+ * Counts are summed with integer atomics (exact in any order); no float sum uses an atomic: two runs give the same bits.          */
+int oniris_vae_loss_fwd(const float* mean, const float* logvar, const float* target, int which, int nd, const long long* size,
+                        const long long* stride, float* part, int max_blocks, int* blocks, oniris_stream_t stream);
+int oniris_vae_loss_bwd(const float* mean, const float* logvar, const float* target, int which, int nd, const long long* size,
+                        const long long* stride, const float* cot_gauss, const float* cot_l1, const float* cot_mse, float* dmean,
+                        float* dlogvar, float* dtarget, int max_blocks, oniris_stream_t stream);
+int oniris_vae_loss_topk_keys(const float* recon, const float* target, int nd, const long long* size, const long long* stride,
+                              float* e, unsigned* hist, int max_blocks, oniris_stream_t stream);
+int oniris_vae_loss_topk_count(const float* e, long long n, int last, const unsigned* state, unsigned* hist, float* part,
+                               int max_blocks, int* blocks, oniris_stream_t stream);
+int oniris_vae_loss_topk_select(const unsigned* hist, int digit, long long k, unsigned* state, const float* part, int P, float* loss,
+                                oniris_stream_t stream);
+int oniris_vae_loss_topk_bwd(const float* recon, const float* target, int nd, const long long* size, const long long* stride,
+                             const unsigned* state, const float* g, long long k, float* drecon, float* dtarget, int max_blocks,
+                             oniris_stream_t stream);
 
 #ifdef __cplusplus
 }
