@@ -26,7 +26,7 @@ typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
 int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
-                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
+                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
 /* Measurement aid: arm a pair of HIP events (hipEvent_t created with timing); the next MFMA conv / weight-gradient /
@@ -862,6 +862,44 @@ int oniris_vae_loss_topk_select(const unsigned* hist, int digit, long long k, un
 int oniris_vae_loss_topk_bwd(const float* recon, const float* target, int nd, const long long* size, const long long* stride,
                              const unsigned* state, const float* g, long long k, float* drecon, float* dtarget, int max_blocks,
                              oniris_stream_t stream);
+
+/* ---- LPIPS, net = 'alex' (added within ABI 14; csrc/lpips.hip, csrc/lpips_conv.h; autoregressive_diffusion_amd/lpips.py) -------------
+ * The perceptual loss of the VAE's training loop, forward and backward, fp32.  Activations are channels-last [image][y][x][C]; the two
+ * operands go through the trunk as one batch of 2 N images, operand 0 first.  No atomics, no host synchronisation; an image's results
+ * do not depend on the images around it.
+ * stem: in0 / in1 (N, 3, H, W) addressed by ELEMENT strides stride0 / stride1 [4] = (n, c, h, w) (host arrays); normalize != 0 maps x to
+ *   2 x - 1 first; f1 [2 N][H1][W1][64] = relu(conv11x11 stride 4 pad 2 ((x - shift[c]) / scale[c]) + bias), H1 = (H - 7) / 4 + 1;
+ *   wp = the weight as [ky][c][kx][64].
+ * stem_dgrad: g1 [NI][H1][W1][64] (the gradient at the stem's conv output, ReLU mask applied) -> dx (NI, 3, H, W) by element strides
+ *   dstride [4], divided by scale[c] (times 2 with normalize); wd = the weight as [ky][kx][c][64].
+ * conv: stride 1, zero padding ksize / 2, ksize 3 or 5, Cin % 32 == 0, Cout % 64 == 0; wp [ksize^2][Cin][Cout].
+ *   mode 0: out = relu(conv + bias[co]).  mode 1 (the data gradient: wp holds the flipped, transposed weight): out = (conv + add) *
+ *   (f > 0), add and f [NI][H][W][Cout], each may be NULL.  tile = the pixels per workgroup: 256, 64, or 0 = 64 where 256-pixel tiles
+ *   would make fewer than 256 workgroups, else 256; the results have the same bits for either.
+ * pool: max-pool 3 x 3 stride 2, floor mode: [NI][H][W][C] -> [NI][(H - 3) / 2 + 1][(W - 3) / 2 + 1][C], C % 4 == 0.
+ * pool_bwd: out [NI][H][W][C] = (sum over the windows whose FIRST maximum (row-major) is this position of dp (+ add)) (* (f > 0) with
+ *   mask != 0); f = the pool's input.
+ * head_fwd: fa, fb [N][HW][C] (C % 64 == 0, <= 384), w [C] -> part [N][ceil(HW / 64)]: the sum over 64 pixels of sum_c w[c] (ua - ub)^2,
+ *   u = f / (sqrt(sum_c f^2) + 1e-10), u = 0 where every channel is 0.
+ * head_sum: out [N] = sum over the layers k of (sum over the chunks of part [off[k] + n P_k + i]) / HW[k], P_k = ceil(HW[k] / 64); off
+ *   and HW are host arrays of `layers` <= 8 entries.
+ * head_bwd: cot [N] (device) -> ga, gb [N][HW][C] (either may be NULL) = d (cot[n] mean_pixels (...)) / d fa, d fb; a pixel whose
+ *   channels are all 0 takes no gradient; mask != 0 multiplies by (f > 0).                                                             */
+int oniris_lpips_stem(const float* in0, const float* in1, const long long* stride0, const long long* stride1, int N, int H, int W,
+                      int normalize, const float* shift, const float* scale, const float* wp, const float* bias, float* f1,
+                      oniris_stream_t stream);
+int oniris_lpips_stem_dgrad(const float* g1, const float* wd, const float* scale, int NI, int H, int W, int normalize, float* dx,
+                            const long long* dstride, oniris_stream_t stream);
+int oniris_lpips_conv(const float* x, const float* wp, const float* bias, const float* add, const float* f, float* out, long long NI,
+                      int H, int W, int Cin, int Cout, int ksize, int mode, int tile, oniris_stream_t stream);
+int oniris_lpips_pool(const float* x, float* out, int NI, int H, int W, int C, oniris_stream_t stream);
+int oniris_lpips_pool_bwd(const float* dp, const float* f, const float* add, int mask, float* out, int NI, int H, int W, int C,
+                          oniris_stream_t stream);
+int oniris_lpips_head_fwd(const float* fa, const float* fb, const float* w, float* part, int N, int HW, int C, oniris_stream_t stream);
+int oniris_lpips_head_sum(const float* part, int layers, const long long* off, const int* HW, int N, float* out,
+                          oniris_stream_t stream);
+int oniris_lpips_head_bwd(const float* fa, const float* fb, const float* w, const float* cot, float* ga, float* gb, int mask, int N,
+                          int HW, int C, oniris_stream_t stream);
 
 #ifdef __cplusplus
 }
