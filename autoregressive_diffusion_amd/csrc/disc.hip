@@ -1,11 +1,11 @@
 // VAE discriminator, the per-frame half (reference: edm2/vae/discriminator.py Discriminator2D :70-111, DiscriminatorBlock2D
 // :11-67, BlurPooling2D :154-178), fp32 throughout, channels-last activations [N][H][W][C].  include/oniris.h: oniris_disc_*.
 //   oniris_disc_conv            3x3 / 1x1 conv on the f32 MFMA with the BatchNorm + LeakyReLU prologue, bias / residual epilogue and
-//                               per-workgroup (count, centre, S2, S1) of what it stores (csrc/disc_conv3.h); the data gradient is the
-//                               same launch on flipped, transposed weights
+//                               per-workgroup (count, centre, S2, S1) of what it stores (csrc/disc_conv3.h over csrc/disc_parts.h);
+//                               the data gradient is the same launch on flipped, transposed weights
 //   oniris_disc_stats_finalize  partials -> mean, biased var, s = gamma rstd, t = beta - mean s, rstd; running buffers
 //   oniris_disc_blur / _bwd     [1,2,1] x [1,2,1] / 16, stride 2, pad 1, with the same prologue; its transpose in gather form
-//   oniris_disc_bn_bwd_reduce   per-workgroup sums of dz and dz xhat, dz = da lrelu'(z s + t)
+//   oniris_disc_bn_bwd_reduce   per-workgroup sums of dz and dz xhat, dz = da lrelu'(z s + t): the GroupNorm reduce at one sample
 //   oniris_disc_part_sum        the sum of such partials, in a fixed tree order
 //   oniris_disc_bn_bwd_dx       dx = s (dz - mean(dz) - xhat mean(dz xhat)) (+ add_scale add)
 //   oniris_disc_wgrad           weight and bias gradient into a bounded number of slabs (summed by oniris_vae_slab_sum_bwd)
@@ -14,24 +14,21 @@
 #include "common.h"
 #include "disc_conv3.h"
 
-template <typename K>
-static int disc_raise_lds(K kern, size_t bytes, const char* what) {
-  if (bytes <= 64 * 1024) return ONIRIS_OK;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) {
-    oniris_set_error("%s: raising the LDS limit failed: %s", what, hipGetErrorString(e));
-    return ONIRIS_ELAUNCH;
-  }
+template <int NB>
+static int disc_conv_launch(const DiscConvParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)p.taps * DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(disc_conv_kernel<NB>, bytes, "disc_conv")) return rc;
+  ONIRIS_KLAUNCH(disc_conv_kernel<NB>, grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }
-
-static bool disc_cin_ok(int c) { return (c >= 1 && c <= 8) || (c > 0 && c % 32 == 0); }
 
 extern "C" int oniris_disc_conv(const float* x, const float* w, const float* bias, const float* pro_s, const float* pro_t,
                                 const float* res, float res_scale, float* out, float* part, int N, int H, int W, int Cin, int Cout,
                                 int taps, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && w && out && N > 0 && H > 0 && W > 0 && (taps == 1 || taps == 9), "disc_conv: bad arguments");
-  ONIRIS_CHECK_ARG(disc_cin_ok(Cin) && disc_cin_ok(Cout), "disc_conv: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
+  ONIRIS_CHECK_ARG(disc_c_ok(Cin) && disc_c_ok(Cout), "disc_conv: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
   ONIRIS_CHECK_ARG(!pro_s == !pro_t, "disc_conv: the prologue needs both s and t");
   ONIRIS_CHECK_ARG(!part || Cout % 32 == 0, "disc_conv: statistics need Cout %% 32 == 0");
   DiscConvParams p;
@@ -41,15 +38,15 @@ extern "C" int oniris_disc_conv(const float* x, const float* w, const float* bia
   const long long wgs = (long long)N * p.tiles_x * p.tiles_y;
   ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL, "disc_conv: %lld tiles", wgs);
   const int nb = p.CoutP % 64 == 0 ? 2 : 1;
-  const int wp = nb == 2 ? 96 : 32;
-  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)taps * DISC_KC * wp) * sizeof(float);
   const dim3 grid((unsigned)wgs, p.CoutP / (32 * nb));
-  if (nb == 2) {
-    if (int rc = disc_raise_lds(disc_conv_kernel<2>, bytes, "disc_conv")) return rc;
-    ONIRIS_KLAUNCH(disc_conv_kernel<2>, grid, dim3(256), bytes, (hipStream_t)stream, p);
-  } else {
-    ONIRIS_KLAUNCH(disc_conv_kernel<1>, grid, dim3(256), bytes, (hipStream_t)stream, p);
-  }
+  return nb == 2 ? disc_conv_launch<2>(p, grid, (hipStream_t)stream) : disc_conv_launch<1>(p, grid, (hipStream_t)stream);
+}
+
+template <int TAPS>
+static int disc_wgrad_launch(const DiscWgradParams& p, dim3 grid, hipStream_t stream) {
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_WPITCH + 256 * 32) * sizeof(float);
+  if (int rc = disc_raise_lds(disc_wgrad_kernel<TAPS>, bytes, "disc_wgrad")) return rc;
+  ONIRIS_KLAUNCH(disc_wgrad_kernel<TAPS>, grid, dim3(256), bytes, stream, p);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }
@@ -57,7 +54,7 @@ extern "C" int oniris_disc_conv(const float* x, const float* w, const float* bia
 extern "C" int oniris_disc_wgrad(const float* x, const float* pro_s, const float* pro_t, const float* dy, float* slab, int nslab,
                                  int N, int H, int W, int Cin, int Cout, int taps, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && dy && slab && nslab > 0 && N > 0 && H > 0 && W > 0 && (taps == 1 || taps == 9), "disc_wgrad: bad arguments");
-  ONIRIS_CHECK_ARG(disc_cin_ok(Cin) && disc_cin_ok(Cout), "disc_wgrad: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
+  ONIRIS_CHECK_ARG(disc_c_ok(Cin) && disc_c_ok(Cout), "disc_wgrad: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
   ONIRIS_CHECK_ARG(!pro_s == !pro_t, "disc_wgrad: the prologue needs both s and t");
   DiscWgradParams p;
   p.x = x; p.pro_s = pro_s; p.pro_t = pro_t; p.dy = dy; p.slab = slab;
@@ -67,29 +64,11 @@ extern "C" int oniris_disc_wgrad(const float* x, const float* pro_s, const float
   ONIRIS_CHECK_ARG(items <= 0x7fffffffLL, "disc_wgrad: %lld work items", items);
   p.nitems = (int)items; p.nslab = nslab;
   p.slab_size = (long long)taps * Cin * Cout + Cout;
-  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_WPITCH + 256 * 32) * sizeof(float);
   const dim3 grid(nslab, cdiv(p.CinP, DISC_WKC), cdiv(Cout, 32));
-  if (taps == 9) {
-    if (int rc = disc_raise_lds(disc_wgrad_kernel<9>, bytes, "disc_wgrad")) return rc;
-    ONIRIS_KLAUNCH(disc_wgrad_kernel<9>, grid, dim3(256), bytes, (hipStream_t)stream, p);
-  } else {
-    if (int rc = disc_raise_lds(disc_wgrad_kernel<1>, bytes, "disc_wgrad")) return rc;
-    ONIRIS_KLAUNCH(disc_wgrad_kernel<1>, grid, dim3(256), bytes, (hipStream_t)stream, p);
-  }
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
+  return taps == 9 ? disc_wgrad_launch<9>(p, grid, (hipStream_t)stream) : disc_wgrad_launch<1>(p, grid, (hipStream_t)stream);
 }
 
-// ---- statistics: Chan's combination of (count, mean, M2) in double (the partials are fp32; a handful of values per channel), thread t
-// takes partials t, t + 256, ... in order, then a fixed tree
-__device__ __forceinline__ void disc_chan(double& n, double& m, double& q, double nb, double mb, double qb) {
-  if (nb == 0.0) return;
-  if (n == 0.0) { n = nb; m = mb; q = qb; return; }
-  const double tot = n + nb, d = mb - m;
-  m = m + d * (nb / tot);
-  q = q + qb + d * d * (n * (nb / tot));
-  n = tot;
-}
+// ---- statistics: disc_chan over the partials of one channel, thread t takes partials t, t + 256, ... in order, then a fixed tree
 
 __global__ __launch_bounds__(256) void disc_stats_finalize_kernel(const float* __restrict__ part, int P, int C,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -215,7 +194,7 @@ __global__ __launch_bounds__(256) void disc_blur_bwd_kernel(const float* __restr
 extern "C" int oniris_disc_blur(const float* x, const float* pro_s, const float* pro_t, float* out, int N, int H, int W, int C,
                                 oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && out && N > 0 && H > 0 && W > 0 && C > 0 && !pro_s == !pro_t, "disc_blur: bad arguments");
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int Ho = disc_out(H, 2), Wo = disc_out(W, 2);
   const long long total = (long long)N * Ho * Wo * C;
   ONIRIS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffLL, "disc_blur: %lld elements", total);
   ONIRIS_KLAUNCH(disc_blur_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, pro_s, pro_t, out, H,
@@ -226,7 +205,7 @@ extern "C" int oniris_disc_blur(const float* x, const float* pro_s, const float*
 
 extern "C" int oniris_disc_blur_bwd(const float* dy, float* dx, int N, int H, int W, int C, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(dy && dx && N > 0 && H > 0 && W > 0 && C > 0, "disc_blur_bwd: bad arguments");
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int Ho = disc_out(H, 2), Wo = disc_out(W, 2);
   const long long total = (long long)N * H * W * C;
   ONIRIS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffLL, "disc_blur_bwd: %lld elements", total);
   ONIRIS_KLAUNCH(disc_blur_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, H, W, C, Ho,
@@ -236,37 +215,6 @@ extern "C" int oniris_disc_blur_bwd(const float* dy, float* dx, int N, int H, in
 }
 
 // ---- BatchNorm + LeakyReLU backward.  stats = [mean | var | s | t | rstd][C] as oniris_disc_stats_finalize writes them.
-#define DISC_BN_PIX 1024
-__global__ __launch_bounds__(256) void disc_bn_bwd_reduce_kernel(const float* __restrict__ da, const float* __restrict__ z,
-                                                                 const float* __restrict__ stats, float* __restrict__ part,
-                                                                 long long npix, int C) {
-  __shared__ float r1[256], r2[256];
-  const int cl = threadIdx.x & 31, q = threadIdx.x >> 5, c = blockIdx.y * 32 + cl;
-  const bool live = c < C;
-  float s1 = 0.f, s2 = 0.f;
-  if (live) {
-    const float mean = stats[c], s = stats[2 * C + c], t = stats[3 * C + c], rstd = stats[4 * C + c];
-    const long long p0 = (long long)blockIdx.x * DISC_BN_PIX + q * (DISC_BN_PIX / 8);
-    for (int k = 0; k < DISC_BN_PIX / 8; ++k) {
-      const long long pix = p0 + k;
-      if (pix >= npix) break;
-      const float zv = z[pix * C + c];
-      const float g = da[pix * C + c];
-      const float dz = __builtin_fmaf(zv, s, t) > 0.f ? g : g * DISC_SLOPE;
-      s1 += dz;
-      s2 = __builtin_fmaf(dz, (zv - mean) * rstd, s2);
-    }
-  }
-  r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-  __syncthreads();
-  if (threadIdx.x < 32 && live) {
-    float a = 0.f, b = 0.f;
-    for (int k = 0; k < 8; ++k) { a += r1[k * 32 + cl]; b += r2[k * 32 + cl]; }
-    part[(size_t)blockIdx.x * 2 * C + c] = a;
-    part[(size_t)blockIdx.x * 2 * C + C + c] = b;
-  }
-}
-
 __global__ __launch_bounds__(256) void disc_bn_bwd_dx_kernel(const float* __restrict__ da, const float* __restrict__ z,
                                                              const float* __restrict__ stats, const float* __restrict__ sums,
                                                              const float* __restrict__ add, float add_scale, float* __restrict__ dx,
@@ -276,7 +224,7 @@ __global__ __launch_bounds__(256) void disc_bn_bwd_dx_kernel(const float* __rest
   const int c = (int)(e % C);
   const float mean = stats[c], s = stats[2 * C + c], t = stats[3 * C + c], rstd = stats[4 * C + c];
   const float zv = z[e], g = da[e];
-  const float dz = __builtin_fmaf(zv, s, t) > 0.f ? g : g * DISC_SLOPE;
+  const float dz = disc_dz(zv, s, t, g);
   float v;
   if (eval) {
     v = s * dz;
@@ -291,12 +239,7 @@ __global__ __launch_bounds__(256) void disc_bn_bwd_dx_kernel(const float* __rest
 extern "C" int oniris_disc_bn_bwd_reduce(const float* da, const float* z, const float* stats, float* part, int64_t npix, int C,
                                          oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(da && z && stats && part && npix > 0 && C > 0, "disc_bn_bwd_reduce: bad arguments");
-  const long long P = (npix + DISC_BN_PIX - 1) / DISC_BN_PIX;
-  ONIRIS_CHECK_ARG(P <= 0x7fffffffLL, "disc_bn_bwd_reduce: %lld pixels", (long long)npix);
-  ONIRIS_KLAUNCH(disc_bn_bwd_reduce_kernel, dim3((unsigned)P, cdiv(C, 32)), dim3(256), 0, (hipStream_t)stream, da, z, stats, part,
-                 (long long)npix, C);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
+  return disc3d_gn_bwd_reduce_launch("disc_bn_bwd_reduce", da, z, stats, part, 1, (long long)npix, C, (hipStream_t)stream);
 }
 
 extern "C" int oniris_disc_bn_bwd_dx(const float* da, const float* z, const float* stats, const float* sums, const float* add,

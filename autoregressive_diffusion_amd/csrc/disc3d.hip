@@ -2,7 +2,7 @@
 // :181-239, BlurPooling3D), fp32 throughout, channels-last activations [N][T][H][W][C].  include/oniris.h: oniris_disc3d_*.
 //   oniris_disc3d_conv             27-tap conv, stride 1 (forward and data gradient) or 2 (the stem), on the f32 MFMA with the
 //                                  per-sample GroupNorm + LeakyReLU prologue, bias / residual epilogue and per-tile statistics
-//                                  (csrc/disc_conv3d.h)
+//                                  (csrc/disc_conv3d.h over csrc/disc_parts.h)
 //   oniris_disc3d_wgrad            its weight and bias gradient into a bounded number of slabs
 //   oniris_disc3d_stem_dgrad       the stem's data gradient (at most 8 channels out): plain FMA, gathered per input element
 //   oniris_disc3d_gn_finalize      tile partials -> per (sample, group) mean / var / rstd and the prologue vectors s, t
@@ -16,25 +16,11 @@
 
 #define DISC3D_GROUPS 32
 
-template <typename K>
-static int disc3d_raise_lds(K kern, size_t bytes, const char* what) {
-  if (bytes <= 64 * 1024) return ONIRIS_OK;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) {
-    oniris_set_error("%s: raising the LDS limit failed: %s", what, hipGetErrorString(e));
-    return ONIRIS_ELAUNCH;
-  }
-  return ONIRIS_OK;
-}
-
-static bool disc3d_c_ok(int c) { return (c >= 1 && c <= 8) || (c > 0 && c % 32 == 0); }
-static int disc3d_out(int n, int stride) { return (n - 1) / stride + 1; }
-
 template <int NB, int S>
 static int disc3d_conv_launch(const Disc3dConvParams& p, dim3 grid, hipStream_t stream) {
   constexpr int HS = 15 * S + 3, AP = S == 1 ? DISC_APITCH : 9, WP = NB == 2 ? 96 : 32;
   const size_t bytes = ((size_t)HS * HS * AP + (size_t)9 * DISC_KC * WP) * sizeof(float);
-  if (int rc = disc3d_raise_lds(disc3d_conv_kernel<NB, S>, bytes, "disc3d_conv")) return rc;
+  if (int rc = disc_raise_lds(disc3d_conv_kernel<NB, S>, bytes, "disc3d_conv")) return rc;
   ONIRIS_KLAUNCH((disc3d_conv_kernel<NB, S>), grid, dim3(256), bytes, stream, p);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
@@ -44,14 +30,14 @@ extern "C" int oniris_disc3d_conv(const float* x, const float* w, const float* b
                                   const float* res, float res_scale, float* out, float* part, int N, int T, int H, int W, int Cin,
                                   int Cout, int stride, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && w && out && N > 0 && T > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "disc3d_conv: bad arguments");
-  ONIRIS_CHECK_ARG(disc3d_c_ok(Cin) && disc3d_c_ok(Cout), "disc3d_conv: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
+  ONIRIS_CHECK_ARG(disc_c_ok(Cin) && disc_c_ok(Cout), "disc3d_conv: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
   ONIRIS_CHECK_ARG(stride == 1 || (Cin <= 8 && Cout % 32 == 0 && !pro_s && !res),
                    "disc3d_conv: stride 2 takes Cin 1..8, Cout %% 32 == 0, no prologue and no residual");
   ONIRIS_CHECK_ARG(!pro_s == !pro_t, "disc3d_conv: the prologue needs both s and t");
   ONIRIS_CHECK_ARG(!part || Cout % 32 == 0, "disc3d_conv: statistics need Cout %% 32 == 0");
   Disc3dConvParams p;
   p.x = x; p.w = w; p.bias = bias; p.pro_s = pro_s; p.pro_t = pro_t; p.res = res; p.out = out; p.part = part;
-  p.N = N; p.T = T; p.H = H; p.W = W; p.To = disc3d_out(T, stride); p.Ho = disc3d_out(H, stride); p.Wo = disc3d_out(W, stride);
+  p.N = N; p.T = T; p.H = H; p.W = W; p.To = disc_out(T, stride); p.Ho = disc_out(H, stride); p.Wo = disc_out(W, stride);
   p.Cin = Cin; p.CinP = Cin <= 8 ? 8 : Cin; p.Cout = Cout; p.CoutP = roundup(Cout, 32);
   p.tiles_x = cdiv(p.Wo, DISC_TILE); p.tiles_y = cdiv(p.Ho, DISC_TILE); p.res_scale = res_scale;
   const long long wgs = (long long)N * p.To * p.tiles_x * p.tiles_y;
@@ -66,7 +52,7 @@ template <int S>
 static int disc3d_wgrad_launch(const Disc3dWgradParams& p, dim3 grid, hipStream_t stream) {
   constexpr int HS = 15 * S + 3, AP = S == 1 ? DISC_WPITCH : 9;
   const size_t bytes = ((size_t)HS * HS * AP + 256 * 32) * sizeof(float);
-  if (int rc = disc3d_raise_lds(disc3d_wgrad_kernel<S>, bytes, "disc3d_wgrad")) return rc;
+  if (int rc = disc_raise_lds(disc3d_wgrad_kernel<S>, bytes, "disc3d_wgrad")) return rc;
   ONIRIS_KLAUNCH((disc3d_wgrad_kernel<S>), grid, dim3(256), bytes, stream, p);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
@@ -76,12 +62,12 @@ extern "C" int oniris_disc3d_wgrad(const float* x, const float* pro_s, const flo
                                    int N, int T, int H, int W, int Cin, int Cout, int stride, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && dy && slab && nslab > 0 && N > 0 && T > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2),
                    "disc3d_wgrad: bad arguments");
-  ONIRIS_CHECK_ARG(disc3d_c_ok(Cin) && disc3d_c_ok(Cout), "disc3d_wgrad: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
+  ONIRIS_CHECK_ARG(disc_c_ok(Cin) && disc_c_ok(Cout), "disc3d_wgrad: Cin %d / Cout %d: 1..8 or a multiple of 32", Cin, Cout);
   ONIRIS_CHECK_ARG(stride == 1 || (Cin <= 8 && !pro_s), "disc3d_wgrad: stride 2 takes Cin 1..8 and no prologue");
   ONIRIS_CHECK_ARG(!pro_s == !pro_t, "disc3d_wgrad: the prologue needs both s and t");
   Disc3dWgradParams p;
   p.x = x; p.pro_s = pro_s; p.pro_t = pro_t; p.dy = dy; p.slab = slab;
-  p.N = N; p.T = T; p.H = H; p.W = W; p.To = disc3d_out(T, stride); p.Ho = disc3d_out(H, stride); p.Wo = disc3d_out(W, stride);
+  p.N = N; p.T = T; p.H = H; p.W = W; p.To = disc_out(T, stride); p.Ho = disc_out(H, stride); p.Wo = disc_out(W, stride);
   p.Cin = Cin; p.CinP = Cin <= 8 ? 8 : Cin; p.Cout = Cout;
   p.tiles_x = cdiv(p.Wo, DISC_TILE); p.tiles_y = cdiv(p.Ho, DISC_TILE);
   const long long items = (long long)N * p.To * p.tiles_x * p.tiles_y;
@@ -135,21 +121,13 @@ extern "C" int oniris_disc3d_stem_dgrad(const float* dy, const float* w, float* 
   const long long total = (long long)N * T * H * W * Cin;
   ONIRIS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffLL, "disc3d_stem_dgrad: %lld elements", total);
   ONIRIS_KLAUNCH(disc3d_stem_dgrad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, w, dx, T, H,
-                 W, disc3d_out(T, 2), disc3d_out(H, 2), disc3d_out(W, 2), Cin, Cout, total);
+                 W, disc_out(T, 2), disc_out(H, 2), disc_out(W, 2), Cin, Cout, total);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }
 
-// ---- GroupNorm statistics: Chan's combination of (count, mean, M2) in double over the P tile partials of one sample times the
-// C / 32 channels of one group; thread t takes entries t, t + 256, ... (entry = partial * cpg + channel) in order, then a fixed tree
-__device__ __forceinline__ void disc3d_chan(double& n, double& m, double& q, double nb, double mb, double qb) {
-  if (nb == 0.0) return;
-  if (n == 0.0) { n = nb; m = mb; q = qb; return; }
-  const double tot = n + nb, d = mb - m;
-  m = m + d * (nb / tot);
-  q = q + qb + d * d * (n * (nb / tot));
-  n = tot;
-}
+// ---- GroupNorm statistics: disc_chan over the P tile partials of one sample times the C / 32 channels of one group; thread t takes
+// entries t, t + 256, ... (entry = partial * cpg + channel) in order, then a fixed tree
 
 __global__ __launch_bounds__(256) void disc3d_gn_finalize_kernel(const float* __restrict__ part, int N, int P, int C,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -160,13 +138,13 @@ __global__ __launch_bounds__(256) void disc3d_gn_finalize_kernel(const float* __
   for (int i = t; i < P * cpg; i += 256) {
     const float* e = part + ((size_t)smp * P + i / cpg) * 4 * C + g * cpg + i % cpg;
     const double cnt = e[0], s1 = e[3 * C];
-    disc3d_chan(n, m, q, cnt, (double)e[C] + s1 / cnt, (double)e[2 * C] - s1 * s1 / cnt);
+    disc_chan(n, m, q, cnt, (double)e[C] + s1 / cnt, (double)e[2 * C] - s1 * s1 / cnt);
   }
   sn[t] = n; sm[t] = m; sq[t] = q;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if (t < s) {
-      disc3d_chan(n, m, q, sn[t + s], sm[t + s], sq[t + s]);
+      disc_chan(n, m, q, sn[t + s], sm[t + s], sq[t + s]);
       sn[t] = n; sm[t] = m; sq[t] = q;
     }
     __syncthreads();
@@ -196,41 +174,6 @@ extern "C" int oniris_disc3d_gn_finalize(const float* part, int N, int P, int C,
 }
 
 // ---- GroupNorm + LeakyReLU backward.  stats = [mean | var | s | t | rstd][N][C] as oniris_disc3d_gn_finalize writes them.
-#define DISC3D_GN_PIX 1024
-__global__ __launch_bounds__(256) void disc3d_gn_bwd_reduce_kernel(const float* __restrict__ da, const float* __restrict__ z,
-                                                                   const float* __restrict__ stats, float* __restrict__ part, int N,
-                                                                   long long npix, int C) {
-  __shared__ float r1[256], r2[256];
-  const int cl = threadIdx.x & 31, q = threadIdx.x >> 5, c = blockIdx.y * 32 + cl, smp = blockIdx.z;
-  const bool live = c < C;
-  float s1 = 0.f, s2 = 0.f;
-  if (live) {
-    const size_t NC = (size_t)N * C, o = (size_t)smp * C + c;
-    const float mean = stats[o], s = stats[2 * NC + o], t = stats[3 * NC + o], rstd = stats[4 * NC + o];
-    const long long p0 = (long long)blockIdx.x * DISC3D_GN_PIX + q * (DISC3D_GN_PIX / 8);
-    const float* zb = z + (size_t)smp * npix * C;
-    const float* db = da + (size_t)smp * npix * C;
-    for (int k = 0; k < DISC3D_GN_PIX / 8; ++k) {
-      const long long pix = p0 + k;
-      if (pix >= npix) break;
-      const float zv = zb[pix * C + c];
-      const float gv = db[pix * C + c];
-      const float dz = __builtin_fmaf(zv, s, t) > 0.f ? gv : gv * DISC_SLOPE;
-      s1 += dz;
-      s2 = __builtin_fmaf(dz, (zv - mean) * rstd, s2);
-    }
-  }
-  r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-  __syncthreads();
-  if (threadIdx.x < 32 && live) {
-    float a = 0.f, b = 0.f;
-    for (int k = 0; k < 8; ++k) { a += r1[k * 32 + cl]; b += r2[k * 32 + cl]; }
-    float* o = part + ((size_t)smp * gridDim.x + blockIdx.x) * 2 * C;
-    o[c] = a;
-    o[C + c] = b;
-  }
-}
-
 // per (sample, group): the channel sums S1 = sum dz, S2 = sum dz xhat (thread t takes partials t, t + 256, ..., then a fixed tree),
 // and the group means m1 = sum_c gamma S1 / cnt, m2 = sum_c gamma S2 / cnt, channels ascending
 __global__ __launch_bounds__(256) void disc3d_gn_bwd_finalize_kernel(const float* __restrict__ part, int N, int P, int C,
@@ -279,7 +222,7 @@ __global__ __launch_bounds__(256) void disc3d_gn_bwd_dx_kernel(const float* __re
   const float mean = stats[o], s = stats[2 * NC + o], t = stats[3 * NC + o], rstd = stats[4 * NC + o];
   const float m1 = mm[(size_t)smp * DISC3D_GROUPS + g], m2 = mm[((size_t)N + smp) * DISC3D_GROUPS + g];
   const float zv = z[e], gv = da[e];
-  const float dz = __builtin_fmaf(zv, s, t) > 0.f ? gv : gv * DISC_SLOPE;
+  const float dz = disc_dz(zv, s, t, gv);
   const float xh = (zv - mean) * rstd;
   float v = rstd * ((gamma[c] * dz - m1) - xh * m2);
   if (add) v = __builtin_fmaf(add_scale, add[e], v);
@@ -289,12 +232,7 @@ __global__ __launch_bounds__(256) void disc3d_gn_bwd_dx_kernel(const float* __re
 extern "C" int oniris_disc3d_gn_bwd_reduce(const float* da, const float* z, const float* stats, float* part, int N, int64_t npix,
                                            int C, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(da && z && stats && part && N > 0 && N <= 65535 && npix > 0 && C > 0, "disc3d_gn_bwd_reduce: bad arguments");
-  const long long P = (npix + DISC3D_GN_PIX - 1) / DISC3D_GN_PIX;
-  ONIRIS_CHECK_ARG(P <= 0x7fffffffLL, "disc3d_gn_bwd_reduce: %lld positions", (long long)npix);
-  ONIRIS_KLAUNCH(disc3d_gn_bwd_reduce_kernel, dim3((unsigned)P, cdiv(C, 32), N), dim3(256), 0, (hipStream_t)stream, da, z, stats, part,
-                 N, (long long)npix, C);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
+  return disc3d_gn_bwd_reduce_launch("disc3d_gn_bwd_reduce", da, z, stats, part, N, (long long)npix, C, (hipStream_t)stream);
 }
 
 extern "C" int oniris_disc3d_gn_bwd_finalize(const float* part, int N, int P, int C, const float* gamma, int64_t npix, float* sums,
@@ -386,7 +324,7 @@ __global__ __launch_bounds__(256) void disc3d_blur_bwd_kernel(const float* __res
 extern "C" int oniris_disc3d_blur(const float* x, const float* pro_s, const float* pro_t, float* out, int N, int T, int H, int W,
                                   int C, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && out && N > 0 && T > 0 && H > 0 && W > 0 && C > 0 && !pro_s == !pro_t, "disc3d_blur: bad arguments");
-  const int To = disc3d_out(T, 2), Ho = disc3d_out(H, 2), Wo = disc3d_out(W, 2);
+  const int To = disc_out(T, 2), Ho = disc_out(H, 2), Wo = disc_out(W, 2);
   const long long total = (long long)N * To * Ho * Wo * C;
   ONIRIS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffLL, "disc3d_blur: %lld elements", total);
   ONIRIS_KLAUNCH(disc3d_blur_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, pro_s, pro_t, out, T,
@@ -397,7 +335,7 @@ extern "C" int oniris_disc3d_blur(const float* x, const float* pro_s, const floa
 
 extern "C" int oniris_disc3d_blur_bwd(const float* dy, float* dx, int N, int T, int H, int W, int C, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(dy && dx && N > 0 && T > 0 && H > 0 && W > 0 && C > 0, "disc3d_blur_bwd: bad arguments");
-  const int To = disc3d_out(T, 2), Ho = disc3d_out(H, 2), Wo = disc3d_out(W, 2);
+  const int To = disc_out(T, 2), Ho = disc_out(H, 2), Wo = disc_out(W, 2);
   const long long total = (long long)N * T * H * W * C;
   ONIRIS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffLL, "disc3d_blur_bwd: %lld elements", total);
   ONIRIS_KLAUNCH(disc3d_blur_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, T, H, W, C,

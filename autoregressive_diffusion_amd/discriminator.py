@@ -2,15 +2,17 @@
 MixedDiscriminator` instead of `from edm2.vae import MixedDiscriminator`.
 
 `Discriminator2D`, the per-frame half and by far the larger one, runs on HIP kernels (include/oniris.h: oniris_disc_*, csrc/disc.hip,
-csrc/disc_conv3.h): fp32 storage and fp32 arithmetic, every convolution an implicit GEMM on the exact-f32 matrix instruction.  One
+csrc/disc_conv3.h, csrc/disc_parts.h): fp32 storage and fp32 arithmetic, every convolution an implicit GEMM on the exact-f32 matrix
+instruction.  One
 autograd Function per block plus the stem and the head; activations travel between them channels-last [N][H][W][C].  BatchNorm and
 LeakyReLU never exist as tensors: a conv emits per-tile (count, centre, S2, S1) of what it stores, a finalize launch turns them into the
 per-channel scale s and shift t, and the consumer (the next conv, or the blur pool) applies lrelu(x s + t) while it stages its operand.
 What stays in torch: the NCHW <-> channels-last copies at the two ends and permutations at parameter size.
 
 `Discriminator3D`, the spatio-temporal half, runs on HIP kernels as well when model and input are on the GPU (oniris_disc3d_*,
-csrc/disc3d.hip, csrc/disc_conv3d.h): the same structure on [N][T][H][W][C], a 27-tap conv being the sum over kt of 9-tap convs of
-neighbouring planes, GroupNorm(32) in place of BatchNorm with scale and shift per (sample, channel), a stride-2 stem and a 3-D blur
+csrc/disc3d.hip, csrc/disc_conv3d.h, the tile parts shared with the 2-D half in csrc/disc_parts.h): the same structure on
+[N][T][H][W][C], a 27-tap conv being the sum over kt of 9-tap convs of neighbouring planes, GroupNorm(32) in place of BatchNorm with
+scale and shift per (sample, channel), a stride-2 stem and a 3-D blur
 pool; with CPU tensors it stays plain torch.nn code.  `MixedDiscriminator` joins the two as the reference does.
 
 Gradients are summed in a fixed order into a bounded number of partial slabs and then over the slabs; nothing uses atomics, two runs
@@ -615,8 +617,8 @@ class DiscriminatorBlock3D(nn.Module):
 
 class Discriminator3D(nn.Module):
     """The reference's Discriminator3D (discriminator.py:242-283).  With model and input on the GPU it runs on HIP kernels, forward
-    and backward (include/oniris.h: oniris_disc3d_*, csrc/disc3d.hip, csrc/disc_conv3d.h); with CPU tensors it is plain torch.nn
-    code in the tensors' dtype.
+    and backward (include/oniris.h: oniris_disc3d_*, csrc/disc3d.hip, csrc/disc_conv3d.h, csrc/disc_parts.h); with CPU tensors it is
+    plain torch.nn code in the tensors' dtype.
 
     Native domain: in_channels 1..8; every width a multiple of 32 up to 256, any sequence of them (the final block's shortcut is a
     1x1x1 conv); any T, H, W >= 1; input (N, C, T, H, W), computed in fp32 -> logits (N, 2, T', H', W'), every extent halved

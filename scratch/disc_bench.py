@@ -34,6 +34,9 @@ def say(s):
         out.flush()
 
 
+runs = [""]                                     # the last ms() call's range, for the report
+
+
 def ms(fn, reps=5):
     fn()
     ts = []
@@ -44,6 +47,7 @@ def ms(fn, reps=5):
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
+    runs[0] = f"({reps} runs {min(ts):.2f} .. {max(ts):.2f})"
     return statistics.median(ts)
 
 
@@ -91,7 +95,7 @@ if mode == "native":
     ff, fb = count["flops"], count["bytes"]
     t_f = ms(fwd)
     alg = nbytes(x) + 4.0 * N * 2 * (H // 4) * (W // 4) + 4.0 * sum(v.numel() for v in params.values())
-    say(f"forward: {t_f:.1f} ms; conv launches {ff / 1e12:.3f} TFLOP -> {ff / t_f / 1e9:.1f} TFLOP/s over the whole pass = "
+    say(f"forward: median {t_f:.2f} ms {runs[0]}; conv launches {ff / 1e12:.3f} TFLOP -> {ff / t_f / 1e9:.1f} TFLOP/s over the whole pass = "
         f"{100 * ff / t_f / 1e9 / 157.3:.1f} % of 157.3 (the guide's untuned LDS-tiled GEMM on this instruction: 122)")
     say(f"forward: launches read + write {fb / 1e9:.2f} GB (counted from operand sizes) -> {fb / t_f / 1e6:.0f} GB/s; the input, the "
         f"logits and the parameters alone are {alg / 1e9:.3f} GB")
@@ -100,14 +104,14 @@ if mode == "native":
     count["on"] = False
     fa = count["flops"]
     t_a = ms(lambda: step(xg))
-    say(f"forward + backward, all gradients: {t_a:.1f} ms; conv + wgrad launches {fa / 1e12:.3f} TFLOP -> {fa / t_a / 1e9:.1f} TFLOP/s")
+    say(f"forward + backward, all gradients: median {t_a:.2f} ms {runs[0]}; conv + wgrad launches {fa / 1e12:.3f} TFLOP -> {fa / t_a / 1e9:.1f} TFLOP/s")
     net.requires_grad_(False)
     count.update(flops=0.0, bytes=0.0, on=True)
     step(xg)
     count["on"] = False
     fi = count["flops"]
     t_i = ms(lambda: step(xg))
-    say(f"forward + backward, input gradient only (parameters frozen): {t_i:.1f} ms; conv launches {fi / 1e12:.3f} TFLOP -> "
+    say(f"forward + backward, input gradient only (parameters frozen): median {t_i:.2f} ms {runs[0]}; conv launches {fi / 1e12:.3f} TFLOP -> "
         f"{fi / t_i / 1e9:.1f} TFLOP/s")
     # the largest conv launch alone: blocks.0.conv1, 64 -> 64 at full resolution with the prologue and the statistics epilogue
     a = torch.randn(N, H, W, 64, device=DEV)

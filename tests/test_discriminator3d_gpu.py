@@ -1,5 +1,5 @@
-"""The native Discriminator3D (autoregressive_diffusion_amd/discriminator.py, csrc/disc3d.hip, csrc/disc_conv3d.h) on the GPU: every
-kernel stage element by element against the float64 expectations (tests/disc3d_cpu_restatement.py), whole nets against the
+"""The native Discriminator3D (autoregressive_diffusion_amd/discriminator.py, csrc/disc3d.hip, csrc/disc_conv3d.h,
+csrc/disc_parts.h) on the GPU: every kernel stage element by element against the float64 expectations (tests/disc3d_cpu_restatement.py), whole nets against the
 reference's fixture G20 and against the float64 restatement, the all-native MixedDiscriminator against G19 with torch's conv3d and
 group_norm replaced by functions that raise, determinism and the frozen-critic step.
 

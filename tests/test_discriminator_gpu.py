@@ -1,5 +1,5 @@
-"""The native Discriminator2D (autoregressive_diffusion_amd/discriminator.py, csrc/disc.hip, csrc/disc_conv3.h) on the GPU: every
-kernel stage element by element against the float64 restatement (tests/disc_cpu_restatement.py), the whole net against the
+"""The native Discriminator2D (autoregressive_diffusion_amd/discriminator.py, csrc/disc.hip, csrc/disc_conv3.h,
+csrc/disc_parts.h) on the GPU: every kernel stage element by element against the float64 restatement (tests/disc_cpu_restatement.py), the whole net against the
 reference's fixtures G18 / G19 and against float64, determinism, the frozen-critic step, and the gradient into the VAE.
 
 Bounds.  u = 2^-24 is the unit roundoff of fp32.
