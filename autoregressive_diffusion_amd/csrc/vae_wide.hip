@@ -1,0 +1,193 @@
+// VAE decoder at block widths above 64 channels (reference: edm2/vae/vae.py EncoderDecoder(type='decoder'), :56-204), inference
+// only, fp32 throughout, channels-last [B][T][H][W][C].  include/oniris.h: oniris_vae_wide_*.  Per wide ResBlock:
+//   oniris_vae_wide_temb    oniris_vae_temb for ResBlocks of any width (one launch per decode of a model with a wide block)
+//   oniris_vae_wide_act     y = SiLU(RMS(x) (1 + scale) + shift) into the sequence buffer S = [g prefix frames ++ y] and the cache
+//   oniris_vae_wide_conv_a  a = bias + the group-causal (2g, 3, 3) conv of S                (vae_wide_kernel<NB, VW_CONV_A>)
+//   oniris_vae_wide_act     u = SiLU(RMS(a))
+//   oniris_vae_wide_conv_b  out = res + bias + conv3x3(u)                                   (disc_conv_kernel<NB>, res_scale = 1)
+// and the 1x1 stages as GEMMs on the same tile kernel: oniris_vae_wide_up, oniris_vae_wide_out (csrc/vae_wide_conv.h).
+// The convs take operands that are already activated: the cache is a plain copy of frames of S, and a conv of integers is exact.
+// Nothing here bounds the width: MAX_WIDTH of autoregressive_diffusion_amd/vae.py is the one constant that does.
+#include "oniris.h"
+#include "common.h"
+#include "vae_conv3.h"
+#include "disc_conv3.h"
+#include "vae_wide_conv.h"
+
+// ---- the activation pass: one wave per pixel, lane l holds channels l, l + 64, ...; the sum of squares is the lane's channels in
+// ascending order, then the xor butterfly over the lanes -- an order that depends on C alone.
+// Pixel p of S = [B][g + T][HW][C]: frame f < g is the prefix (a copy of cache_in; without one the workgroup of frame f + g
+// writes it), frame f >= g is y of input frame f - g; the last g frames of S also go to cache_out.  g = 0: S = [B][T][HW][C].
+__global__ __launch_bounds__(256) void vae_wide_act_kernel(const float* __restrict__ x, const float* __restrict__ emb,
+                                                           const float* __restrict__ cache_in, float* __restrict__ cache_out,
+                                                           float* __restrict__ S, long long total, int T, long long HW, int C, int g) {
+  const long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (p >= total) return;
+  const long long q = p % HW, bf = p / HW;
+  const int f = (int)(bf % (g + T));
+  const long long b = bf / (g + T);
+  float* dst = S + (size_t)p * C;
+  if (f < g) {
+    if (!cache_in) return;
+    const float* src = cache_in + (((size_t)b * g + f) * HW + q) * C;
+    for (int c = lane; c < C; c += 64) dst[c] = src[c];
+    return;
+  }
+  const int t = f - g;
+  const float* src = x + (((size_t)b * T + t) * HW + q) * C;
+  const float* sc = emb ? emb + (size_t)b * 2 * C : nullptr;
+  float ss = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = src[c];
+    ss = fmaf(v, v, ss);
+  }
+  const float d = vae_rms(wave_sum(ss), C);
+  float* pre = (!cache_in && t < g) ? S + (((size_t)b * (g + T) + t) * HW + q) * C : nullptr;
+  float* co = (g > 0 && t >= T - g) ? cache_out + (((size_t)b * g + (t - (T - g))) * HW + q) * C : nullptr;
+  for (int c = lane; c < C; c += 64) {
+    const float v = vae_act(src[c], d, sc, C, c);
+    dst[c] = v;
+    if (pre) pre[c] = v;
+    if (co) co[c] = v;
+  }
+}
+
+// ---- t-embedding: vae_temb_kernel of csrc/vae.hip (the same operations in the same order, so the same bits) with the Fourier
+// features of a ResBlock of any width in dynamic LDS; that kernel holds 128 of them, enough for 64 channels.
+__global__ __launch_bounds__(128) void vae_wide_temb_kernel(const float* __restrict__ params, const int32_t* __restrict__ table,
+                                                            const float* __restrict__ t, int B, float* __restrict__ emb) {
+  extern __shared__ float vae_wide_f[];
+  const int r = blockIdx.x, b = blockIdx.y;
+  const int poff = table[3 * r], C2 = table[3 * r + 1], eoff = table[3 * r + 2] * B;
+  const float* freqs = params + poff;
+  const float* phases = freqs + C2;
+  const float* W = phases + C2;
+  const float* bias = W + (size_t)C2 * C2;
+  const float tb = t[b];
+  for (int k = threadIdx.x; k < C2; k += blockDim.x) vae_wide_f[k] = cosf(tb * freqs[k] + phases[k]) * 1.41421356237309515f;
+  __syncthreads();
+  for (int j = threadIdx.x; j < C2; j += blockDim.x) {
+    float acc = 0.f;
+    for (int k = 0; k < C2; ++k) acc = fmaf(W[(size_t)j * C2 + k], vae_wide_f[k], acc);
+    emb[eoff + (size_t)b * C2 + j] = acc + bias[j];
+  }
+}
+
+// ---- host side
+static inline bool vae_wide_c_ok(int c) { return c > 0 && c <= 65536; }
+static inline int vae_wide_nb(int CP) { return CP % 64 == 0 ? 2 : 1; }
+
+template <int NB, int MODE>
+static int vae_wide_launch(const char* what, const VaeWideParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32, TAPS = MODE == VW_CONV_A ? 9 : 1;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)TAPS * DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(vae_wide_kernel<NB, MODE>, bytes, what)) return rc;
+  ONIRIS_KLAUNCH((vae_wide_kernel<NB, MODE>), grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+// planes: the output planes a workgroup column walks; p.nsub, p.Cout, p.H, p.W set
+template <int MODE>
+static int vae_wide_dispatch(const char* what, VaeWideParams& p, long long planes, hipStream_t stream) {
+  p.CinP = roundup(p.Cin, 2);
+  p.CP = roundup(p.Cout, 32);
+  p.tiles_x = cdiv(p.W, DISC_TILE); p.tiles_y = cdiv(p.H, DISC_TILE);
+  const int nb = vae_wide_nb(p.CP);
+  p.nblk = p.CP / (32 * nb);
+  const long long wgs = planes * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && (long long)p.nsub * p.nblk <= 65535, "%s: %lld tiles", what, wgs);
+  const dim3 grid((unsigned)wgs, p.nsub * p.nblk);
+  return nb == 2 ? vae_wide_launch<2, MODE>(what, p, grid, stream) : vae_wide_launch<1, MODE>(what, p, grid, stream);
+}
+
+extern "C" int oniris_vae_wide_temb(const float* params, const int32_t* table, int n_res_blocks, int max_c2, const float* t, int B,
+                                    float* emb, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(params && table && t && emb, "vae_wide_temb: null pointer");
+  ONIRIS_CHECK_ARG(n_res_blocks > 0 && B > 0 && B <= 65535 && max_c2 > 0 && max_c2 <= 16384,
+                   "vae_wide_temb: bad sizes (res blocks %d, B %d, widest 2C %d)", n_res_blocks, B, max_c2);
+  ONIRIS_KLAUNCH(vae_wide_temb_kernel, dim3(n_res_blocks, B), dim3(128), (size_t)max_c2 * sizeof(float), (hipStream_t)stream, params,
+                 table, t, B, emb);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+extern "C" int oniris_vae_wide_act(const float* x, const float* emb, const float* cache_in, float* cache_out, float* S, int B, int T,
+                                   int H, int W, int C, int g, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(x && S && (const float*)S != x, "vae_wide_act: null pointer or S aliases x");
+  ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(C) && g >= 0 && g <= 8,
+                   "vae_wide_act: bad sizes (B %d T %d H %d W %d C %d g %d)", B, T, H, W, C, g);
+  ONIRIS_CHECK_ARG(g == 0 ? (!cache_in && !cache_out) : (cache_out && T % g == 0 && cache_in != cache_out),
+                   "vae_wide_act: g %d, T %d: the sequence form needs cache_out and T %% g == 0, the plain form no cache", g, T);
+  const long long HW = (long long)H * W, total = (long long)B * (g + T) * HW;
+  ONIRIS_CHECK_ARG((total + 3) / 4 <= 0x7fffffffLL, "vae_wide_act: %lld pixels", total);
+  oniris_launch(vae_wide_act_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), (hipStream_t)stream, x, emb, cache_in, cache_out, S,
+                total, T, HW, C, g);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+extern "C" int oniris_vae_wide_conv_a(const float* S, const float* w, const float* bias, float* out, int B, int T, int H, int W, int C,
+                                      int g, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(S && w && bias && out && (const float*)out != S, "vae_wide_conv_a: null pointer or out aliases S");
+  ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(C) && g >= 1 && g <= 8 && T % g == 0,
+                   "vae_wide_conv_a: bad sizes (B %d T %d H %d W %d C %d g %d)", B, T, H, W, C, g);
+  ONIRIS_CHECK_ARG((long long)B * (g + T) <= 0x7fffffffLL, "vae_wide_conv_a: %lld planes", (long long)B * (g + T));
+  VaeWideParams p{};
+  p.x = S; p.w = w; p.bias = bias; p.out = out;
+  p.B = B; p.T = T; p.H = H; p.W = W; p.Cin = C; p.Cout = C; p.nsub = g; p.g = g;
+  return vae_wide_dispatch<VW_CONV_A>("vae_wide_conv_a", p, (long long)B * (T / g), (hipStream_t)stream);
+}
+
+template <int NB>
+static int vae_wide_conv_b_launch(const DiscConvParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)p.taps * DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(disc_conv_kernel<NB>, bytes, "vae_wide_conv_b")) return rc;
+  ONIRIS_KLAUNCH(disc_conv_kernel<NB>, grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+extern "C" int oniris_vae_wide_conv_b(const float* u, const float* res, const float* w, const float* bias, float* out, int B, int T,
+                                      int H, int W, int C, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(u && res && w && bias && out && (const float*)out != u, "vae_wide_conv_b: null pointer or out aliases u");
+  ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(C), "vae_wide_conv_b: bad sizes (B %d T %d H %d W %d C %d)", B, T,
+                   H, W, C);
+  DiscConvParams p;
+  p.x = u; p.w = w; p.bias = bias; p.pro_s = nullptr; p.pro_t = nullptr; p.res = res; p.out = out; p.part = nullptr;
+  p.N = B * T; p.H = H; p.W = W; p.Cin = C; p.CinP = roundup(C, 2); p.Cout = C; p.CoutP = roundup(C, 32); p.taps = 9;
+  p.tiles_x = cdiv(W, DISC_TILE); p.tiles_y = cdiv(H, DISC_TILE); p.res_scale = 1.f;
+  const long long wgs = (long long)B * T * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL, "vae_wide_conv_b: %lld tiles", wgs);
+  const int nb = vae_wide_nb(p.CoutP);
+  const dim3 grid((unsigned)wgs, p.CoutP / (32 * nb));
+  return nb == 2 ? vae_wide_conv_b_launch<2>(p, grid, (hipStream_t)stream) : vae_wide_conv_b_launch<1>(p, grid, (hipStream_t)stream);
+}
+
+extern "C" int oniris_vae_wide_up(const float* x, const float* w, const float* bias, float* out, int B, int T, int H, int W, int C,
+                                  int tcomp, int scomp, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(x && w && bias && out && (const float*)out != x, "vae_wide_up: null pointer or out aliases x");
+  ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(C) && tcomp >= 1 && tcomp <= 2 && scomp >= 1 && scomp <= 2,
+                   "vae_wide_up: bad sizes (B %d T %d H %d W %d C %d tc %d sc %d)", B, T, H, W, C, tcomp, scomp);
+  VaeWideParams p{};
+  p.x = x; p.w = w; p.bias = bias; p.out = out;
+  p.B = B; p.T = T; p.H = H; p.W = W; p.Cin = C; p.Cout = C; p.nsub = tcomp * scomp * scomp; p.g = 1; p.tc = tcomp; p.sc = scomp;
+  return vae_wide_dispatch<VW_UP>("vae_wide_up", p, (long long)B * T, (hipStream_t)stream);
+}
+
+extern "C" int oniris_vae_wide_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout,
+                                   int split, const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh,
+                                   int64_t sw, int64_t sc, uint8_t* frames, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(x && w && bias && (out || frames), "vae_wide_out: null pointer");
+  ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(Cin) && vae_wide_c_ok(Cout) && split >= 0 && split < Cout,
+                   "vae_wide_out: bad sizes (B %d T %d H %d W %d Cin %d Cout %d split %d)", B, T, H, W, Cin, Cout, split);
+  ONIRIS_CHECK_ARG(split == 0 || (logvar_mult && (out2 || !out)), "vae_wide_out: the split needs logvar_mult and out2");
+  ONIRIS_CHECK_ARG(!frames || split > 0, "vae_wide_out: frames need the mean / logvar split");
+  VaeWideParams p{};
+  p.x = x; p.w = w; p.bias = bias; p.out = out; p.out2 = out2; p.frames = (unsigned char*)frames; p.lvm = logvar_mult;
+  p.B = B; p.T = T; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.nsub = 1; p.g = 1; p.split = split;
+  p.sb = sb; p.st = st; p.sh = sh; p.sw = sw; p.scs = sc;
+  return vae_wide_dispatch<VW_OUT>("vae_wide_out", p, (long long)B * T, (hipStream_t)stream);
+}

@@ -10,6 +10,9 @@ whole sequence gives (bit-identical here: csrc/vae*.hip and csrc/vae_conv3.h sum
 Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up` launch, two per ResBlock, one `out` launch,
 plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
 ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
+Decoder blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip:
+the same `up` and `out` stages as GEMMs and four launches per ResBlock (activation, conv A, activation, conv B), with the same
+cache entries; a model that has such a block has the decoder only (include/oniris.h: oniris_vae_wide_*).
 
 `forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
 enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
@@ -25,7 +28,8 @@ from torch import nn
 from . import _lib
 from .edm2.utils import BetterModule, MPFourier, bmult
 
-MAX_WIDTH = 64
+MAX_WIDTH = 256        # the widest decoder block (the MFMA tile kernels of csrc/vae_wide.hip take any width; this is the one bound)
+MAX_NARROW = 64        # up to here a block runs on the register-tile kernels of csrc/vae.hip / csrc/vae_conv3.h
 _REF = "the reference's edm2.vae (this package runs the VAE on HIP kernels only)"
 
 
@@ -77,6 +81,32 @@ def _pack_res(rb, C, g, f32):
     bb = torch.zeros(nch, **f32)
     bb[:C] = rb.conv3d1.bias.detach().to(**f32)
     return dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
+
+
+def _pack_res_wide(rb, C, g, f32):
+    """The two convolutions of a ResBlock wider than MAX_NARROW in the layouts of csrc/vae_wide_conv.h: output channels
+    [sub][CP] (CP = C rounded up to a multiple of 32), input channels rounded up to even, zero where padded."""
+    CP, CinP = -(-C // 32) * 32, C + (C & 1)
+    w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gl
+    wa = torch.zeros(2 * g, 3, 3, CinP, g, CP, **f32)
+    wa[:, :, :, :C, :, :C] = w.reshape(C, g, C, 2 * g, 3, 3).permute(3, 4, 5, 2, 1, 0)   # kt, ky, kx, ci, gl, c
+    ba = torch.zeros(g, CP, **f32)
+    ba[:, :C] = rb.conv3d0.conv3d.bias.detach().to(**f32).reshape(C, g).t()
+    wb = torch.zeros(3, 3, CinP, CP, **f32)
+    wb[:, :, :C, :C] = rb.conv3d1.weight.detach().to(**f32)[:, :, 0].permute(2, 3, 1, 0)   # ky, kx, ci, co
+    bb = torch.zeros(CP, **f32)
+    bb[:C] = rb.conv3d1.bias.detach().to(**f32)
+    return dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
+
+
+def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
+    """A 1x1 conv Cin -> nsub Cout (conv channel sub Cout + c) as w [CinP][nsub CP], bias [nsub][CP] (csrc/vae_wide_conv.h)."""
+    CP, CinP = -(-Cout // 32) * 32, Cin + (Cin & 1)
+    w = torch.zeros(CinP, nsub, CP, **f32)
+    w[:Cin, :, :Cout] = weight.detach().to(**f32).reshape(nsub, Cout, Cin).permute(2, 0, 1)
+    b = torch.zeros(nsub, CP, **f32)
+    b[:, :Cout] = bias.detach().to(**f32).reshape(nsub, Cout)
+    return w.contiguous(), b.contiguous()
 
 
 class GroupCausal3DConvVAE(nn.Module):
@@ -151,9 +181,12 @@ class EncoderDecoder(nn.Module):
 
 
 class VAE(BetterModule):
-    """The reference's VAE (vae.py:207-318) on HIP kernels.  Supported: every decoder width <= 64, time and
-    spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises NotImplementedError
-    here (the Counter-Strike VAE, 512 channels, is out of scope)."""
+    """The reference's VAE (vae.py:207-318) on HIP kernels.  Supported: every decoder width <= 256 with at most 64 latent
+    channels, time and spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises
+    NotImplementedError here.  Blocks of up to 64 channels run on the register-tile kernels (csrc/vae.hip), wider ones on the
+    fp32 MFMA tile kernels (csrc/vae_wide.hip); a model may mix them.  A model with a width above 64 has the decoder only:
+    its encoder and training entry points raise NotImplementedError (the wide encoder, and 512 channels, the full-size
+    Counter-Strike VAE, are out of scope)."""
 
     def __init__(self, channels, n_res_blocks, time_compressions=[1, 2, 2], spatial_compressions=[1, 2, 2], mean=None, std=None):
         super().__init__()
@@ -165,7 +198,11 @@ class VAE(BetterModule):
         if any(int(c) not in (1, 2) for c in list(time_compressions) + list(spatial_compressions)):
             raise NotImplementedError(f"VAE decoder: compressions {list(time_compressions)} / {list(spatial_compressions)}: "
                                       "the HIP kernels take 1 or 2")
+        if channels[-1] > MAX_NARROW:
+            raise NotImplementedError(f"VAE decoder: {channels[-1]} latent channels: the first block reads the strided latents "
+                                      f"on the narrow kernels, which take 1..{MAX_NARROW} channels")
         self.latent_channels = channels[-1]
+        self._wide = max(widths) if max(widths) > MAX_NARROW else 0
         self.encoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="encoder")
         self.decoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="decoder")
         self.time_compression = np.prod(time_compressions)
@@ -193,6 +230,7 @@ class VAE(BetterModule):
         In eval mode or under torch.no_grad() it is encode -> mix -> decode on the inference kernels: real caches are carried
         under cache["encoder"] / cache["decoder"] and the outputs have no grad_fn."""
         self._check_frames("forward", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
+        self._refuse_wide("forward")
         B = x.shape[0]
         if t_sample is not None and (t_sample.dim() != 1 or t_sample.shape[0] != B):
             raise ValueError(f"VAE.forward: t_sample must be ({B},), got {tuple(t_sample.shape)}")
@@ -238,20 +276,26 @@ class VAE(BetterModule):
         with torch.no_grad():
             for i, blk in enumerate(self.decoder.encoder_blocks):
                 C, Cout, g = self.decoder.in_channels[i], self.decoder.out_channels[i], self.decoder.group_sizes[i]
-                nch, gpt = _nch(C), _gpt(C, g)
+                wide = C > MAX_NARROW
+                nch, gpt = (0, 0) if wide else (_nch(C), _gpt(C, g))
                 res = []
                 for rb in blk.res_blocks:
-                    res.append(dict(_pack_res(rb, C, g, f32), emb_off=eoff))
+                    res.append(dict((_pack_res_wide if wide else _pack_res)(rb, C, g, f32), emb_off=eoff))
                     off = sum(x.numel() for x in tparams)
                     tparams += [rb.fourier_cond.freqs.detach().to(**f32), rb.fourier_cond.phases.detach().to(**f32),
                                 rb.t_cond.weight.detach().to(**f32).reshape(-1), rb.t_cond.bias.detach().to(**f32)]
                     table += [off, 2 * C, eoff]
                     eoff += 2 * C
-                blocks.append(dict(C=C, Cout=Cout, g=g, nch=nch, gpt=gpt, tc=blk.time_compression, sc=blk.spatial_compression,
-                                   wu=blk.decompression_block.weight.detach().to(**f32).reshape(-1, C).contiguous(),
-                                   bu=blk.decompression_block.bias.detach().to(**f32).contiguous(),
-                                   wo=blk.final_conv.weight.detach().to(**f32).reshape(Cout, C).contiguous(),
-                                   bo=blk.final_conv.bias.detach().to(**f32).contiguous(), res=res))
+                bk = dict(C=C, Cout=Cout, g=g, nch=nch, gpt=gpt, tc=blk.time_compression, sc=blk.spatial_compression, wide=wide,
+                          wu=blk.decompression_block.weight.detach().to(**f32).reshape(-1, C).contiguous(),
+                          bu=blk.decompression_block.bias.detach().to(**f32).contiguous(),
+                          wo=blk.final_conv.weight.detach().to(**f32).reshape(Cout, C).contiguous(),
+                          bo=blk.final_conv.bias.detach().to(**f32).contiguous(), res=res)
+                if wide:                                             # the 1x1 stages as GEMMs (csrc/vae_wide_conv.h)
+                    bk["wu"], bk["bu"] = _pack_lin_wide(blk.decompression_block.weight, blk.decompression_block.bias, C, C,
+                                                        blk.time_compression * blk.spatial_compression ** 2, f32)
+                    bk["wo"], bk["bo"] = _pack_lin_wide(blk.final_conv.weight, blk.final_conv.bias, C, Cout, 1, f32)
+                blocks.append(bk)
             pk = dict(sig=sig, blocks=blocks, tparams=torch.cat(tparams).contiguous(),
                       table=torch.tensor(table, dtype=torch.int32, device=device), n_rb=len(table) // 3, emb_per_row=eoff,
                       lvm=self.decoder.logvar_multiplier.detach().to(**f32).reshape(1).contiguous())
@@ -272,6 +316,19 @@ class VAE(BetterModule):
                                  f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
             cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=x.device)
             u = torch.empty_like(x)
+            if bk.get("wide"):                                   # act, conv A, act, conv B (csrc/vae_wide.hip)
+                seq = torch.empty(B, g + T, H, W, C, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.lib.oniris_vae_wide_act(_p(x), emb_of(rb), _p(cin), _p(cout), _p(seq), B, T, H, W, C, g, s), "vae_wide_act")
+                _lib.check(_lib.lib.oniris_vae_wide_conv_a(_p(seq), _p(rb["wa"]), _p(rb["ba"]), _p(u), B, T, H, W, C, g, s),
+                           "vae_wide_conv_a")
+                a2 = seq.view(-1)[:x.numel()].view(x.shape)      # S is free again: SiLU(RMS(a)) goes there
+                _lib.check(_lib.lib.oniris_vae_wide_act(_p(u), None, None, None, _p(a2), B, T, H, W, C, 0, s), "vae_wide_act")
+                xn = torch.empty_like(x)
+                _lib.check(_lib.lib.oniris_vae_wide_conv_b(_p(a2), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(xn), B, T, H, W, C, s),
+                           "vae_wide_conv_b")
+                x = xn
+                new_cache[f"res_block_{j}"] = {"conv3d_res0": cout}
+                continue
             _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb_of(rb), _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g,
                                                  bk["nch"], bk["gpt"], _p(u), s), "vae_res_a")
             xn = torch.empty_like(x)
@@ -293,7 +350,11 @@ class VAE(BetterModule):
         t = torch.as_tensor(t, dtype=torch.float32, device=dev)
         t = (t.expand(B) if t.dim() == 0 else t.reshape(B)).contiguous()
         emb = torch.empty(B * pk["emb_per_row"], dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), B, _p(emb), s), "vae_temb")
+        if self._wide:                                           # oniris_vae_temb holds the 2C Fourier features of up to 64 channels
+            _lib.check(_lib.lib.oniris_vae_wide_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], 2 * self._wide, _p(t), B, _p(emb), s),
+                       "vae_wide_temb")
+        else:
+            _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), B, _p(emb), s), "vae_temb")
         cache = {} if cache is None else cache
         new_cache = {}
         scale = shift = None
@@ -307,31 +368,35 @@ class VAE(BetterModule):
         for i, bk in enumerate(pk["blocks"]):
             C, tc, sc = bk["C"], bk["tc"], bk["sc"]
             up = torch.empty(B, T * tc, H * sc, W * sc, C, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]),
-                                              tc, sc, _p(up), s), "vae_up")
+            if bk["wide"]:                                       # never block 0: x is the contiguous output of the block before
+                _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(up), B, T, H, W, C, tc, sc, s), "vae_wide_up")
+            else:
+                _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]),
+                                                  tc, sc, _p(up), s), "vae_up")
             x, T, H, W = up, T * tc, H * sc, W * sc
             scale = shift = None
             x, new_cache[f"encoder_block_{i}"] = self._res_blocks("decoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
                                                                   lambda rb: emb.data_ptr() + 4 * B * rb["emb_off"], s)
             Cout = bk["Cout"]
+            vae_out, what = (_lib.lib.oniris_vae_wide_out, "vae_wide_out") if bk["wide"] else (_lib.lib.oniris_vae_out, "vae_out")
             if i < nblk - 1:
                 y = torch.empty(B, T, H, W, Cout, dtype=torch.float32, device=dev)
-                _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, 0, None, _p(y), None,
-                                                   *y.stride()[:4], 1, None, s), "vae_out")
+                _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, 0, None, _p(y), None, *y.stride()[:4], 1, None, s),
+                           what)
                 x = y
                 strides = y.stride()[:4] + (1,)
                 continue
             half = Cout // 2
             if want == "frames":
                 frames = torch.empty(B, T, H, W, half, dtype=torch.uint8, device=dev)
-                _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]),
-                                                   None, None, 0, 0, 0, 0, 0, _p(frames), s), "vae_out")
+                _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]), None, None, 0, 0, 0, 0, 0,
+                                   _p(frames), s), what)
                 return frames, new_cache
             mean = torch.empty(B, half, T, H, W, dtype=torch.float32, device=dev)
             logvar = torch.empty_like(mean)
             sb, scc, st, sh, sw = mean.stride()
-            _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]),
-                                               _p(mean), _p(logvar), sb, st, sh, sw, scc, None, s), "vae_out")
+            _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]), _p(mean), _p(logvar), sb, st,
+                               sh, sw, scc, None, s), what)
             return (mean, logvar), new_cache
 
     @torch.no_grad()
@@ -413,6 +478,14 @@ class VAE(BetterModule):
             raise ValueError(f"VAE.{what}: frames of {H} x {W}: height and width must be positive multiples of the spatial "
                              f"compression {scomp}")
 
+    def _refuse_wide(self, what):
+        """A model with a decoder block wider than MAX_NARROW has no native encoder: said after the shape checks, before anything
+        is packed or launched, wherever the model lives."""
+        if self._wide:
+            raise NotImplementedError(f"VAE.{what}: this model has a block of {self._wide} channels: above {MAX_NARROW} only the "
+                                      f"decoder (decode, decode_frames, latents_to_frames) runs natively; for the encoder and "
+                                      f"training at that width use {_REF}")
+
     def _encoder_device(self, what, x=None):
         dev = self.device if x is None else x.device
         if dev.type != "cuda" or self.device.type != "cuda":
@@ -459,6 +532,7 @@ class VAE(BetterModule):
         reference's keys cache['encoder_block_{i}']['res_block_{j}']['conv3d_res0'], the last g activated input frames of every
         group-causal conv as opaque channels-last (B, g, H, W, C) fp32 tensors; pass it back to continue the sequence."""
         self._check_frames("encode", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
+        self._refuse_wide("encode")
         self._encoder_device("encode", x)
         x = x.float()
         sb, sc, st, sh, sw = x.stride()
@@ -470,6 +544,7 @@ class VAE(BetterModule):
         mean (vae.py:250-259).  split_size must be a multiple of the time compression."""
         self._check_frames("encode_long_sequence", frames.shape, "frames (B, {c}, T, H, W)",
                            *(frames.shape if frames.dim() == 5 else (None,) * 5))
+        self._refuse_wide("encode_long_sequence")
         if split_size <= 0 or split_size % int(self.time_compression) != 0:
             raise ValueError(f"VAE.encode_long_sequence: split_size {split_size} must be a positive multiple of the time compression "
                              f"{int(self.time_compression)}")
@@ -488,6 +563,7 @@ class VAE(BetterModule):
         latent frame), the result equals frames_to_latents over the whole sequence."""
         B, T, H, W, C = frames.shape if frames.dim() == 5 else (None,) * 5
         self._check_frames("encode_frames", frames.shape, "frames (B, T, H, W, {c})", B, C, T, H, W)
+        self._refuse_wide("encode_frames")
         self._encoder_device("encode_frames", frames)
         if not hasattr(self, "mean"):
             raise RuntimeError("VAE: frames_to_latents needs the `mean` / `std` constructor arguments (as in the reference)")

@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
@@ -631,7 +631,8 @@ int oniris_attn_f32_bwd(const OnirisAttnF32Args* args, oniris_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * VAE decoder (reference: edm2/vae/vae.py EncoderDecoder(type='decoder') :167-204 and VAE.decode / latents_to_frames
- * :253-318), inference, fp32 throughout.  Activations channels-last fp32 [B][T][H][W][C], C <= 64.  csrc/vae.hip; the 3x3
+ * :253-318), inference, fp32 throughout.  Activations channels-last fp32 [B][T][H][W][C], C <= 64 (wider: oniris_vae_wide_*
+ * below).  csrc/vae.hip; the 3x3
  * tile kernel of oniris_vae_res_a / _res_b is csrc/vae_conv3.h.
  * oniris_vae_temb: the FiLM scale | shift of every ResBlock for one decode, emb[r][b][2 C_r] = t_cond(MPFourier(t_b))
  * (vae.py:76-80); table [3 n_res_blocks] int32 = {offset of block r's freqs[2C] | phases[2C] | W[2C][2C] | bias[2C] in params,
@@ -663,6 +664,41 @@ int oniris_vae_res_b(const float* u, const float* res, const float* w, const flo
 int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout, int split,
                    const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc,
                    uint8_t* frames, oniris_stream_t stream);
+
+/* VAE decoder at block widths above 64 channels, added within ABI 14 (nothing above changed).  fp32 throughout, channels-last
+ * [B][T][H][W][C]; the caller allocates every buffer and nothing synchronises.  csrc/vae_wide.hip; the tile kernel is
+ * csrc/vae_wide_conv.h over csrc/disc_parts.h (16x16 pixel tiles on v_mfma_f32_32x32x2_f32).  A wide ResBlock is four launches,
+ * act, conv_a, act, conv_b, and the convs take operands that are ALREADY activated.  In every packed layout CP = the width
+ * rounded up to a multiple of 32, CinP = the input width rounded up to even, and the padding is zero.
+ * oniris_vae_wide_temb: oniris_vae_temb (the same arguments, operations and bits) for ResBlocks of any width; max_c2 = the largest
+ *   2 C_r in the table.  oniris_vae_temb itself holds 128 Fourier features, that is, widths up to 64.
+ * oniris_vae_wide_act: y = SiLU(RMS(x) (1 + scale) + shift), RMS(x) = x / sqrt(mean_c x^2 + 1e-4); emb = [B][2C] scale | shift or
+ *   NULL (plain SiLU(RMS(x))).  g >= 1: S = [B][g + T][H][W][C]; frames g.. receive y, frames 0 .. g - 1 the prefix = cache_in
+ *   [B][g][H][W][C] or, when NULL, the first g frames of y; cache_out (a different buffer) receives the last g frames of S;
+ *   T % g == 0.  g = 0: S = [B][T][H][W][C] receives y, no cache.  The sum of squares runs in an order that depends on C alone.
+ * oniris_vae_wide_conv_a: the group-causal (2g, 3, 3) conv C -> C g with stride g in time (vae.py:18-53) and '(c g) t -> c (t g)':
+ *   out[b, tau g + gl, y, x, c] = bias[gl][c] + sum_{kt < 2g, ky, kx, ci} w[kt 9 + ky 3 + kx][ci][gl CP + c] S[b, tau g + kt, y + ky
+ *   - 1, x + kx - 1, ci], zero outside the image; w packed [2g 9][CinP][g CP] (conv channel c g + gl at gl CP + c), bias [g][CP].
+ * oniris_vae_wide_conv_b: out = res + bias + conv3x3(u); w packed [9][CinP][CP], bias [CP].
+ * oniris_vae_wide_up: the decompression 1x1 conv C -> C tc sc^2 written to out [B][T tc][H sc][W sc][C] (vae.py:96-133,
+ *   :148-164); x contiguous [B][T][H][W][C]; w packed [CinP][tc sc^2 CP] (conv channel sub C + c at sub CP + c, sub = (tq sc + hq)
+ *   sc + wq), bias [tc sc^2][CP].
+ * oniris_vae_wide_out: oniris_vae_out for Cin above 64, same arguments, except w packed [CinP][CP of Cout], bias [CP].
+ * Every output is summed in the order time tap, 16-channel chunk, spatial tap, channel pair, then the bias and the residual; it
+ * depends on neither T, nor B, nor where the sequence was cut.                                                                 */
+int oniris_vae_wide_temb(const float* params, const int32_t* table, int n_res_blocks, int max_c2, const float* t, int B, float* emb,
+                         oniris_stream_t stream);
+int oniris_vae_wide_act(const float* x, const float* emb, const float* cache_in, float* cache_out, float* S, int B, int T, int H,
+                        int W, int C, int g, oniris_stream_t stream);
+int oniris_vae_wide_conv_a(const float* S, const float* w, const float* bias, float* out, int B, int T, int H, int W, int C, int g,
+                           oniris_stream_t stream);
+int oniris_vae_wide_conv_b(const float* u, const float* res, const float* w, const float* bias, float* out, int B, int T, int H,
+                           int W, int C, oniris_stream_t stream);
+int oniris_vae_wide_up(const float* x, const float* w, const float* bias, float* out, int B, int T, int H, int W, int C, int tcomp,
+                       int scomp, oniris_stream_t stream);
+int oniris_vae_wide_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout, int split,
+                        const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw,
+                        int64_t sc, uint8_t* frames, oniris_stream_t stream);
 
 /* VAE encoder (reference: EncoderDecoder(type='encoder') vae.py:96-204, VAE.encode :239-241), inference, fp32 throughout.
  * csrc/vae_encoder.hip.  Its ResBlocks are oniris_vae_res_a / oniris_vae_res_b with a zero emb buffer (the encoder passes
