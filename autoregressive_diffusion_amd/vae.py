@@ -41,6 +41,13 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _slab_sum(slab, n):
+    """oniris_vae_slab_sum_bwd: the partial slabs slab[i] of n floats each -> their sum (n,), added in the order of i."""
+    out = torch.empty(n, dtype=torch.float32, device=slab.device)
+    _lib.check(_lib.lib.oniris_vae_slab_sum_bwd(_p(slab), slab.shape[0], n, _p(out), _stream()), "vae_slab_sum_bwd")
+    return out
+
+
 def _has_tensor(cache):
     """Whether a (nested) cache dict holds anything but None leaves."""
     if isinstance(cache, dict):
@@ -107,6 +114,140 @@ def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
     b = torch.zeros(nsub, CP, **f32)
     b[:, :Cout] = bias.detach().to(**f32).reshape(nsub, Cout)
     return w.contiguous(), b.contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# launches: thin wrappers, one per entry point, on channels-last fp32 tensors (B, T, H, W, C) of the GPU.  bk: a packed block
+# (VAE._pack, VAE._pack_encoder), rb: one of its packed ResBlocks, pk: the decoder's pack, dims: the coarse grid (B, T, H, W),
+# strides: element strides (b, t, h, w, c) of an operand in any layout, s: the stream.  Each allocates what it writes and returns it.
+
+def _new(x, *shape, dtype=torch.float32):
+    return torch.empty(*shape, dtype=dtype, device=x.device)
+
+
+def temb(pk, t, s):
+    """oniris_vae_temb: t (B,) -> the FiLM scale | shift of every ResBlock, [ResBlock][B][2C] flat."""
+    emb = _new(t, t.shape[0] * pk["emb_per_row"])
+    _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), t.shape[0], _p(emb), s), "vae_temb")
+    return emb
+
+
+def wide_temb(pk, width, t, s):
+    """oniris_vae_wide_temb: as temb, for a model whose widest block has `width` channels (temb holds the Fourier features of 64)."""
+    emb = _new(t, t.shape[0] * pk["emb_per_row"])
+    _lib.check(_lib.lib.oniris_vae_wide_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], 2 * width, _p(t), t.shape[0], _p(emb), s),
+               "vae_wide_temb")
+    return emb
+
+
+def up(x, strides, dims, bk, s, scale=None, shift=None):
+    """oniris_vae_up: x over `dims` by `strides` (times scale plus shift per channel) -> (B, T tc, H sc, W sc, C)."""
+    B, T, H, W = dims
+    C, tc, sc = bk["C"], bk["tc"], bk["sc"]
+    y = _new(x, B, T * tc, H * sc, W * sc, C)
+    _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]), tc, sc, _p(y),
+                                      s), "vae_up")
+    return y
+
+
+def wide_up(x, bk, s):
+    """oniris_vae_wide_up: contiguous x (B, T, H, W, C) -> (B, T tc, H sc, W sc, C)."""
+    B, T, H, W, C = x.shape
+    tc, sc = bk["tc"], bk["sc"]
+    y = _new(x, B, T * tc, H * sc, W * sc, C)
+    _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(y), B, T, H, W, C, tc, sc, s), "vae_wide_up")
+    return y
+
+
+def res_a(x, cin, emb, rb, bk, s):
+    """oniris_vae_res_a: x, the cache entry cin or None, the address emb of the FiLM scale | shift -> (u, the new cache entry)."""
+    B, T, H, W, C = x.shape
+    cout, u = _new(x, B, bk["g"], H, W, C), torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb, _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, bk["g"], bk["nch"],
+                                         bk["gpt"], _p(u), s), "vae_res_a")
+    return u, cout
+
+
+def res_b(u, x, rb, bk, s):
+    """oniris_vae_res_b: -> x + conv B(u)."""
+    B, T, H, W, C = x.shape
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(y), s), "vae_res_b")
+    return y
+
+
+def wide_act(x, s, emb=None, cin=None, g=0, out=None):
+    """oniris_vae_wide_act: the activation of x (with FiLM where emb is an address), behind the g cached frames cin where g > 0
+    -> (the sequence (B, g + T, H, W, C), written to `out` where given, the new cache entry or None)."""
+    B, T, H, W, C = x.shape
+    cout = _new(x, B, g, H, W, C) if g else None
+    out = _new(x, B, g + T, H, W, C) if out is None else out
+    _lib.check(_lib.lib.oniris_vae_wide_act(_p(x), emb, _p(cin), _p(cout), _p(out), B, T, H, W, C, g, s), "vae_wide_act")
+    return out, cout
+
+
+def wide_conv_a(seq, rb, g, s):
+    """oniris_vae_wide_conv_a: the sequence (B, g + T, H, W, C) -> u (B, T, H, W, C)."""
+    B, T, H, W, C = seq.shape[0], seq.shape[1] - g, *seq.shape[2:]
+    u = _new(seq, B, T, H, W, C)
+    _lib.check(_lib.lib.oniris_vae_wide_conv_a(_p(seq), _p(rb["wa"]), _p(rb["ba"]), _p(u), B, T, H, W, C, g, s), "vae_wide_conv_a")
+    return u
+
+
+def wide_conv_b(a, x, rb, s):
+    """oniris_vae_wide_conv_b: -> x + conv B(a)."""
+    B, T, H, W, C = x.shape
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_wide_conv_b(_p(a), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(y), B, T, H, W, C, s), "vae_wide_conv_b")
+    return y
+
+
+def out(x, bk, s, lvm=None, want="next"):
+    """oniris_vae_out, or oniris_vae_wide_out where bk["wide"]: x (B, T, H, W, C) -> by `want` "next": the next block's input
+    (B, T, H, W, Cout); "moments": (mean, logvar), each (B, Cout / 2, T, H, W); "frames": uint8 (B, T, H, W, Cout / 2).  lvm: the
+    logvar multiplier, for the last two."""
+    B, T, H, W, C = x.shape
+    Cout = bk["Cout"]
+    half = 0 if want == "next" else Cout // 2
+    y = mean = logvar = frames = None
+    if want == "next":
+        y = _new(x, B, T, H, W, Cout)
+        strides = y.stride()[:4] + (1,)
+    elif want == "frames":
+        frames = _new(x, B, T, H, W, half, dtype=torch.uint8)
+        strides = (0, 0, 0, 0, 0)
+    else:
+        mean = _new(x, B, half, T, H, W)
+        logvar = torch.empty_like(mean)
+        sb, sc, st, sh, sw = mean.stride()
+        strides = (sb, st, sh, sw, sc)
+    entry, what = (_lib.lib.oniris_vae_wide_out, "vae_wide_out") if bk["wide"] else (_lib.lib.oniris_vae_out, "vae_out")
+    _lib.check(entry(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(lvm), _p(y if want == "next" else mean),
+                     _p(logvar), *strides, _p(frames), s), what)
+    return y if want == "next" else frames if want == "frames" else (mean, logvar)
+
+
+def down(x, strides, dims, normalize, bk, s):
+    """oniris_vae_down: fp32 or uint8 frames x by `strides` (normalize: x / 127.5 - 1 on load) -> (B, T, H, W, C) over `dims`."""
+    B, T, H, W = dims
+    y = _new(x, B, T, H, W, bk["C"])
+    _lib.check(_lib.lib.oniris_vae_down(_p(x), int(x.dtype == torch.uint8), *strides, B, T, H, W, bk["Cin"], bk["tc"], bk["sc"],
+                                        int(normalize), _p(bk["wd"]), _p(bk["bd"]), bk["C"], _p(y), s), "vae_down")
+    return y
+
+
+def latents(x, s, mean=None, std=None):
+    """oniris_vae_latents: x (B, T, H, W, C) -> the mean (B, C, T, H, W), or, with mean and std, the normalised latents
+    (B, T, C, H, W)."""
+    B, T, H, W, C = x.shape
+    if mean is None:
+        y = _new(x, B, C, T, H, W)
+        sb, sc, st, sh, sw = y.stride()
+    else:
+        y = _new(x, B, T, C, H, W)
+        sb, st, sc, sh, sw = y.stride()
+    _lib.check(_lib.lib.oniris_vae_latents(_p(x), B, T, H, W, C, _p(mean), _p(std), _p(y), sb, st, sh, sw, sc, s), "vae_latents")
+    return y
 
 
 class GroupCausal3DConvVAE(nn.Module):
@@ -314,27 +455,14 @@ class VAE(BetterModule):
             if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != x.device or cin.dtype != torch.float32):
                 raise ValueError(f"VAE {side} cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
                                  f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
-            cout = torch.empty(B, g, H, W, C, dtype=torch.float32, device=x.device)
-            u = torch.empty_like(x)
             if bk.get("wide"):                                   # act, conv A, act, conv B (csrc/vae_wide.hip)
-                seq = torch.empty(B, g + T, H, W, C, dtype=torch.float32, device=x.device)
-                _lib.check(_lib.lib.oniris_vae_wide_act(_p(x), emb_of(rb), _p(cin), _p(cout), _p(seq), B, T, H, W, C, g, s), "vae_wide_act")
-                _lib.check(_lib.lib.oniris_vae_wide_conv_a(_p(seq), _p(rb["wa"]), _p(rb["ba"]), _p(u), B, T, H, W, C, g, s),
-                           "vae_wide_conv_a")
-                a2 = seq.view(-1)[:x.numel()].view(x.shape)      # S is free again: SiLU(RMS(a)) goes there
-                _lib.check(_lib.lib.oniris_vae_wide_act(_p(u), None, None, None, _p(a2), B, T, H, W, C, 0, s), "vae_wide_act")
-                xn = torch.empty_like(x)
-                _lib.check(_lib.lib.oniris_vae_wide_conv_b(_p(a2), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(xn), B, T, H, W, C, s),
-                           "vae_wide_conv_b")
-                x = xn
-                new_cache[f"res_block_{j}"] = {"conv3d_res0": cout}
-                continue
-            _lib.check(_lib.lib.oniris_vae_res_a(_p(x), _p(cin), _p(cout), emb_of(rb), _p(rb["wa"]), _p(rb["ba"]), B, T, H, W, C, g,
-                                                 bk["nch"], bk["gpt"], _p(u), s), "vae_res_a")
-            xn = torch.empty_like(x)
-            _lib.check(_lib.lib.oniris_vae_res_b(_p(u), _p(x), _p(rb["wb"]), _p(rb["bb"]), B, T, H, W, C, bk["nch"], _p(xn), s),
-                       "vae_res_b")
-            x = xn
+                seq, cout = wide_act(x, s, emb_of(rb), cin, g)
+                u = wide_conv_a(seq, rb, g, s)
+                a2, _ = wide_act(u, s, out=seq.view(-1)[:x.numel()].view(x.shape))    # S is free again: SiLU(RMS(a)) goes there
+                x = wide_conv_b(a2, x, rb, s)
+            else:
+                u, cout = res_a(x, cin, emb_of(rb), rb, bk, s)
+                x = res_b(u, x, rb, bk, s)
             new_cache[f"res_block_{j}"] = {"conv3d_res0": cout}
         return x, new_cache
 
@@ -349,12 +477,8 @@ class VAE(BetterModule):
         s = _stream()
         t = torch.as_tensor(t, dtype=torch.float32, device=dev)
         t = (t.expand(B) if t.dim() == 0 else t.reshape(B)).contiguous()
-        emb = torch.empty(B * pk["emb_per_row"], dtype=torch.float32, device=dev)
-        if self._wide:                                           # oniris_vae_temb holds the 2C Fourier features of up to 64 channels
-            _lib.check(_lib.lib.oniris_vae_wide_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], 2 * self._wide, _p(t), B, _p(emb), s),
-                       "vae_wide_temb")
-        else:
-            _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), B, _p(emb), s), "vae_temb")
+        # oniris_vae_temb holds the 2C Fourier features of up to 64 channels
+        emb = wide_temb(pk, self._wide, t, s) if self._wide else temb(pk, t, s)
         cache = {} if cache is None else cache
         new_cache = {}
         scale = shift = None
@@ -366,38 +490,17 @@ class VAE(BetterModule):
         H, W = h, w_
         nblk = len(pk["blocks"])
         for i, bk in enumerate(pk["blocks"]):
-            C, tc, sc = bk["C"], bk["tc"], bk["sc"]
-            up = torch.empty(B, T * tc, H * sc, W * sc, C, dtype=torch.float32, device=dev)
-            if bk["wide"]:                                       # never block 0: x is the contiguous output of the block before
-                _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(up), B, T, H, W, C, tc, sc, s), "vae_wide_up")
-            else:
-                _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]),
-                                                  tc, sc, _p(up), s), "vae_up")
-            x, T, H, W = up, T * tc, H * sc, W * sc
+            # a wide block is never block 0: its x is the contiguous output of the block before
+            x = wide_up(x, bk, s) if bk["wide"] else up(x, strides, (B, T, H, W), bk, s, scale, shift)
+            T, H, W = x.shape[1:4]
             scale = shift = None
             x, new_cache[f"encoder_block_{i}"] = self._res_blocks("decoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
                                                                   lambda rb: emb.data_ptr() + 4 * B * rb["emb_off"], s)
-            Cout = bk["Cout"]
-            vae_out, what = (_lib.lib.oniris_vae_wide_out, "vae_wide_out") if bk["wide"] else (_lib.lib.oniris_vae_out, "vae_out")
             if i < nblk - 1:
-                y = torch.empty(B, T, H, W, Cout, dtype=torch.float32, device=dev)
-                _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, 0, None, _p(y), None, *y.stride()[:4], 1, None, s),
-                           what)
-                x = y
-                strides = y.stride()[:4] + (1,)
-                continue
-            half = Cout // 2
-            if want == "frames":
-                frames = torch.empty(B, T, H, W, half, dtype=torch.uint8, device=dev)
-                _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]), None, None, 0, 0, 0, 0, 0,
-                                   _p(frames), s), what)
-                return frames, new_cache
-            mean = torch.empty(B, half, T, H, W, dtype=torch.float32, device=dev)
-            logvar = torch.empty_like(mean)
-            sb, scc, st, sh, sw = mean.stride()
-            _lib.check(vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(pk["lvm"]), _p(mean), _p(logvar), sb, st,
-                               sh, sw, scc, None, s), what)
-            return (mean, logvar), new_cache
+                x = out(x, bk, s)
+                strides = x.stride()[:4] + (1,)
+            else:
+                return out(x, bk, s, pk["lvm"], want), new_cache
 
     @torch.no_grad()
     def decode(self, z, t, cache=None):
@@ -504,27 +607,16 @@ class VAE(BetterModule):
             zeros = pk["zeros"][B] = torch.zeros(B * 2 * MAX_WIDTH, dtype=torch.float32, device=dev)
         cache = {} if cache is None else cache
         new_cache = {}
-        u8 = x.dtype == torch.uint8
         for i, bk in enumerate(pk["blocks"]):
-            C, tc, sc = bk["C"], bk["tc"], bk["sc"]
-            T, H, W = T // tc, H // sc, W // sc
-            y = torch.empty(B, T, H, W, C, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.oniris_vae_down(_p(x), int(u8), *strides, B, T, H, W, bk["Cin"], tc, sc, int(normalize), _p(bk["wd"]),
-                                                _p(bk["bd"]), C, _p(y), s), "vae_down")
-            x, strides, u8, normalize = y, y.stride()[:4] + (1,), False, False
+            T, H, W = T // bk["tc"], H // bk["sc"], W // bk["sc"]
+            x = down(x, strides, (B, T, H, W), normalize, bk, s)
+            strides, normalize = x.stride()[:4] + (1,), False
             x, new_cache[f"encoder_block_{i}"] = self._res_blocks("encoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
                                                                   lambda rb: _p(zeros), s)
         if want == "latents":
-            out = torch.empty(B, T, C, H, W, dtype=torch.float32, device=dev)
-            sb, st, scc, sh, sw = out.stride()
-            mean = self.mean.to(device=dev, dtype=torch.float32).contiguous()
-            std = self.std.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            out = torch.empty(B, C, T, H, W, dtype=torch.float32, device=dev)
-            sb, scc, st, sh, sw = out.stride()
-            mean = std = None
-        _lib.check(_lib.lib.oniris_vae_latents(_p(x), B, T, H, W, C, _p(mean), _p(std), _p(out), sb, st, sh, sw, scc, s), "vae_latents")
-        return out, new_cache
+            return latents(x, s, self.mean.to(device=dev, dtype=torch.float32).contiguous(),
+                           self.std.to(device=dev, dtype=torch.float32).contiguous()), new_cache
+        return latents(x, s), new_cache
 
     @torch.no_grad()
     def encode(self, x, cache=None):

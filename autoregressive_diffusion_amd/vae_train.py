@@ -9,8 +9,8 @@ oniris_vae_train_*, oniris_vae_*_bwd).
 Gradients are summed in a fixed order into a bounded number of partial slabs and then over the slabs; nothing uses atomics."""
 import torch
 
-from . import _lib
-from .vae import _area_windows, _gpt, _nch, _p, _stream
+from . import _lib, vae as V
+from .vae import _area_windows, _gpt, _nch, _p, _slab_sum, _stream
 
 _SLAB_BYTES = 64 << 20          # the most memory one launch's partial slabs may take
 _area_cache = {}
@@ -31,12 +31,6 @@ def _area(K, N, device):
             m[o, s0:s1] = 1.0 / (s1 - s0)
         m = _area_cache[key] = m.to(device)
     return m
-
-
-def _slab_sum(slab, n):
-    out = torch.empty(n, dtype=torch.float32, device=slab.device)
-    _lib.check(_lib.lib.oniris_vae_slab_sum_bwd(_p(slab), slab.shape[0], n, _p(out), _stream()), "vae_slab_sum_bwd")
-    return out
 
 
 def _lin_dw(x, vx, dy, vy, grid):
@@ -65,9 +59,7 @@ class Down(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, bk):
         B, T, H, W = x.shape[0], x.shape[1] // bk["tc"], x.shape[2] // bk["sc"], x.shape[3] // bk["sc"]
-        y = torch.empty(B, T, H, W, bk["C"], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib.oniris_vae_down(_p(x), 0, *x.stride(), B, T, H, W, bk["Cin"], bk["tc"], bk["sc"], 0, _p(bk["wd"]),
-                                            _p(bk["bd"]), bk["C"], _p(y), _stream()), "vae_down")
+        y = V.down(x, x.stride(), (B, T, H, W), False, bk, _stream())
         ctx.save_for_backward(x, weight)
         ctx.bk, ctx.grid = bk, (B, T, H, W)
         return y
@@ -93,9 +85,7 @@ class Up(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, bk):
         B, T, H, W, C = x.shape
-        up = torch.empty(B, T * bk["tc"], H * bk["sc"], W * bk["sc"], C, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib.oniris_vae_up(_p(x), *x.stride(), B, T, H, W, C, None, None, _p(bk["wu"]), _p(bk["bu"]), bk["tc"],
-                                          bk["sc"], _p(up), _stream()), "vae_up")
+        up = V.up(x, x.stride(), (B, T, H, W), bk, _stream())
         ctx.save_for_backward(x, weight)
         ctx.bk, ctx.grid = bk, (B, T, H, W)
         return up
@@ -121,22 +111,12 @@ class Out(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, lvm, bk, lvm32):
-        B, T, H, W, C = x.shape
-        Cout = bk["Cout"]
-        ctx.bk, ctx.grid, ctx.last = bk, (B, T, H, W), lvm is not None
-        s = _stream()
+        ctx.bk, ctx.grid, ctx.last = bk, tuple(x.shape[:4]), lvm is not None
         if lvm is None:
-            y = torch.empty(B, T, H, W, Cout, dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, 0, None, _p(y), None,
-                                               *y.stride()[:4], 1, None, s), "vae_out")
+            y = V.out(x, bk, _stream())
             ctx.save_for_backward(x, weight)
             return y
-        half = Cout // 2
-        mean = torch.empty(B, half, T, H, W, dtype=torch.float32, device=x.device)
-        logvar = torch.empty_like(mean)
-        sb, scc, st, sh, sw = mean.stride()
-        _lib.check(_lib.lib.oniris_vae_out(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(lvm32), _p(mean),
-                                           _p(logvar), sb, st, sh, sw, scc, None, s), "vae_out")
+        mean, logvar = V.out(x, bk, _stream(), lvm32, "moments")
         ctx.save_for_backward(x, weight, lvm, logvar)
         return mean, logvar
 
