@@ -42,7 +42,7 @@ clean:
 
 # experiment builds of the gated-conv translation unit with other -D settings (VNAME / VDEF), e.g.
 #   make variant VNAME=m816 VDEF="-DGLDS_MID_OWN=8 -DGLDS_MID_CTX=16"   -> autoregressive_diffusion_amd/liboniris_hip_m816.so
-#   make variant VSRC=conv_wgrad VNAME=wro0 VDEF="-DWGRAD_ROWORDER=0"     (another translation unit: VSRC, default conv_fwd_s2ctx)
+#   make variant VSRC=conv_wgrad VNAME=ph8 VDEF="-DWGRAD_STREAM_PH=8"      (another translation unit: VSRC, default conv_fwd_s2ctx)
 VSRC ?= conv_fwd_s2ctx
 variant: $(OBJS)
 	$(HIPCC) $(HIPFLAGS) $(VDEF) -c $(CSRC)/$(VSRC).hip -o build/$(VSRC)_$(VNAME).o

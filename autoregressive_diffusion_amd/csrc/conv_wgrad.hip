@@ -4,33 +4,32 @@
 // row-major ([position][channel]) in LDS and the k-contiguous MFMA fragments are produced by the gfx950
 // transposing LDS read ds_read_b64_tr_b16 (4 rows x 16 columns per 16-lane group).  The x tile is the halo image
 // of the patch, shared by the 9 taps.  A workgroup owns a (32*CT co) x (32*IT ci) x 9-tap output tile and walks
-// a strided subset of the position tiles (split-K) and writes its partial sums to ITS OWN fp32 slab with plain stores
-// (two 128-byte row segments per wave store); the slabs are summed by weight_bwd_kernel.  The first version used
+// a strided subset of the position tiles (split-K) and writes its partial sums to ITS OWN bf16 slab with plain stores
+// (two 64-byte row segments per wave store); the slabs are summed by weight_bwd_kernel.  The first version used
 // fp32 atomics, which run at ~1.3 TB/s chip-wide and took about half of the kernel time.
+// What the four kernels of this translation unit have in common is in wgrad_parts.h.
 #include "conv_kernels.h"
 
-// Up to three sub-problems of identical geometry (H, W, channels, taps) share one launch: the own-frame weight and the
-// two context taps of a gated conv.  Workgroup columns [gstart[g], gstart[g+1]) belong to group g; every column
-// writes ONE slab, so one launch writes as many slabs as three separate ones used to write each.
-#define WGRAD_MAXG 3
-struct WgradDev {
-  OnirisWgradArgs a[WGRAD_MAXG];
-  int ntiles[WGRAD_MAXG], ntt[WGRAD_MAXG], gstart[WGRAD_MAXG + 1];
-  int ntx, nty, ncib;
-};
+// ---- build-time A/B settings of the family (make variant VSRC=conv_wgrad VNAME=... VDEF=-D...)
+#ifndef WGRAD_NG
+// K-groups of 4 waves per workgroup of the LDS-DMA kernel.  1 (round 5): two independent 4-wave workgroups per CU instead of one workgroup of
+// two K-groups -- the same waves, registers and LDS per CU, but no common barrier: the groups drift apart, and one's copy issue, waits and
+// fragment prologue run under the other's MFMAs (a K-group pair in lockstep had both of a SIMD's waves in the same part of the tile loop at
+// any time).  Same-box A/B at B = 8: <2,2,*,16> 25.4 -> 22.4 ms per cycle (roof 0.41 -> 0.47), <2,2,*,8> 9.3 -> 8.5 ms, bench +1.3 %
+// (profiles/r05_ab_wgrad_groups.txt); costs twice the split-K slabs of the 64x64-channel form (ops._nsplit_cap).
+#define WGRAD_NG 1
+#endif
+#ifndef WGRAD_NG1
+#define WGRAD_NG1 1                          // ... of the 32x32-channel tile form (+0.15 %)
+#endif
+#ifndef WGRAD1X1_NG
+#define WGRAD1X1_NG 2                        // K-groups per workgroup of wgrad1x1_glds_kernel (1: two 4-wave workgroups per CU; A/B)
+#endif
+#ifndef WGRAD_STREAM_PH
+#define WGRAD_STREAM_PH 4                    // 8: conv_wgrad_stream_kernel always in the 8x16-pixel form (A/B: -DWGRAD_STREAM_PH=8)
+#endif
 
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base0, const unsigned char* base1) {
-  // two transposing reads -> 8 k-contiguous bf16 for this lane's channel
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)base1);
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
+#include "wgrad_parts.h"
 #include "conv_wgrad_glds.h"
 #include "conv_wgrad_stream.h"
 #include "wgrad1x1_glds.h"
@@ -48,18 +47,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradDev d) {
   unsigned char* dy_lds = smem;
   unsigned char* x_lds = smem + 128 * DY_ROWB;
 
+  // group select and channel block: wgrad_group()'s lines, kept here -- through the helper this kernel re-derives &d.a[gsel] at every
+  // field it reads inside the tile loop, and <1,16,1,1> ran 1.5 % slower (profiles/wgrad_shared_parts.txt)
   int gsel = 0;
   if ((int)blockIdx.x >= d.gstart[1]) gsel = 1;
   if ((int)blockIdx.x >= d.gstart[2]) gsel = 2;
   const OnirisWgradArgs& a = d.a[gsel];
   const int bx = blockIdx.x - d.gstart[gsel], gxg = d.gstart[gsel + 1] - d.gstart[gsel];
   const int g_ntiles = d.ntiles[gsel], g_ntt = d.ntt[gsel];
+  const int cib = blockIdx.y % d.ncib, cob = blockIdx.y / d.ncib;
+  const int co0 = cob * 32 * CT, ci0 = cib * 32 * IT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = a.H, W = a.W, T = a.T, HWp = H * W;
   const int my_tile = wave % NTILE, my_ks = wave / NTILE;
   const int ct = my_tile % CT, it = my_tile / CT;
-  const int cib = blockIdx.y % d.ncib, cob = blockIdx.y / d.ncib;
-  const int co0 = cob * 32 * CT, ci0 = cib * 32 * IT;
 
   f32x16 acc[TAPS];
 #pragma unroll
@@ -69,8 +70,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradDev d) {
 
   const bf16* xg = (const bf16*)a.x;
   const bf16* dyg = (const bf16*)a.dy;
-  // lane roles for the transposing reads
-  const int grp = lane >> 4, hh = grp >> 1, q = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
+  const WgradLane ln = wgrad_lane(lane);                 // lane roles for the transposing reads
+  const int hh = ln.hh, q = ln.q;
+  const int dcol = ct * 64 + ln.cslot, xcol = it * 64 + ln.cslot;     // the lane's byte column in a dy / x row
 
   // Software pipeline (issue early / write late): the global loads of the NEXT position tile are issued into
   // registers before the MFMA section of the current one.
@@ -145,12 +147,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradDev d) {
     for (int i = 0; i < DNI; ++i) {
       const int e = tid + i * 256;
       u32x4 o = rd[i];
-      if (a.scale) {                          // per-frame coefficient folded into dy (bf16 rounding, like a dy2 tensor)
-        bf16x8 bv = __builtin_bit_cast(bf16x8, o);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) bv[k] = f2bf(bf2f(bv[k]) * rsc[i]);
-        o = __builtin_bit_cast(u32x4, bv);
-      }
+      if (a.scale) o = __builtin_bit_cast(u32x4, wgrad_fold(__builtin_bit_cast(bf16x8, o), rsc[i]));
       *(u32x4*)(dy_lds + (e / DPARTS) * DY_ROWB + (e % DPARTS) * 16) = o;
     }
 #pragma unroll
@@ -166,18 +163,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradDev d) {
     store_tile();
     __syncthreads();
     if (tile + gxg < g_ntiles) load_tile(tile + gxg);
-    // ---- MFMA: k = 16 positions per step; (k-step, tap) pairs form one flat sequence whose fragment reads run one
-    // step ahead of the MFMAs (double-buffered registers, order pinned with sched_group_barrier)
+    // ---- MFMA: the flat (k-step, tap) sequence; the waves that share a tile deal its k-steps among themselves
     {
-      constexpr int NK = 8 / NKS, NSTEP = NK * TAPS;
-      bf16x8 af[4], bfm[4];                               // rings: the lookahead (<= 3 steps) never laps a live fragment
-      auto ld_a = [&](int kb, int ksi) __attribute__((always_inline)) {
+      constexpr int NK = 8 / NKS;
+      auto ld_a = [&](int ksi) __attribute__((always_inline)) {
         const int ks = ksi * NKS + my_ks;
         const int p0 = ks * 16 + 8 * hh + q, p1 = p0 + 4;
-        af[kb] = tr_frag(dy_lds + p0 * DY_ROWB + (ct * 32 + pcol) * 2, dy_lds + p1 * DY_ROWB + (ct * 32 + pcol) * 2);
+        return tr_frag(dy_lds + p0 * DY_ROWB + dcol, dy_lds + p1 * DY_ROWB + dcol);
       };
-      auto ld_b = [&](int fb, int st) __attribute__((always_inline)) {
-        const int ksi = st / TAPS, tap = st % TAPS;
+      auto ld_b = [&](int ksi, int tap) __attribute__((always_inline)) {
         const int ks = ksi * NKS + my_ks;
         const int p0 = ks * 16 + 8 * hh + q, p1 = p0 + 4;
         int r0 = p0, r1 = p1;
@@ -186,71 +180,21 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradDev d) {
           r1 = ((p1 / (P::PH * P::PW)) * P::HH + (p1 / P::PW) % P::PH) * P::HW + p1 % P::PW;
         }
         const int off = (TAPS == 9) ? ((tap / 3) * P::HW + (tap % 3)) : 0;
-        bfm[fb] = tr_frag(x_lds + (r0 + off) * X_ROWB + (it * 32 + pcol) * 2, x_lds + (r1 + off) * X_ROWB + (it * 32 + pcol) * 2);
+        return tr_frag(x_lds + (r0 + off) * X_ROWB + xcol, x_lds + (r1 + off) * X_ROWB + xcol);
       };
-      constexpr int LA = (NSTEP > 3) ? 3 : 1;            // fragment reads run LA MFMAs ahead (one wave per SIMD: the
-      constexpr int NA0 = (LA + TAPS - 1) / TAPS;         // wave has to cover the LDS latency by itself)
-#pragma unroll
-      for (int j = 0; j < LA; ++j) {
-        if (j % TAPS == 0) ld_a((j / TAPS) & 3, j / TAPS);
-        ld_b(j, j);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NA0 + 2 * LA, 0);
-#pragma unroll
-      for (int st = 0; st < NSTEP; ++st) {
-        const int ksi = st / TAPS, tap = st % TAPS;
-        const int nx = st + LA;
-        if (nx < NSTEP) {
-          if (nx % TAPS == 0) ld_a((nx / TAPS) & 3, nx / TAPS);
-          ld_b(nx & 3, nx);
-        }
-        acc[tap] = mfma32(af[ksi & 3], bfm[st & 3], acc[tap]);
-        if (nx < NSTEP) {
-          if (nx % TAPS == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
+      wgrad_flat_loop<TAPS, NK>(acc, ld_a, ld_b);
     }
     __syncthreads();
   }
 
-  // ---- write this workgroup column's slab  dwp[blockIdx.x][tap0 + tap][co][ci]
-  // When several waves of the workgroup share one output tile (NKS > 1) they are first summed through LDS.
-  if (bx == 0 && blockIdx.y == 0 && tid == 0 && a.nsplit_out) *a.nsplit_out = gxg;
-  const int cj = ci0 + it * 32 + (lane & 31);
-  if constexpr (NKS > 1) {
-    float* red = (float*)smem;                               // [NKS-1][16][64] floats = 12 KB, staging LDS is free now
+  // ---- write this workgroup column's slab.  When several waves of the workgroup share one output tile (NKS > 1) they are
+  // first summed through LDS ([NKS-1][16][64] floats = 12 KB).
+  wgrad_report_nsplit(a.nsplit_out, bx, gxg);
+  if (!wgrad_meet<TAPS, NKS, NTILE>((float*)smem, acc, my_ks, my_tile, lane)) return;
+  bf16* slab = wgrad_slab(a.dwp, bx, a.taps_total, a.CoutP, a.CinP);
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      __syncthreads();
-      if (my_ks > 0) {
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) red[((my_ks - 1) * 16 + rr) * 64 + lane] = acc[tap][rr];
-      }
-      __syncthreads();
-      if (my_ks == 0) {
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          float v = acc[tap][rr];
-#pragma unroll
-          for (int w = 0; w < NKS - 1; ++w) v += red[(w * 16 + rr) * 64 + lane];
-          acc[tap][rr] = v;
-        }
-      }
-    }
-    if (my_ks != 0) return;
-  }
-  bf16* slab = (bf16*)a.dwp + (size_t)bx * a.taps_total * a.CoutP * a.CinP;
-#pragma unroll
-  for (int tap = 0; tap < TAPS; ++tap) {
-    bf16* base = slab + (size_t)(a.tap0 + tap) * a.CinP;               // slab layout [co][tap][ci]: a weight row is contiguous
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {
-      const int co = co0 + ct * 32 + mfma_row(rr, lane);
-      if (co < a.CoutP && cj < a.CinP) base[(size_t)co * a.taps_total * a.CinP + cj] = f2bf(acc[tap][rr]);
-    }
-  }
+  for (int tap = 0; tap < TAPS; ++tap)
+    wgrad_store_tile(slab, a.tap0 + tap, a.taps_total, a.CoutP, a.CinP, co0 + ct * 32, ci0 + it * 32 + (lane & 31), lane, acc[tap]);
 }
 
 template <int TAPS, int PW, int CT, int IT>
@@ -275,14 +219,6 @@ static int launch_wgrad(const OnirisWgradArgs* args, int ng, hipStream_t stream)
   }
   // ~1-2 workgroups per CU in total; the split-K columns are dealt to the groups in proportion to their position
   // tiles (every column owns one slab of ITS group's weight)
-#ifndef WGRAD_NG
-// K-groups of 4 waves per workgroup of the LDS-DMA kernel.  1 (round 5): two independent 4-wave workgroups per CU instead of one workgroup of
-// two K-groups -- the same waves, registers and LDS per CU, but no common barrier: the groups drift apart, and one's copy issue, waits and
-// fragment prologue run under the other's MFMAs (a K-group pair in lockstep had both of a SIMD's waves in the same part of the tile loop at
-// any time).  Same-box A/B at B = 8: <2,2,*,16> 25.4 -> 22.4 ms per cycle (roof 0.41 -> 0.47), <2,2,*,8> 9.3 -> 8.5 ms, bench +1.3 %
-// (profiles/r05_ab_wgrad_groups.txt); costs twice the split-K slabs of the 64x64-channel form (ops._nsplit_cap).
-#define WGRAD_NG 1
-#endif
   const int gx_budget = (CT * IT == 4) ? ((use_glds && WGRAD_NG == 1) ? 512 : 256) : 512;
   const int gx_all = gx_budget / gy > ng ? gx_budget / gy : ng;
   int gx_tot = 0;
@@ -297,9 +233,6 @@ static int launch_wgrad(const OnirisWgradArgs* args, int ng, hipStream_t stream)
   for (int g = ng; g <= WGRAD_MAXG; ++g) d.gstart[g] = gx_tot;      // empty groups
   if constexpr (TAPS == 9 && (PW == 16 || PW == 8)) {
     if (use_glds) {
-#ifndef WGRAD_NG1
-#define WGRAD_NG1 1                          // ... of the 32x32-channel tile form (+0.15 %)
-#endif
       constexpr int NG = (CT * IT == 4) ? WGRAD_NG : WGRAD_NG1;
       auto kern = conv_wgrad_glds_kernel<CT, IT, NG, PW>;
       oniris_launch(kern, dim3(gx_tot, gy), dim3(256 * NG), stream, d);

@@ -19,13 +19,9 @@
 
 // PW = 16: 8 x 16 pixel tiles of one frame (128 positions); PW = 8: one whole 8x8 frame (64 positions: four buffers of
 // a 128-position tile of two frames would need 166 KB of LDS)
-#ifndef WGRAD_ROWORDER
-#define WGRAD_ROWORDER 1                     // 0: every (k-step, tap) reads its own x fragment (the round-2..4 loop; A/B: make variant)
-#endif
 template <int CT, int IT, int NG, int PW = 16>
 __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const WgradDev d) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr bool ROWORDER = WGRAD_ROWORDER != 0;
   constexpr int NPOS = (PW == 16) ? 128 : 64, NKT = NPOS / 16;         // positions and 16-position k-steps per tile
   using P = Patch<PW, NPOS>;
   constexpr int FT = P::FT, HHW = P::HH * P::HW;
@@ -39,18 +35,13 @@ __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const Wgra
   };
   __shared__ __attribute__((aligned(16))) unsigned char smem[NG * 2 * BUFB];
 
-  int gsel = 0;
-  if ((int)blockIdx.x >= d.gstart[1]) gsel = 1;
-  if ((int)blockIdx.x >= d.gstart[2]) gsel = 2;
-  const OnirisWgradArgs& a = d.a[gsel];
-  const int bx = blockIdx.x - d.gstart[gsel], gxg = d.gstart[gsel + 1] - d.gstart[gsel];
-  const int g_ntiles = d.ntiles[gsel], g_ntt = d.ntt[gsel];
+  const WgradGroup grp = wgrad_group<CT, IT>(d);
+  const OnirisWgradArgs& a = d.a[grp.gsel];
+  const int bx = grp.bx, gxg = grp.gxg, g_ntiles = grp.ntiles, g_ntt = grp.ntt, co0 = grp.co0, ci0 = grp.ci0;
   const int tid = threadIdx.x, lane = tid & 63, kg = tid >> 8, gtid = tid & 255, wave4 = (tid >> 6) & 3;
   const int H = a.H, W = a.W, HWp = H * W, Cin = a.Cin, Cout = a.Cout;
   const int my_tile = wave4 % NTILE, my_ks = wave4 / NTILE;
   const int ct = my_tile % CT, it = my_tile / CT;
-  const int cib = blockIdx.y % d.ncib, cob = blockIdx.y / d.ncib;
-  const int co0 = cob * 32 * CT, ci0 = cib * 32 * IT;
   unsigned char* gbase = smem + kg * 2 * BUFB;          // this K-group's two buffers
 
   f32x16 acc[TAPS];
@@ -133,10 +124,10 @@ __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const Wgra
     }
   };
 
-  // ---- fragment addresses (transposing reads: lane -> (row q, 8-byte column slot); see conv_wgrad.hip)
+  // ---- fragment addresses (transposing reads: lane -> (row q, 8-byte column slot); wgrad_lane)
   // k-step of this wave: ks = ksi*NKS + my_ks; the my_ks part of every row offset / swizzle parity lives in the bases
-  const int hh = lane >> 5, q = (lane & 15) >> 2;
-  const int cslot = (lane & 3) * 8 + 32 * ((lane >> 4) & 1);
+  const WgradLane ln = wgrad_lane(lane);
+  const int hh = ln.hh, q = ln.q, cslot = ln.cslot;
   const int dsw = (CT == 2) ? 64 * ((q >> 1) & 1) : 0;
   const int dya = (my_ks * 16 + 8 * hh + q) * DROWB + ((ct * 64 + cslot) ^ dsw);          // + ksi*NKS*16*DROWB (+4 rows)
   // halo row of position p0 = ks*16 + 8*hh + q under tap (ky,kx):
@@ -152,17 +143,6 @@ __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const Wgra
       const int rbase = (PW == 16) ? my_ks * P::HW + 8 * hh + q + kx : 20 * my_ks + 10 * hh + q + kx;
       xa[kx][par] = DY_BYTES + rbase * XROWB + ((it * 64 + cslot) ^ xsw);
     }
-
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto trf = [&](const unsigned char* p0, int rowb) __attribute__((always_inline)) {       // rows r..r+3 and r+4..r+7
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 4 * rowb));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
 
   // ---- tile loop: K-group kg takes tiles (bx + j*gxg)*NG + kg
   const int tstep = gxg * NG;
@@ -200,87 +180,27 @@ __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const Wgra
     }
     if (have) {
       const unsigned char* buf = gbase + bsel * BUFB;
-      constexpr int NK = NKT / NKS, NSTEP = NK * TAPS, LA = 3;
-      bf16x8 af[2], bfm[4];
-      auto ld_a = [&](int kb, int ksi) __attribute__((always_inline)) {
-        bf16x8 v = trf(buf + dya + ksi * NKS * 16 * DROWB, DROWB);
-        if (a.scale) {                    // per-frame coefficient folded into dy (bf16 rounding, like a dy2 tensor)
-          const float scf = sc[(FT > 1) ? ((ksi * NKS) >> 2) : 0];       // a k-step never straddles frames
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v[k] = f2bf(bf2f(v[k]) * scf);
-        }
-        af[kb] = v;
+      constexpr int NK = NKT / NKS;
+      auto ld_a = [&](int ksi) __attribute__((always_inline)) {
+        const unsigned char* p = buf + dya + ksi * NKS * 16 * DROWB;
+        bf16x8 v = tr_frag(p, p + 4 * DROWB);
+        if (a.scale) v = wgrad_fold(v, sc[(FT > 1) ? ((ksi * NKS) >> 2) : 0]);          // a k-step never straddles frames
+        return v;
       };
-      auto ld_b = [&](int fb, int st) __attribute__((always_inline)) {
-        const int ksi = st / TAPS, tap = st % TAPS, ky = tap / 3, kx = tap % 3;
-        constexpr int dummy = 0; (void)dummy;
-        const int ksc = ksi * NKS;                                          // compile-time part of the k-step
-        const int par = (PW == 16) ? ((ksc + ky) & 1) : (ky & 1);
-        const int rimm = (PW == 16) ? (ksc + ky) * P::HW : 100 * (ksc >> 2) + 20 * (ksc & 3) + 10 * ky;
-        bfm[fb] = trf(buf + xa[kx][par] + rimm * XROWB, XROWB);
-      };
-      if constexpr (NKS == 1 && ROWORDER) {
-        // HALO-ROW ORDER (a wave that owns every k-step of its 32x32 tile).  The x fragment of (k-step ks, tap (ky, kx)) depends on
-        // u = ks + ky (PW 16: halo row u) resp. u = 2 ks + ky (PW 8: halo rows u, u + 1) and kx only: walking (u, kx) instead of
-        // (ks, tap) reads each of the 30 (27) distinct fragments ONCE and feeds it to up to three MFMAs -- 76 (70) transposing LDS
-        // reads per tile and wave instead of 160 (88), in a loop whose two waves per SIMD issue 2.2 LDS reads per MFMA against
-        // ~1 the LDS pipe can serve.  Per tap the k-steps are still added in ascending order: the partial sums are bit-identical.
-        constexpr int NU = (PW == 16) ? NK + 2 : 2 * NK + 1, NB = NU * 3, AW = (PW == 16) ? 4 : 2;
-        bf16x8 aw[AW];
-        auto ld_aw = [&](int ks) __attribute__((always_inline)) { ld_a(0, ks); aw[ks % AW] = af[0]; };
-        auto ld_bu = [&](int fb, int j) __attribute__((always_inline)) {
-          const int u = j / 3, kx = j % 3;
-          const int par = u & 1;
-          const int rimm = (PW == 16) ? u * P::HW : 10 * u;
-          bfm[fb] = trf(buf + xa[kx][par] + rimm * XROWB, XROWB);
-        };
-        ld_aw(0);
-#pragma unroll
-        for (int j = 0; j < LA; ++j) ld_bu(j, j);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * LA, 0);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int u = j / 3, kx = j % 3;
-          int nrd = 0, nmf = 0;
-          if (j + LA < NB) { ld_bu((j + LA) & 3, j + LA); nrd += 2; }
-          // the dy fragment of k-step ks is first used at u = ks (PW 16) / u = 2 ks (PW 8): requested one u earlier, into the slot
-          // of the k-step whose last use (ky = 2) lies behind
-          const int ksn = (PW == 16) ? u + 1 : (u + 1) / 2;
-          if (kx == 0 && ksn < NK && ((PW == 16) || (u & 1))) { ld_aw(ksn); nrd += 2; }
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int num = u - ky, ks = (PW == 16) ? num : num / 2;
-            if (num >= 0 && ks < NK && ((PW == 16) || (num & 1) == 0)) {
-              acc[ky * 3 + kx] = mfma32(aw[ks % AW], bfm[j & 3], acc[ky * 3 + kx]);
-              ++nmf;
-            }
-          }
-          if (nrd == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);          // (the builtin takes literals)
-          else if (nrd == 4) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          if (nmf == 1) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          else if (nmf == 2) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-        }
-      } else {
-      ld_a(0, 0);
-#pragma unroll
-      for (int j = 0; j < LA; ++j) ld_b(j, j);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * LA, 0);
-#pragma unroll
-      for (int st = 0; st < NSTEP; ++st) {
-        const int ks = st / TAPS, tap = st % TAPS;
-        const int nxs = st + LA;
-        if (nxs < NSTEP) {
-          if (nxs % TAPS == 0) ld_a((nxs / TAPS) & 1, nxs / TAPS);
-          ld_b(nxs & 3, nxs);
-        }
-        acc[tap] = mfma32(af[ks & 1], bfm[st & 3], acc[tap]);
-        if (nxs < NSTEP) {
-          if (nxs % TAPS == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
+      if constexpr (NKS == 1) {           // halo-row order: u = ks + ky (PW 16) resp. 2 ks + ky (PW 8) picks the halo row
+        wgrad_halo_row_loop<PW, NK>(acc, ld_a, [&](int u, int kx) __attribute__((always_inline)) {
+          const unsigned char* p = buf + xa[kx][u & 1] + ((PW == 16) ? u * P::HW : 10 * u) * XROWB;
+          return tr_frag(p, p + 4 * XROWB);
+        });
+      } else {                            // the waves that share a tile deal its k-steps among themselves
+        wgrad_flat_loop<TAPS, NK>(acc, ld_a, [&](int ksi, int tap) __attribute__((always_inline)) {
+          const int ky = tap / 3, kx = tap % 3;
+          const int ksc = ksi * NKS;                                          // compile-time part of the k-step
+          const int par = (PW == 16) ? ((ksc + ky) & 1) : (ky & 1);
+          const int rimm = (PW == 16) ? (ksc + ky) * P::HW : 100 * (ksc >> 2) + 20 * (ksc & 3) + 10 * ky;
+          const unsigned char* p = buf + xa[kx][par] + rimm * XROWB;
+          return tr_frag(p, p + 4 * XROWB);
+        });
       }
     }
     tile = ntile;
@@ -288,42 +208,12 @@ __global__ __launch_bounds__(256 * NG, 2) void conv_wgrad_glds_kernel(const Wgra
   }
 
   // ---- the NKS*NG waves that worked on the same 32x32 tile meet in LDS (tap by tap), then one of them writes the slab
-  if (bx == 0 && blockIdx.y == 0 && tid == 0 && a.nsplit_out) *a.nsplit_out = gxg;
-  constexpr int NPART = NKS * NG;
-  if constexpr (NPART > 1) {
-    const int part = kg * NKS + my_ks;                      // 0 = the wave that keeps the sum
-    float* red = (float*)smem;                             // [NPART-1][NTILE][16][64] floats
+  wgrad_report_nsplit(a.nsplit_out, bx, gxg);
+  if (!wgrad_meet<TAPS, NKS * NG, NTILE>((float*)smem, acc, kg * NKS + my_ks, my_tile, lane)) return;
+  bf16* slab = wgrad_slab(a.dwp, bx, a.taps_total, a.CoutP, a.CinP);
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      __syncthreads();
-      if (part > 0) {
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) red[(((part - 1) * NTILE + my_tile) * 16 + rr) * 64 + lane] = acc[tap][rr];
-      }
-      __syncthreads();
-      if (part == 0) {
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          float v = acc[tap][rr];
-#pragma unroll
-          for (int w = 0; w < NPART - 1; ++w) v += red[((w * NTILE + my_tile) * 16 + rr) * 64 + lane];
-          acc[tap][rr] = v;
-        }
-      }
-    }
-    if (part != 0) return;
-  }
-  const int cj = ci0 + it * 32 + (lane & 31);
-  bf16* slab = (bf16*)a.dwp + (size_t)bx * a.taps_total * a.CoutP * a.CinP;
-#pragma unroll
-  for (int tap = 0; tap < TAPS; ++tap) {
-    bf16* base = slab + (size_t)(a.tap0 + tap) * a.CinP;               // slab layout [co][tap][ci]: a weight row is contiguous
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {
-      const int co = co0 + ct * 32 + mfma_row(rr, lane);
-      if (co < a.CoutP && cj < a.CinP) base[(size_t)co * a.taps_total * a.CinP + cj] = f2bf(acc[tap][rr]);
-    }
-  }
+  for (int tap = 0; tap < TAPS; ++tap)
+    wgrad_store_tile(slab, a.tap0 + tap, a.taps_total, a.CoutP, a.CinP, co0 + ct * 32, ci0 + it * 32 + (lane & 31), lane, acc[tap]);
 #endif
 }
 

@@ -112,24 +112,13 @@ __global__ __launch_bounds__(64 * PH, 2) void conv_wgrad_stream_kernel(const Wgr
     dma16(rs_d3, dvoff, ((b * T + f) * HWp * Cout) * 2 + dy_origin, dyb + 2 * DB + wdst);
   };
 
-  // ---- fragment addresses (transposing reads; see conv_wgrad.hip): lane -> (row q of its 8-row half, 8-byte column slot)
-  const int hh = lane >> 5, q = (lane & 15) >> 2;
-  const int cslot = (lane & 3) * 8 + 32 * ((lane >> 4) & 1);
+  // ---- fragment addresses (transposing reads; wgrad_lane): lane -> (row q of its 8-row half, 8-byte column slot)
+  const WgradLane ln = wgrad_lane(lane);
+  const int hh = ln.hh, q = ln.q, cslot = ln.cslot;
   const int dya = (half * 64 + 8 * hh + q) * 64 + cslot;           // + j*16*64: pixel row j of this wave's four
   int xa[3];
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) xa[kx] = (half * 4 * HW_ + 8 * hh + q + kx) * 64 + cslot;     // + (j + ky) * 18 * 64
-
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto trf = [&](const unsigned char* p0) __attribute__((always_inline)) {       // rows r..r+3 and r+4..r+7 (64-byte rows)
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 256));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
 
   // ---- prologue: the two frames in front of the segment (padding frames in front of the sequence), then frame t0
   const bool scaled = role == 0 && d.scale != nullptr;
@@ -155,118 +144,49 @@ __global__ __launch_bounds__(64 * PH, 2) void conv_wgrad_stream_kernel(const Wgr
     const unsigned char* abuf = smem + DY0 + (t & 1) * 3 * DB + ((role == 0) ? slot * DB : 2 * DB);
     const unsigned char* bbuf = smem + ((role == 0) ? (slot ? XS1 + (t & 1) * XB : XS0 + (t & 3) * XB)
                                                     : XS0 + ((t - 3 + role) & 3) * XB);
-    constexpr int NK = 4, NSTEP = NK * TAPS, LA = 3;
-    bf16x8 af[2], bfm[4];
-    auto ld_a = [&](int kb, int j) __attribute__((always_inline)) {
-      bf16x8 v = trf(abuf + dya + j * 16 * 64);
-      if (scaled) {                          // per-frame coefficient folded into dy (bf16 rounding, like a dy2 tensor)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = f2bf(bf2f(v[k]) * sc);
-      }
-      af[kb] = v;
-    };
-    auto ld_b = [&](int fb, int st) __attribute__((always_inline)) {
-      const int j = st / TAPS, tap = st % TAPS, ky = tap / 3, kx = tap % 3;
-      bfm[fb] = trf(bbuf + xa[kx] + (j + ky) * HW_ * 64);
-    };
-#ifndef WGRAD_STREAM_ROWORDER
-#define WGRAD_STREAM_ROWORDER 1            // 0: every (pixel row, tap) reads its own x fragment (round 4's loop; A/B)
-#endif
-    if constexpr (WGRAD_STREAM_ROWORDER != 0) {
-      // halo-row order (see conv_wgrad_glds.h): the x fragment of (pixel row j, tap (ky, kx)) depends on u = j + ky and kx only --
-      // 18 distinct fragments per frame and wave instead of 36 reads; per tap the rows are still added in ascending order
-      constexpr int NU = NK + 2, NB = NU * 3;
-      bf16x8 aw[4];
-      auto ld_aw = [&](int j) __attribute__((always_inline)) { ld_a(0, j); aw[j & 3] = af[0]; };
-      auto ld_bu = [&](int fb, int i) __attribute__((always_inline)) { bfm[fb] = trf(bbuf + xa[i % 3] + (i / 3) * HW_ * 64); };
-      ld_aw(0);
-#pragma unroll
-      for (int i = 0; i < LA; ++i) ld_bu(i, i);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * LA, 0);
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int u = i / 3, kx = i % 3;
-        int nrd = 0, nmf = 0;
-        if (i + LA < NB) { ld_bu((i + LA) & 3, i + LA); nrd += 2; }
-        if (kx == 0 && u + 1 < NK) { ld_aw(u + 1); nrd += 2; }
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int j = u - ky;
-          if (j >= 0 && j < NK) { acc[ky * 3 + kx] = mfma32(aw[j & 3], bfm[i & 3], acc[ky * 3 + kx]); ++nmf; }
-        }
-        if (nrd == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        else if (nrd == 4) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        if (nmf == 1) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        else if (nmf == 2) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        else __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-      }
-    } else {
-    ld_a(0, 0);
-#pragma unroll
-    for (int j = 0; j < LA; ++j) ld_b(j, j);
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * LA, 0);
-#pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
-      const int ks = st / TAPS, tap = st % TAPS;
-      const int nxs = st + LA;
-      if (nxs < NSTEP) {
-        if (nxs % TAPS == 0) ld_a((nxs / TAPS) & 1, nxs / TAPS);
-        ld_b(nxs & 3, nxs);
-      }
-      acc[tap] = mfma32(af[ks & 1], bfm[st & 3], acc[tap]);
-      if (nxs < NSTEP) {
-        if (nxs % TAPS == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    }
-    }
+    // halo-row order: the x fragment of (pixel row j, tap (ky, kx)) depends on u = j + ky and kx only -- 18 distinct fragments
+    // per frame and wave instead of 36 reads; per tap the rows are still added in ascending order
+    wgrad_halo_row_loop<16, 4>(                                      // a wave: four pixel rows of 16 = four k-steps
+        acc,
+        [&](int j) __attribute__((always_inline)) {
+          const unsigned char* p = abuf + dya + j * 16 * 64;
+          bf16x8 v = tr_frag(p, p + 256);
+          if (scaled) v = wgrad_fold(v, sc);
+          return v;
+        },
+        [&](int u, int kx) __attribute__((always_inline)) {
+          const unsigned char* p = bbuf + xa[kx] + u * HW_ * 64;
+          return tr_frag(p, p + 256);
+        });
   }
 
   // ---- the waves that worked on the same weight meet in LDS (three taps per round), then waves 0 / 4 / 6 write the slabs
-  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-    if (d.nsplit2) *d.nsplit2 = gridDim.x;
-    if (d.nsplit3) *d.nsplit3 = gridDim.x;
-  }
+  wgrad_report_nsplit(d.nsplit2, blockIdx.x, gridDim.x);
+  wgrad_report_nsplit(d.nsplit3, blockIdx.x, gridDim.x);
   const int nl = (PH == 8) ? ((wave == 1) ? 0 : (wave == 2) ? 1 : (wave == 3) ? 2 : (wave == 5) ? 3 : (wave == 7) ? 4 : -1)
                            : ((wave == 1) ? 0 : -1);             // PH 4: only dW2 has two partial sums (the slots)
-  float* red = (float*)smem;                                     // [5][3][16][64]
+  const int first = (PH == 8) ? ((wave == 0) ? 0 : (wave == 4) ? 3 : 4) : 0;
+  const int cnt = (PH == 8) ? ((wave == 0) ? 3 : 1) : ((wave == 0) ? 1 : 0);
+  float* red = (float*)smem;                                     // slots [3 taps of a round][5 partial sums]
 #pragma unroll
   for (int r3 = 0; r3 < 3; ++r3) {
     __syncthreads();
     if (nl >= 0) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) red[((nl * 3 + k) * 16 + rr) * 64 + lane] = acc[r3 * 3 + k][rr];
+      for (int k = 0; k < 3; ++k) wgrad_red_put(red, k * 5 + nl, lane, acc[r3 * 3 + k]);
     }
     __syncthreads();
     if (nl < 0) {
-      const int first = (PH == 8) ? ((wave == 0) ? 0 : (wave == 4) ? 3 : 4) : 0;
-      const int cnt = (PH == 8) ? ((wave == 0) ? 3 : 1) : ((wave == 0) ? 1 : 0);
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          float v = acc[r3 * 3 + k][rr];
-          for (int w = 0; w < cnt; ++w) v += red[(((first + w) * 3 + k) * 16 + rr) * 64 + lane];
-          acc[r3 * 3 + k][rr] = v;
-        }
+      for (int k = 0; k < 3; ++k) wgrad_red_add(red, k * 5 + first, cnt, lane, acc[r3 * 3 + k]);
     }
   }
   if (nl >= 0) return;
   const int taps_total = (role == 0) ? 9 : 18, tap0 = (role == 2) ? 9 : 0;
-  const int cj = ci0 + (lane & 31);
-  bf16* slab = (bf16*)((role == 0) ? d.dwp2 : d.dwp3) + (size_t)blockIdx.x * taps_total * d.CoutP * d.CinP;
+  bf16* slab = wgrad_slab((role == 0) ? d.dwp2 : d.dwp3, blockIdx.x, taps_total, d.CoutP, d.CinP);
 #pragma unroll
-  for (int tap = 0; tap < TAPS; ++tap) {
-    bf16* base = slab + (size_t)(tap0 + tap) * d.CinP;             // slab layout [co][tap][ci]
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {
-      const int co = co0 + mfma_row(rr, lane);
-      if (co < d.CoutP && cj < d.CinP) base[(size_t)co * taps_total * d.CinP + cj] = f2bf(acc[tap][rr]);
-    }
-  }
+  for (int tap = 0; tap < TAPS; ++tap)
+    wgrad_store_tile(slab, tap0 + tap, taps_total, d.CoutP, d.CinP, co0, ci0 + (lane & 31), lane, acc[tap]);
 #endif
 }
 
@@ -295,9 +215,6 @@ static int launch_wgrad_stream(const OnirisWgradArgs* a, hipStream_t stream) {
   d.x = o.x; d.dout = o.dy; d.dy3 = c0.dy; d.scale = o.scale;
   d.dwp2 = o.dwp; d.dwp3 = c0.dwp; d.nsplit2 = o.nsplit_out; d.nsplit3 = c0.nsplit_out;
   d.B = c0.B; d.T = c0.T; d.H = o.H; d.W = o.W; d.Cin = o.Cin; d.CinP = o.CinP; d.Cout = o.Cout; d.CoutP = o.CoutP;
-#ifndef WGRAD_STREAM_PH
-#define WGRAD_STREAM_PH 4                  // 8: always the 8x16-pixel form (A/B: make variant VSRC=conv_wgrad VDEF=-DWGRAD_STREAM_PH=8)
-#endif
   d.ntx = o.W / 16; d.ncib = cdiv(o.Cin, 32);
   d.fill = c0.fill;
   const int ncob = cdiv(o.Cout, 32), gy = d.ncib * ncob;

@@ -5,7 +5,7 @@
 // output tile (each of the 4 waves of a K-group a 64x64 quarter = 2x2 MFMA tiles, so every fragment feeds two MFMAs),
 // stages 64-position tiles of dy and x with LDS-DMA (256-byte rows whose four 64-byte granules are XOR-swizzled with
 // row&3 on the source side: the four rows of a transposing read hit disjoint banks), double-buffered, two K-groups
-// per workgroup (8 waves), partial sums of the groups summed in LDS, one fp32 slab per workgroup column.
+// per workgroup (8 waves), partial sums of the groups summed in LDS, one bf16 slab per workgroup column.
 #pragma once
 #include "lds_dma.h"
 
@@ -58,25 +58,15 @@ __global__ __launch_bounds__(256 * NG, 2) void wgrad1x1_glds_kernel(const WgradD
     }
   };
 
-  // transposing-read addresses (lane -> row q of a 4-row group, 8-byte column slot); granule swizzle = q << 6
-  const int hh = lane >> 5, q = (lane & 15) >> 2;
-  const int cslot = (lane & 3) * 8 + 32 * ((lane >> 4) & 1);
+  // transposing-read addresses (wgrad_lane: lane -> row q of a 4-row group, 8-byte column slot); granule swizzle = q << 6
+  const WgradLane ln = wgrad_lane(lane);
+  const int hh = ln.hh, q = ln.q, cslot = ln.cslot;
   int aoff[2], boff[2];
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     aoff[m] = (8 * hh + q) * ROWB + ((wr * 128 + m * 64 + cslot) ^ (q << 6));
     boff[m] = TILEB + (8 * hh + q) * ROWB + ((wc * 128 + m * 64 + cslot) ^ (q << 6));
   }
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto trf = [&](const unsigned char* p0) __attribute__((always_inline)) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 4 * ROWB));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
 
   const int tstep = gxg * NG;
   int tile = bx * NG + kg, bsel = 0;
@@ -91,15 +81,20 @@ __global__ __launch_bounds__(256 * NG, 2) void wgrad1x1_glds_kernel(const WgradD
       const unsigned char* buf = smem + (kg * 2 + bsel) * BUFB;
       bf16x8 af[2][2], bf_[2][2];                           // [k-step parity][tile]
 #pragma unroll
-      for (int m = 0; m < 2; ++m) { af[0][m] = trf(buf + aoff[m]); bf_[0][m] = trf(buf + boff[m]); }
+      for (int m = 0; m < 2; ++m) {
+        const unsigned char *pa = buf + aoff[m], *pb = buf + boff[m];
+        af[0][m] = tr_frag(pa, pa + 4 * ROWB);
+        bf_[0][m] = tr_frag(pb, pb + 4 * ROWB);
+      }
       __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
       for (int ks = 0; ks < KT / 16; ++ks) {
         if (ks + 1 < KT / 16) {
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            af[(ks + 1) & 1][m] = trf(buf + aoff[m] + (ks + 1) * 16 * ROWB);
-            bf_[(ks + 1) & 1][m] = trf(buf + boff[m] + (ks + 1) * 16 * ROWB);
+            const unsigned char *pa = buf + aoff[m] + (ks + 1) * 16 * ROWB, *pb = buf + boff[m] + (ks + 1) * 16 * ROWB;
+            af[(ks + 1) & 1][m] = tr_frag(pa, pa + 4 * ROWB);
+            bf_[(ks + 1) & 1][m] = tr_frag(pb, pb + 4 * ROWB);
           }
         }
 #pragma unroll
@@ -114,38 +109,27 @@ __global__ __launch_bounds__(256 * NG, 2) void wgrad1x1_glds_kernel(const WgradD
     bsel ^= 1;
   }
 
-  if (bx == 0 && blockIdx.y == 0 && tid == 0 && a.nsplit_out) *a.nsplit_out = gxg;
+  wgrad_report_nsplit(a.nsplit_out, bx, gxg);
   if constexpr (NG > 1) {
-    float* red = (float*)smem;                             // [4 waves][16][64] floats per 32x32 tile
+    float* red = (float*)smem;                             // a slot per wave of a K-group, one 32x32 tile at a time
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         __syncthreads();
-        if (kg == 1) {
-#pragma unroll
-          for (int rr = 0; rr < 16; ++rr) red[(wave4 * 16 + rr) * 64 + lane] = acc[m][n][rr];
-        }
+        if (kg == 1) wgrad_red_put(red, wave4, lane, acc[m][n]);
         __syncthreads();
-        if (kg == 0) {
-#pragma unroll
-          for (int rr = 0; rr < 16; ++rr) acc[m][n][rr] += red[(wave4 * 16 + rr) * 64 + lane];
-        }
+        if (kg == 0) wgrad_red_add(red, wave4, 1, lane, acc[m][n]);
       }
     if (kg != 0) return;
   }
-  bf16* slab = (bf16*)a.dwp + (size_t)bx * a.taps_total * a.CoutP * a.CinP + (size_t)a.tap0 * a.CinP;   // [co][tap][ci]
+  bf16* slab = wgrad_slab(a.dwp, bx, a.taps_total, a.CoutP, a.CinP);
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-      const int cj = ci0 + wc * 64 + n * 32 + (lane & 31);
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        const int co = co0 + wr * 64 + m * 32 + mfma_row(rr, lane);
-        if (co < a.CoutP && cj < a.CinP) slab[(size_t)co * a.taps_total * a.CinP + cj] = f2bf(acc[m][n][rr]);
-      }
-    }
+    for (int n = 0; n < 2; ++n)
+      wgrad_store_tile(slab, a.tap0, a.taps_total, a.CoutP, a.CinP, co0 + wr * 64 + m * 32, ci0 + wc * 64 + n * 32 + (lane & 31), lane,
+                       acc[m][n]);
 #endif
 }
 
@@ -156,9 +140,6 @@ static inline bool wgrad1x1_glds_ok(const OnirisWgradArgs& a) {
 }
 
 static int launch_wgrad1x1_glds(const OnirisWgradArgs& a, hipStream_t stream) {
-#ifndef WGRAD1X1_NG
-#define WGRAD1X1_NG 2                        // K-groups per workgroup (1: two 4-wave workgroups per CU; A/B)
-#endif
   constexpr int NG = WGRAD1X1_NG;
   WgradDev d;
   memset(&d, 0, sizeof(d));
