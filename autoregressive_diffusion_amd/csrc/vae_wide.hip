@@ -1,4 +1,4 @@
-// VAE decoder at block widths above 64 channels (reference: edm2/vae/vae.py EncoderDecoder(type='decoder'), :56-204), inference
+// VAE decoder and encoder at block widths above 64 channels (reference: edm2/vae/vae.py EncoderDecoder, :56-204), inference
 // only, fp32 throughout, channels-last [B][T][H][W][C].  include/oniris.h: oniris_vae_wide_*.  Per wide ResBlock:
 //   oniris_vae_wide_temb    oniris_vae_temb for ResBlocks of any width (one launch per decode of a model with a wide block)
 //   oniris_vae_wide_act     y = SiLU(RMS(x) (1 + scale) + shift) into the sequence buffer S = [g prefix frames ++ y] and the cache
@@ -6,6 +6,8 @@
 //   oniris_vae_wide_act     u = SiLU(RMS(a))
 //   oniris_vae_wide_conv_b  out = res + bias + conv3x3(u)                                   (disc_conv_kernel<NB>, res_scale = 1)
 // and the 1x1 stages as GEMMs on the same tile kernel: oniris_vae_wide_up, oniris_vae_wide_out (csrc/vae_wide_conv.h).
+// The encoder at those widths runs the same ResBlock launches with a null emb (it passes t = None) behind oniris_vae_wide_down, the
+// compression stage as a GEMM over the strided fp32 or uint8 input (vae_wide_down_kernel of csrc/vae_wide_conv.h).
 // The convs take operands that are already activated: the cache is a plain copy of frames of S, and a conv of integers is exact.
 // Nothing here bounds the width: MAX_WIDTH of autoregressive_diffusion_amd/vae.py is the one constant that does.
 #include "oniris.h"
@@ -190,4 +192,45 @@ extern "C" int oniris_vae_wide_out(const float* x, const float* w, const float* 
   p.B = B; p.T = T; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.nsub = 1; p.g = 1; p.split = split;
   p.sb = sb; p.st = st; p.sh = sh; p.sw = sw; p.scs = sc;
   return vae_wide_dispatch<VW_OUT>("vae_wide_out", p, (long long)B * T, (hipStream_t)stream);
+}
+
+template <int NB, typename TIN, bool VEC>
+static int vae_wide_down_launch(const VaeWideDownParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(vae_wide_down_kernel<NB, TIN, VEC>, bytes, "vae_wide_down")) return rc;
+  ONIRIS_KLAUNCH((vae_wide_down_kernel<NB, TIN, VEC>), grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+template <int NB>
+static int vae_wide_down_pick(const VaeWideDownParams& p, int x_is_u8, bool vec, dim3 grid, hipStream_t stream) {
+  if (x_is_u8) return vae_wide_down_launch<NB, unsigned char, false>(p, grid, stream);
+  return vec ? vae_wide_down_launch<NB, float, true>(p, grid, stream) : vae_wide_down_launch<NB, float, false>(p, grid, stream);
+}
+
+extern "C" int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B,
+                                    int To, int Ho, int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w,
+                                    const float* bias, int Cout, float* out, oniris_stream_t stream) {
+  ONIRIS_CHECK_ARG(x && w && bias && out && (const void*)out != x, "vae_wide_down: null pointer or out aliases x");
+  ONIRIS_CHECK_ARG(B > 0 && To > 0 && Ho > 0 && Wo > 0 && vae_wide_c_ok(Cin) && vae_wide_c_ok(Cout) && tcomp >= 1 && tcomp <= 2 &&
+                       scomp >= 1 && scomp <= 2,
+                   "vae_wide_down: bad sizes (B %d T %d H %d W %d Cin %d tc %d sc %d Cout %d)", B, To, Ho, Wo, Cin, tcomp, scomp, Cout);
+  VaeWideDownParams p{};
+  p.x = x; p.w = w; p.bias = bias; p.out = out;
+  p.sb = sb; p.st = st; p.sh = sh; p.sw = sw; p.sc = sc;
+  p.B = B; p.To = To; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.Cout = Cout; p.tc = tcomp; p.scm = scomp; p.normalize = normalize;
+  p.CinP = roundup(Cin, 2);
+  p.CP = roundup(Cout, 32);
+  p.tiles_x = cdiv(Wo, DISC_TILE); p.tiles_y = cdiv(Ho, DISC_TILE);
+  const int nb = vae_wide_nb(p.CP);
+  p.nblk = p.CP / (32 * nb);
+  const long long wgs = (long long)B * To * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && p.nblk <= 65535, "vae_wide_down: %lld tiles", wgs);
+  const bool vec = !x_is_u8 && !normalize && sc == 1 && Cin % 32 == 0 && sb % 4 == 0 && st % 4 == 0 && sh % 4 == 0 && sw % 4 == 0 &&
+                   ((uintptr_t)x & 15) == 0;
+  const dim3 grid((unsigned)wgs, p.nblk);
+  return nb == 2 ? vae_wide_down_pick<2>(p, x_is_u8, vec, grid, (hipStream_t)stream)
+                 : vae_wide_down_pick<1>(p, x_is_u8, vec, grid, (hipStream_t)stream);
 }

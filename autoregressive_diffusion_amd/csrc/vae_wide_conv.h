@@ -13,6 +13,10 @@
 // up, 0 for out, so that a block of output channels lies inside one output frame / sub-position and a lane's stores are
 // contiguous over the channels.  Weights w[tap][CinP][nsub CP], CinP = Cin rounded up to even, zero where padded.
 //
+// The encoder's stage is a sibling kernel over the same parts (vae_wide_down_kernel, below):
+//   down       'b c (t tc) (h hc) (w wc) -> b (tc hc wc c) t h w', the compression 1x1 conv K = Cin tc sc^2 -> Cout + the channel-area
+//              residual of the rearranged input; M = a 16x16 tile of OUTPUT pixels, K walked as sub-position, chunk, channel pair.
+//
 // Every output is summed in the order time tap, channel chunk, spatial tap, channel pair, then the bias (and the residual); it
 // depends on neither T, nor B, nor where a sequence was cut: a decode in chunks through the cache is bit-identical to the whole.
 #pragma once
@@ -133,5 +137,163 @@ __global__ __launch_bounds__(256) void vae_wide_kernel(VaeWideParams p) {
           }
         }
       }
+  }
+}
+
+// ---- down (reference: edm2/vae/vae.py :109-122, :136-141, :157-161).  Output pixel (t, y, x) at sub-position pos = (tq sc + hq) sc +
+// wq reads input pixel (t tc + tq, y sc + hq, x sc + wq); the rearranged channel is k = pos Cin + c.  The input is fp32 or uint8
+// addressed through element strides (b, t, h, w, c), normalised on load as vae_load_in of csrc/vae_encoder.hip does it.  Weights
+// w[pos][CinP][CP], bias [CP].  One MFMA tap (the centre one): only the 16x16 interior of the stage is filled and read.
+// out = (conv + bias) + area / len, area = the window [floor(o K / Cout), ceil((o + 1) K / Cout)) of output channel o summed in
+// ascending k (the association of vae_down_kernel), read again from the input (vae_wide_area).  Every sum runs in an order set by (Cin, tc, sc, Cout) alone.
+struct VaeWideDownParams {
+  const void* x; const float* w; const float* bias;
+  float* out;
+  long long sb, st, sh, sw, sc;
+  int B, To, Ho, Wo, Cin, CinP, Cout, CP, nblk, tiles_x, tiles_y, tc, scm, normalize;
+};
+
+template <typename TIN>
+__device__ __forceinline__ float vae_wide_load_in(const TIN* p, int normalize) {
+  const float v = (float)*p;
+  return normalize ? __fsub_rn(__fdiv_rn(v, 127.5f), 1.f) : v;
+}
+
+// Channels c0 .. c0 + kc - 1 of the tile's 256 input pixels at one sub-position (xs: the sample's plane t tc + tq moved by hq rows
+// and wq columns; ysh / xsw: the strides of one OUTPUT row / column) into the interior of hl; channels >= Cin and pixels outside
+// the output plane are 0.
+template <typename TIN>
+__device__ __forceinline__ void vae_wide_stage_down(float* hl, const TIN* xs, long long ysh, long long xsw, long long sc, int normalize,
+                                                    int y0, int x0, int Ho, int Wo, int Cin, int c0, int kc) {
+  for (int idx = threadIdx.x; idx < DISC_TILE * DISC_TILE * kc; idx += 256) {
+    const int c = idx % kc, pix = idx / kc, py = pix >> 4, px = pix & 15;
+    const int y = y0 + py, xx = x0 + px;
+    float v = 0.f;
+    if (y < Ho && xx < Wo && c0 + c < Cin) v = vae_wide_load_in(xs + y * ysh + xx * xsw + (c0 + c) * sc, normalize);
+    hl[((py + 1) * DISC_HALO + px + 1) * DISC_APITCH + c] = v;
+  }
+}
+
+// The same for a full chunk of DISC_KC channels of contiguous fp32 whose channel count is a multiple of 32: 16-byte loads, all of a
+// thread's loads issued before the first is used (the pattern of disc_stage_halo_vec).  Bit for bit what the scalar routine stores.
+__device__ __forceinline__ void vae_wide_stage_down_vec(float* hl, const float* xs, long long ysh, long long xsw, int y0, int x0, int Ho,
+                                                        int Wo, int c0) {
+  constexpr int Q = DISC_KC / 4, IT = DISC_TILE * DISC_TILE * Q / 256;
+  f32x4 v[IT];
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int idx = threadIdx.x + it * 256, q = idx % Q, pix = idx / Q;
+    const int y = y0 + (pix >> 4), xx = x0 + (pix & 15);
+    v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (y < Ho && xx < Wo) v[it] = *reinterpret_cast<const f32x4*>(xs + y * ysh + xx * xsw + c0 + 4 * q);
+  }
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+    const int idx = threadIdx.x + it * 256, q = idx % Q, pix = idx / Q;
+    float* o = hl + (((pix >> 4) + 1) * DISC_HALO + (pix & 15) + 1) * DISC_APITCH + 4 * q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = v[it][e];
+  }
+}
+
+// The window [s0, s1) of the rearranged channel axis at one output pixel (xp: the pixel's sub-position 0), summed in ascending k.
+// Loads run ahead of the adds, eight values (VEC: four 16-byte loads) at a time; the adds keep their order.
+template <typename TIN, bool VEC>
+__device__ __forceinline__ float vae_wide_area(const TIN* xp, int s0, int s1, const VaeWideDownParams& p) {
+  float area = 0.f;
+  int pos = s0 / p.Cin, c = s0 - pos * p.Cin;
+  for (int k = s0; k < s1; ++pos) {
+    const TIN* xq = xp + (pos / (p.scm * p.scm)) * p.st + ((pos / p.scm) % p.scm) * p.sh + (pos % p.scm) * p.sw;
+    const int ce = min(p.Cin, c + (s1 - k));
+    k += ce - c;
+    if (VEC) {
+      const float* xf = (const float*)xq;
+      for (; c < ce && (c & 3); ++c) area += xf[c];
+      for (; c + 16 <= ce; c += 16) {
+        f32x4 v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = *reinterpret_cast<const f32x4*>(xf + c + 4 * e);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) area += v[e >> 2][e & 3];
+      }
+      for (; c + 4 <= ce; c += 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xf + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) area += v[e];
+      }
+    }
+    for (; c + 8 <= ce; c += 8) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = vae_wide_load_in(xq + (c + e) * p.sc, p.normalize);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) area += v[e];
+    }
+    for (; c < ce; ++c) area += vae_wide_load_in(xq + c * p.sc, p.normalize);
+    c = 0;
+  }
+  return area;
+}
+
+template <int NB, typename TIN, bool VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void vae_wide_down_kernel(VaeWideDownParams p) {
+  extern __shared__ __attribute__((aligned(16))) float disc_lds[];
+  float* hl = disc_lds;                                          // [324][17], the interior only
+  float* wl = disc_lds + DISC_HALO * DISC_HALO * DISC_APITCH;    // [1][16][WP]
+  const int tiles = p.tiles_x * p.tiles_y;
+  const int tile = blockIdx.x % tiles, pl = blockIdx.x / tiles;  // pl = n To + t
+  const int y0 = (tile / p.tiles_x) * DISC_TILE, x0 = (tile % p.tiles_x) * DISC_TILE;
+  const int n0 = blockIdx.y * 32 * NB;
+  const int n = pl / p.To, t = pl % p.To;
+  const int P = p.tc * p.scm * p.scm;
+  const long long ysh = p.scm * p.sh, xsw = p.scm * p.sw;
+  const TIN* xn = (const TIN*)p.x + n * p.sb + (long long)t * p.tc * p.st;
+
+  f32x16 acc[2][NB];
+  disc_zero(acc);
+  for (int pos = 0; pos < P; ++pos) {
+    const TIN* xs = xn + (pos / (p.scm * p.scm)) * p.st + ((pos / p.scm) % p.scm) * p.sh + (pos % p.scm) * p.sw;
+    for (int c0 = 0; c0 < p.CinP; c0 += DISC_KC) {
+      const int kc = min(DISC_KC, p.CinP - c0);
+      __syncthreads();
+      if (VEC) vae_wide_stage_down_vec(hl, (const float*)xs, ysh, xsw, y0, x0, p.Ho, p.Wo, c0);
+      else vae_wide_stage_down(hl, xs, ysh, xsw, p.sc, p.normalize, y0, x0, p.Ho, p.Wo, p.Cin, c0, kc);
+      disc_stage_weights<NB>(wl, p.w, pos, 1, p.CinP, p.CP, c0, kc, n0);
+      __syncthreads();
+      vae_wide_mfma_taps<NB, 1>(acc, hl, wl, kc);
+    }
+  }
+
+  // the area residual: per lane the window of its output channel at its 32 pixels, each summed in ascending k; a rolled loop per
+  // 16 pixels leaves the sums in the lane's own slots of the (now free) stage, and the unrolled store loop picks them up
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31;
+  const long long K = (long long)P * p.Cin;
+  float* al = disc_lds;                                          // [16][256]
+  __syncthreads();
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    const int co = n0 + nb * 32 + j;
+    if (co >= p.Cout) continue;
+    const float bv = p.bias[co];
+    const int s0 = (int)((co * K) / p.Cout), s1 = (int)(((co + 1) * K + p.Cout - 1) / p.Cout);
+    const float len = (float)(s1 - s0);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll 1
+      for (int r = 0; r < 16; ++r) {
+        const int i = mfma_row(r, lane);
+        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
+        float area = 0.f;
+        if (y < p.Ho && xx < p.Wo) area = vae_wide_area<TIN, VEC>(xn + y * ysh + xx * xsw, s0, s1, p);
+        al[r * 256 + threadIdx.x] = area;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = mfma_row(r, lane);
+        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
+        if (y >= p.Ho || xx >= p.Wo) continue;
+        p.out[(((size_t)pl * p.Ho + y) * p.Wo + xx) * p.Cout + co] = (acc[mb][nb][r] + bv) + al[r * 256 + threadIdx.x] / len;
+      }
+    }
   }
 }

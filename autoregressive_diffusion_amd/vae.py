@@ -10,9 +10,11 @@ whole sequence gives (bit-identical here: csrc/vae*.hip and csrc/vae_conv3.h sum
 Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up` launch, two per ResBlock, one `out` launch,
 plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
 ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
-Decoder blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip:
-the same `up` and `out` stages as GEMMs and four launches per ResBlock (activation, conv A, activation, conv B), with the same
-cache entries; a model that has such a block has the decoder only (include/oniris.h: oniris_vae_wide_*).
+Blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip, on
+both sides: the `up`, `out` and `down` stages as GEMMs and four launches per ResBlock (activation, conv A, activation, conv B; the
+encoder passes a null FiLM pointer), with the same cache entries.  An encoder `down` also takes the GEMM when it compresses more
+than 512 channels, whatever its output width.  A model that has such a block runs for inference only: the training path of
+`forward` raises NotImplementedError (include/oniris.h: oniris_vae_wide_*).
 
 `forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
 enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
@@ -28,8 +30,9 @@ from torch import nn
 from . import _lib
 from .edm2.utils import BetterModule, MPFourier, bmult
 
-MAX_WIDTH = 256        # the widest decoder block (the MFMA tile kernels of csrc/vae_wide.hip take any width; this is the one bound)
+MAX_WIDTH = 256        # the widest block (the MFMA tile kernels of csrc/vae_wide.hip take any width; this is the one bound)
 MAX_NARROW = 64        # up to here a block runs on the register-tile kernels of csrc/vae.hip / csrc/vae_conv3.h
+MAX_DOWN_K = 512       # up to here a narrow encoder block's `down` runs on vae_down_kernel (csrc/vae_encoder.hip)
 _REF = "the reference's edm2.vae (this package runs the VAE on HIP kernels only)"
 
 
@@ -114,6 +117,17 @@ def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
     b = torch.zeros(nsub, CP, **f32)
     b[:, :Cout] = bias.detach().to(**f32).reshape(nsub, Cout)
     return w.contiguous(), b.contiguous()
+
+
+def _pack_down_wide(weight, bias, Cin, Cout, npos, f32):
+    """The compression 1x1 conv npos Cin -> Cout (rearranged channel k = pos Cin + c) as w [npos][CinP][CP], bias [CP]
+    (vae_wide_down_kernel of csrc/vae_wide_conv.h)."""
+    CP, CinP = -(-Cout // 32) * 32, Cin + (Cin & 1)
+    w = torch.zeros(npos, CinP, CP, **f32)
+    w[:, :Cin, :Cout] = weight.detach().to(**f32).reshape(Cout, npos, Cin).permute(1, 2, 0)
+    b = torch.zeros(CP, **f32)
+    b[:Cout] = bias.detach().to(**f32)
+    return w.contiguous(), b
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -228,11 +242,13 @@ def out(x, bk, s, lvm=None, want="next"):
 
 
 def down(x, strides, dims, normalize, bk, s):
-    """oniris_vae_down: fp32 or uint8 frames x by `strides` (normalize: x / 127.5 - 1 on load) -> (B, T, H, W, C) over `dims`."""
+    """oniris_vae_down, or oniris_vae_wide_down where bk["wide_down"]: fp32 or uint8 frames x by `strides` (normalize:
+    x / 127.5 - 1 on load) -> (B, T, H, W, C) over `dims`."""
     B, T, H, W = dims
     y = _new(x, B, T, H, W, bk["C"])
-    _lib.check(_lib.lib.oniris_vae_down(_p(x), int(x.dtype == torch.uint8), *strides, B, T, H, W, bk["Cin"], bk["tc"], bk["sc"],
-                                        int(normalize), _p(bk["wd"]), _p(bk["bd"]), bk["C"], _p(y), s), "vae_down")
+    entry, what = (_lib.lib.oniris_vae_wide_down, "vae_wide_down") if bk.get("wide_down") else (_lib.lib.oniris_vae_down, "vae_down")
+    _lib.check(entry(_p(x), int(x.dtype == torch.uint8), *strides, B, T, H, W, bk["Cin"], bk["tc"], bk["sc"], int(normalize),
+                     _p(bk["wd"]), _p(bk["bd"]), bk["C"], _p(y), s), what)
     return y
 
 
@@ -322,12 +338,12 @@ class EncoderDecoder(nn.Module):
 
 
 class VAE(BetterModule):
-    """The reference's VAE (vae.py:207-318) on HIP kernels.  Supported: every decoder width <= 256 with at most 64 latent
+    """The reference's VAE (vae.py:207-318) on HIP kernels.  Supported: every block width <= 256 with at most 64 latent
     channels, time and spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises
-    NotImplementedError here.  Blocks of up to 64 channels run on the register-tile kernels (csrc/vae.hip), wider ones on the
-    fp32 MFMA tile kernels (csrc/vae_wide.hip); a model may mix them.  A model with a width above 64 has the decoder only:
-    its encoder and training entry points raise NotImplementedError (the wide encoder, and 512 channels, the full-size
-    Counter-Strike VAE, are out of scope)."""
+    NotImplementedError here.  Blocks of up to 64 channels run on the register-tile kernels (csrc/vae.hip, csrc/vae_encoder.hip),
+    wider ones on the fp32 MFMA tile kernels (csrc/vae_wide.hip), encoder and decoder alike; a model may mix them.  A model
+    with a width above 64 runs for inference only: the training path of `forward` raises NotImplementedError (training at
+    those widths, and 512 channels, the full-size Counter-Strike VAE, are out of scope)."""
 
     def __init__(self, channels, n_res_blocks, time_compressions=[1, 2, 2], spatial_compressions=[1, 2, 2], mean=None, std=None):
         super().__init__()
@@ -369,9 +385,15 @@ class VAE(BetterModule):
         carried cache is not supported), and so does an x that requires grad (frames are data: no gradient is produced for them).
 
         In eval mode or under torch.no_grad() it is encode -> mix -> decode on the inference kernels: real caches are carried
-        under cache["encoder"] / cache["decoder"] and the outputs have no grad_fn."""
+        under cache["encoder"] / cache["decoder"] and the outputs have no grad_fn.  A model with a block wider than MAX_NARROW has
+        this path only: its training path raises NotImplementedError that names the width."""
         self._check_frames("forward", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
-        self._refuse_wide("forward")
+        if self._wide:                                       # said before anything else is looked at, wherever the model lives
+            self._encoder_device("forward", x)
+            if self.training and torch.is_grad_enabled():
+                raise NotImplementedError(f"VAE.forward: this model has a block of {self._wide} channels: above {MAX_NARROW} the "
+                                          f"encoder and decoder run for inference only (eval mode or torch.no_grad()); for "
+                                          f"training at that width use {_REF}")
         B = x.shape[0]
         if t_sample is not None and (t_sample.dim() != 1 or t_sample.shape[0] != B):
             raise ValueError(f"VAE.forward: t_sample must be ({B},), got {tuple(t_sample.shape)}")
@@ -534,7 +556,10 @@ class VAE(BetterModule):
     # ---- the encoder
     def _pack_encoder(self, device):
         """fp32 copies of the encoder's parameters on `device` in the layouts of csrc/vae_encoder.hip and csrc/vae_conv3.h, rebuilt
-        when a parameter changed.  pk["params"] names every state_dict entry that went into it."""
+        when a parameter changed.  pk["params"] names every state_dict entry that went into it.  A block wider than MAX_NARROW
+        carries wide=True and its ResBlocks the layouts of csrc/vae_wide_conv.h; its `down`, and that of any block compressing
+        more than MAX_DOWN_K channels, carries wide_down=True and the GEMM layout (_pack_down_wide).  Every other block holds
+        exactly what it held before there were wide ones."""
         params = list(self.encoder.parameters())
         sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
         pk = self.__dict__.get("_oniris_vae_enc_pack")
@@ -545,27 +570,36 @@ class VAE(BetterModule):
         with torch.no_grad():
             for i, blk in enumerate(self.encoder.encoder_blocks):
                 Cin, C, g = self.encoder.in_channels[i], self.encoder.out_channels[i], self.encoder.group_sizes[i]
-                K = Cin * blk.time_compression * blk.spatial_compression ** 2
-                if K > 512:
-                    raise NotImplementedError(f"VAE encoder: block {i} compresses {K} channels: the HIP kernel takes up to 512")
-                g4 = (C + 3) // 4 * 4
-                wd = torch.zeros(K, 2, g4, **f32)              # per k = ((tc hc) wc) c: the conv weights | the area windows
-                wd[:, 0, :C] = blk.compression_block.weight.detach().to(**f32).reshape(C, K).t()
-                bd = torch.ones(2, g4, **f32)                  # the bias | the window lengths
-                bd[0] = 0
-                bd[0, :C] = blk.compression_block.bias.detach().to(**f32)
-                for o, (s0, s1) in enumerate(_area_windows(K, C)):
-                    wd[s0:s1, 1, o] = 1
-                    bd[1, o] = s1 - s0
+                npos = blk.time_compression * blk.spatial_compression ** 2
+                K = Cin * npos
+                wide, wide_down = C > MAX_NARROW, C > MAX_NARROW or K > MAX_DOWN_K
+                if wide_down:                                  # the GEMM of csrc/vae_wide_conv.h
+                    wd, bd = _pack_down_wide(blk.compression_block.weight, blk.compression_block.bias, Cin, C, npos, f32)
+                else:
+                    g4 = (C + 3) // 4 * 4
+                    wd = torch.zeros(K, 2, g4, **f32)          # per k = ((tc hc) wc) c: the conv weights | the area windows
+                    wd[:, 0, :C] = blk.compression_block.weight.detach().to(**f32).reshape(C, K).t()
+                    bd = torch.ones(2, g4, **f32)              # the bias | the window lengths
+                    bd[0] = 0
+                    bd[0, :C] = blk.compression_block.bias.detach().to(**f32)
+                    for o, (s0, s1) in enumerate(_area_windows(K, C)):
+                        wd[s0:s1, 1, o] = 1
+                        bd[1, o] = s1 - s0
                 pre = f"encoder.encoder_blocks.{i}."
                 names += [pre + "compression_block.weight", pre + "compression_block.bias"]
                 res = []
                 for j, rb in enumerate(blk.res_blocks):
-                    res.append(_pack_res(rb, C, g, f32))
+                    res.append((_pack_res_wide if wide else _pack_res)(rb, C, g, f32))
                     names += [pre + f"res_blocks.{j}.{n}" for n in ("conv3d0.conv3d.weight", "conv3d0.conv3d.bias", "conv3d1.weight",
                                                                    "conv3d1.bias")]
-                blocks.append(dict(Cin=Cin, C=C, g=g, nch=_nch(C), gpt=_gpt(C, g), tc=blk.time_compression, sc=blk.spatial_compression,
-                                   wd=wd.contiguous(), bd=bd, res=res))
+                nch, gpt = (0, 0) if wide else (_nch(C), _gpt(C, g))
+                bk = dict(Cin=Cin, C=C, g=g, nch=nch, gpt=gpt, tc=blk.time_compression, sc=blk.spatial_compression,
+                          wd=wd.contiguous(), bd=bd, res=res)
+                if wide:
+                    bk["wide"] = True
+                if wide_down:
+                    bk["wide_down"] = True
+                blocks.append(bk)
             pk = dict(sig=sig, blocks=blocks, params=names, zeros={})
         self.__dict__["_oniris_vae_enc_pack"] = pk
         return pk
@@ -581,16 +615,24 @@ class VAE(BetterModule):
             raise ValueError(f"VAE.{what}: frames of {H} x {W}: height and width must be positive multiples of the spatial "
                              f"compression {scomp}")
 
-    def _refuse_wide(self, what):
-        """A model with a decoder block wider than MAX_NARROW has no native encoder: said after the shape checks, before anything
-        is packed or launched, wherever the model lives."""
-        if self._wide:
-            raise NotImplementedError(f"VAE.{what}: this model has a block of {self._wide} channels: above {MAX_NARROW} only the "
-                                      f"decoder (decode, decode_frames, latents_to_frames) runs natively; for the encoder and "
-                                      f"training at that width use {_REF}")
+    def _check_groups(self, T):
+        """Block i sees T / (its cumulative time compression) frames in groups of g_i, and every group must be whole; the default
+        compressions ask for no more than _check_frames does.  Said once the model is known to run (after the device check)."""
+        need = 1
+        for i in range(len(self.encoder.encoder_blocks)):
+            need = int(np.lcm(need, self.encoder.group_sizes[i] * int(np.prod(self.encoder.time_compressions[:i + 1]))))
+        if T % need != 0:
+            raise ValueError(f"VAE encoder: {T} frames: with time compressions {list(self.encoder.time_compressions)} every block must "
+                             f"see whole groups of frames (group sizes {self.encoder.group_sizes}), so the number of frames, of a "
+                             f"chunk too, must be a multiple of {need} (as in the reference)")
 
     def _encoder_device(self, what, x=None):
+        """The device the encoder runs on; a model or an input on the CPU is refused, after the shape checks and before anything is
+        packed or launched.  A model with a block wider than MAX_NARROW says so: its refusal names the widest width."""
         dev = self.device if x is None else x.device
+        if (dev.type != "cuda" or self.device.type != "cuda") and self._wide:
+            raise NotImplementedError(f"VAE.{what}: this model has a block of {self._wide} channels: the encoder and the decoder at "
+                                      f"that width run on HIP kernels only (model and input on the GPU); on the CPU use {_REF}")
         if dev.type != "cuda" or self.device.type != "cuda":
             raise NotImplementedError(f"VAE.{what}: the encoder runs on HIP kernels only (model and input on the GPU); on the CPU "
                                       f"use {_REF}")
@@ -600,6 +642,7 @@ class VAE(BetterModule):
         """x: fp32 or uint8 frames addressed by element strides (b, t, h, w, c); returns (mean (B, C, t, h, w) | normalised latents
         (B, t, C, h, w), cache)."""
         B, dev = x.shape[0], x.device
+        self._check_groups(T)
         pk = self._pack_encoder(dev)
         s = _stream()
         zeros = pk["zeros"].get(B)
@@ -611,8 +654,9 @@ class VAE(BetterModule):
             T, H, W = T // bk["tc"], H // bk["sc"], W // bk["sc"]
             x = down(x, strides, (B, T, H, W), normalize, bk, s)
             strides, normalize = x.stride()[:4] + (1,), False
+            # a wide block's activation pass takes a null FiLM pointer
             x, new_cache[f"encoder_block_{i}"] = self._res_blocks("encoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),
-                                                                  lambda rb: _p(zeros), s)
+                                                                  lambda rb: None if bk.get("wide") else _p(zeros), s)
         if want == "latents":
             return latents(x, s, self.mean.to(device=dev, dtype=torch.float32).contiguous(),
                            self.std.to(device=dev, dtype=torch.float32).contiguous()), new_cache
@@ -624,7 +668,6 @@ class VAE(BetterModule):
         reference's keys cache['encoder_block_{i}']['res_block_{j}']['conv3d_res0'], the last g activated input frames of every
         group-causal conv as opaque channels-last (B, g, H, W, C) fp32 tensors; pass it back to continue the sequence."""
         self._check_frames("encode", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
-        self._refuse_wide("encode")
         self._encoder_device("encode", x)
         x = x.float()
         sb, sc, st, sh, sw = x.stride()
@@ -636,7 +679,6 @@ class VAE(BetterModule):
         mean (vae.py:250-259).  split_size must be a multiple of the time compression."""
         self._check_frames("encode_long_sequence", frames.shape, "frames (B, {c}, T, H, W)",
                            *(frames.shape if frames.dim() == 5 else (None,) * 5))
-        self._refuse_wide("encode_long_sequence")
         if split_size <= 0 or split_size % int(self.time_compression) != 0:
             raise ValueError(f"VAE.encode_long_sequence: split_size {split_size} must be a positive multiple of the time compression "
                              f"{int(self.time_compression)}")
@@ -652,10 +694,10 @@ class VAE(BetterModule):
         """Streaming frames_to_latents: frames (B, 4t, H, W, 3) with values 0..255, uint8 or any real dtype, on the GPU ->
         (latents (B, t, C, h, w) fp32, normalised as Precond and the sampler take them, cache).  uint8 frames are read in place and
         frames / 127.5 - 1 is applied on load.  Feed the returned cache to the next call: chunk by chunk (the smallest chunk is one
-        latent frame), the result equals frames_to_latents over the whole sequence."""
+        latent frame; two where a time compression of 1 follows one of 2, as in channels=[3,16,64,256,8]: every block must see
+        whole groups), the result equals frames_to_latents over the whole sequence."""
         B, T, H, W, C = frames.shape if frames.dim() == 5 else (None,) * 5
         self._check_frames("encode_frames", frames.shape, "frames (B, T, H, W, {c})", B, C, T, H, W)
-        self._refuse_wide("encode_frames")
         self._encoder_device("encode_frames", frames)
         if not hasattr(self, "mean"):
             raise RuntimeError("VAE: frames_to_latents needs the `mean` / `std` constructor arguments (as in the reference)")

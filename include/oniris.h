@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*); guided sampling: OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*), the wide encoder's oniris_vae_wide_down among them; guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
@@ -665,7 +665,7 @@ int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int
                    const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc,
                    uint8_t* frames, oniris_stream_t stream);
 
-/* VAE decoder at block widths above 64 channels, added within ABI 14 (nothing above changed).  fp32 throughout, channels-last
+/* VAE decoder (and the encoder's stages, see oniris_vae_wide_down) at block widths above 64 channels, added within ABI 14 (nothing above changed).  fp32 throughout, channels-last
  * [B][T][H][W][C]; the caller allocates every buffer and nothing synchronises.  csrc/vae_wide.hip; the tile kernel is
  * csrc/vae_wide_conv.h over csrc/disc_parts.h (16x16 pixel tiles on v_mfma_f32_32x32x2_f32).  A wide ResBlock is four launches,
  * act, conv_a, act, conv_b, and the convs take operands that are ALREADY activated.  In every packed layout CP = the width
@@ -684,6 +684,12 @@ int oniris_vae_out(const float* x, const float* w, const float* bias, int B, int
  *   :148-164); x contiguous [B][T][H][W][C]; w packed [CinP][tc sc^2 CP] (conv channel sub C + c at sub CP + c, sub = (tq sc + hq)
  *   sc + wq), bias [tc sc^2][CP].
  * oniris_vae_wide_out: oniris_vae_out for Cin above 64, same arguments, except w packed [CinP][CP of Cout], bias [CP].
+ * oniris_vae_wide_down: oniris_vae_down (the same arguments and meaning: the rearrangement, the compression 1x1 conv K = Cin tc sc^2
+ *   -> Cout and the channel-area residual, x fp32 or uint8 through element strides, normalize on load) as a GEMM for any Cin and
+ *   Cout up to 65536, so for a wide output or K above 512; w packed [tc sc^2][CinP][CP] (rearranged channel k = pos Cin + c, pos =
+ *   (tq sc + hq) sc + wq, at [pos][c]), bias [CP]; out contiguous [B][To][Ho][Wo][Cout], not x.  out = (conv + bias) + area / len,
+ *   the conv summed in the order sub-position, 16-channel chunk, channel pair, the area window in ascending k.  The encoder's wide
+ *   ResBlocks are oniris_vae_wide_act (emb NULL) / _conv_a / _act / _conv_b above.
  * Every output is summed in the order time tap, 16-channel chunk, spatial tap, channel pair, then the bias and the residual; it
  * depends on neither T, nor B, nor where the sequence was cut.                                                                 */
 int oniris_vae_wide_temb(const float* params, const int32_t* table, int n_res_blocks, int max_c2, const float* t, int B, float* emb,
@@ -699,6 +705,9 @@ int oniris_vae_wide_up(const float* x, const float* w, const float* bias, float*
 int oniris_vae_wide_out(const float* x, const float* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout, int split,
                         const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh, int64_t sw,
                         int64_t sc, uint8_t* frames, oniris_stream_t stream);
+int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B, int To, int Ho,
+                         int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w, const float* bias, int Cout,
+                         float* out, oniris_stream_t stream);
 
 /* VAE encoder (reference: EncoderDecoder(type='encoder') vae.py:96-204, VAE.encode :239-241), inference, fp32 throughout.
  * csrc/vae_encoder.hip.  Its ResBlocks are oniris_vae_res_a / oniris_vae_res_b with a zero emb buffer (the encoder passes
@@ -709,7 +718,7 @@ int oniris_vae_wide_out(const float* x, const float* w, const float* bias, int B
  * channel k the conv weights, then 1 where k lies in output o's area window [floor(o K / Cout), ceil((o + 1) K / Cout)) and
  * 0 elsewhere; bias packed [2][G4]: the bias, then the window lengths (1 beyond Cout).  x is addressed through element strides sb / st / sh / sw / sc and holds To tc x Ho sc x Wo sc
  * pixels of Cin channels, fp32 or (x_is_u8) uint8; normalize: x / 127.5 - 1 is applied on load (vae.py:271).
- * K <= 512, Cout <= 64, tc and sc in {1, 2}.
+ * K <= 512, Cout <= 64, tc and sc in {1, 2} (beyond either: oniris_vae_wide_down).
  * oniris_vae_latents: x channels-last [B][T][H][W][C] -> out through element strides, as it is (mean / std NULL) or
  * (x - mean[c]) / std[c].  The summation order of every output is fixed (rearranged channel ascending, bias, residual): an
  * encode in chunks through the cache is bit-identical to the whole sequence.                                                */
