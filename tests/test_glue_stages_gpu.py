@@ -34,6 +34,7 @@ import pytest
 import torch
 
 import glue_oracle as GO
+from oracle_hold import out as _out, ratio as _ratio, hold_bf16, hold_f32, hold_exact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -75,37 +76,7 @@ def _g(t):
     return None if t is None else t.to(DEV).contiguous()
 
 
-def _out(*shape, dtype=BF16, fill=NAN):
-    """An output buffer the kernel must write completely: pre-filled with NaN (accumulators: zeros)."""
-    return torch.full(shape, fill, dtype=dtype, device=DEV)
-
-
-def _ratio(case, name, got, ref, bound):
-    got = got.detach().double().cpu().reshape(ref.shape)
-    assert bool(torch.isfinite(got).all()), f"{case} {name}: non-finite values (an element the kernel never wrote?)"
-    err = (got - ref).abs()
-    live = bound > 0
-    dead_ok = bool((err[~live] == 0).all())
-    worst = (err[live] / bound[live]).max().item() if bool(live.any()) else 0.0
-    print(f"GLUE {case} {name} {worst:.3f}")
-    assert dead_ok, f"{case} {name}: an element whose reference is exactly 0 came back non-zero"
-    assert worst <= 1.0, f"{case} {name}: worst |got - ref| / bound = {worst:.3f} over {err.numel()} elements"
-
-
-def hold_bf16(case, name, got, pair):
-    _ratio(case, name, got, pair[0], GO.bound_bf16(*pair))
-
-
-def hold_f32(case, name, got, pair):
-    _ratio(case, name, got, pair[0], GO.bound_f32(pair[1]))
-
-
-def hold_exact(case, name, got, ref):
-    got = got.detach().cpu()
-    ref = ref.reshape(got.shape)
-    assert bool(torch.isfinite(got.float()).all()), f"{case} {name}: non-finite values"
-    assert bool((got.double() == ref.double()).all()), f"{case} {name}: {int((got.double() != ref.double()).sum())} elements differ (exact probe)"
-    print(f"GLUE {case} {name} exact")
+# (the NaN-prefilled buffers and the three kinds of comparison are shared with test_step_edge_gpu.py: tests/oracle_hold.py)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
