@@ -7,14 +7,17 @@
 // Forward / dQ: one workgroup = 128 query rows (4 waves x 32 rows), S^T = K.Q^T is computed with the KEY index on
 // the MFMA rows and the QUERY on the lanes, so a lane owns one query row: row max / row sum are 32 in-register ops
 // plus one cross-half shuffle, and the S^T accumulator is directly the B operand of O^T += V^T.P^T (no LDS round
-// trip).  K / V tiles (64 keys) are prefetched into registers one tile ahead and staged row-major in LDS (144-byte
-// rows); row fragments are 16-byte reads, the transposed operands (V^T, K^T, Q^T, dO^T: MFMA k index = token) come
+// trip).  K / V tiles (64 keys) go global -> LDS by LDS-DMA one tile ahead, row-major in unpadded, swizzled 128-byte
+// rows; row fragments are 16-byte reads, the transposed operands (V^T, K^T, Q^T, dO^T: MFMA k index = token) come
 // from the SAME tiles through the gfx950 transposing read ds_read_b64_tr_b16.  dK/dV: one workgroup = 128 keys,
 // lane = key, S = Q.K^T with queries on the rows, P and dS feed dV^T += dO^T.P and dK^T += Q^T.dS from registers.
+// The tile images, their fragment reads, the own-row load, the lane-row store, the table row in a VGPR and the tile
+// copies are in attention_parts.h, shared with the persistent (attention_*ws.h) and frame (attention_frame.h) kernels.
 #include <type_traits>
 #include "common.h"
 #include "lds_dma.h"
 #include "../../include/oniris.h"
+#include "attention_parts.h"
 
 #define NEG_BIG (-1.0e30f)
 // Softmax without a running maximum: VideoAttention / FrameAttention L2-normalise every 64-vector of q and k to
@@ -24,7 +27,6 @@
 // VALU-bound at head dim 64: 256 MFMA FLOP per score element against ~10 VALU instructions with a running max).
 #define SOFTMAX_OFF 12.0f
 #define SCALE_LOG2 (0.125f * 1.4426950408889634f)
-#define KROW 144   // bytes per row of a [64 tok][64 ch] bf16 tile (128 + 16 pad)
 
 struct AttnDev {
   OnirisAttnArgs a;
@@ -77,39 +79,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& v, int s2) {
   return o;
 }
 
-// ---- 64-token x 64-channel bf16 tiles: global -> registers (prefetch) -> LDS rows of KROW bytes -----------------
-__device__ __forceinline__ void tile_load(u32x4 (&v)[2], const bf16* g, int tok0, int L, int C, int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + i * 256;
-    const int row = e >> 3, part = e & 7;
-    v[i] = u32x4{0u, 0u, 0u, 0u};
-    if (tok0 + row < L) v[i] = *(const u32x4*)(g + (size_t)(tok0 + row) * C + part * 8);
-  }
-}
-__device__ __forceinline__ void tile_store(unsigned char* lds, const u32x4 (&v)[2], int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + i * 256;
-    *(u32x4*)(lds + (e >> 3) * KROW + (e & 7) * 16) = v[i];
-  }
-}
-// Transposed fragment of a row-major tile via the gfx950 transposing LDS read: this lane gets channel
-// chbase + (lane & 31) of the 8 tokens {tokbase + 4h + 0..3, tokbase + 8 + 4h + 0..3} -- exactly the k order in which
-// an S^T / P accumulator (rows = tokens) is consumed as the other MFMA operand.
-__device__ __forceinline__ bf16x8 trfrag(const unsigned char* lds, int tokbase, int chbase, int lane) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const int grp = lane >> 4, hh = grp >> 1, q = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const unsigned char* p0 = lds + (tokbase + 4 * hh + q) * KROW + (chbase + pcol) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * KROW));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 // XCD-aware workgroup order: hardware deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own
 // 4 MB L2).  All workgroups of one (batch, head) pair read the same K / V (1 MB each at L = 8192), so a pair is
 // pinned to ONE XCD whenever the number of pairs is a multiple of 8: x = position inside the pair's row of the grid,
@@ -134,8 +103,8 @@ __device__ __forceinline__ void attn_block_decode(int& x, int& head, int& b) {
 // forward.  K / V tiles (64 keys x 64 channels, 128-byte rows) go global -> LDS by LDS-DMA into two alternating
 // buffers: the copy of tile i+1 runs under the MFMA / softmax work of tile i, one barrier per tile, no staging
 // registers.  The rows are unpadded (the DMA image is lane-linear), so the 16-byte pieces are XOR-swizzled on the
-// source side: K (read row-wise, ds_read_b128, 16 rows per access group) with (row>>1)&7, V (read through the
-// transposing ds_read_b64_tr_b16, 4 rows x 64 bytes) with 4*bit1(row).
+// source side: K (read row-wise, ds_read_b128, 16 rows per access group) in the row image, V (read through the
+// transposing ds_read_b64_tr_b16, 4 rows x 64 bytes) in the transposing image of attention_parts.h.
 // KS key streams per workgroup: the 4 waves are 4/KS query waves (32 rows each) x KS streams; stream j walks the key
 // tiles j, j+KS, ... of the block's list (own LDS buffers) and the streams' (O, l) partial results meet in LDS at the
 // end -- without a running max they simply add.  With a causal table the last query blocks have the longest lists
@@ -165,84 +134,40 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnDev d) {
 
   const bf16* qg = (const bf16*)a.q + (size_t)b * Lq * C + head * 64;
   bf16x8 qf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    u32x4 v = u32x4{0u, 0u, 0u, 0u};
-    if (qrow < Lq) v = *(const u32x4*)(qg + (size_t)qrow * C + ks * 16 + h * 8);
-    qf[ks] = __builtin_bit_cast(bf16x8, v);
-  }
+  own_row(qf, qg + (size_t)qrow * C + h * 8, qrow < Lq);
   f32x16 o[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { o[0][i] = 0.f; o[1][i] = 0.f; }
   float l2[2] = {0.f, 0.f};                        // this lane's half of the row sum (two chains: packed adds)
 
-  const int trow = qb >> d.tshift, tmask = (1 << d.tshift) - 1;
-  const int nkv = a.kv_num ? (a.kv_num[trow] << d.tshift) : (Lk + 127) / 128;
-  const int nsub = nkv * 2;
-  // the row's block list sits in one VGPR (lane i = entry i; rows with more than 64 entries fall back to memory):
-  // a scalar load per tile put ~1 us of load latency into every iteration
-  const int nent = a.kv_num ? a.kv_num[trow] : 0;
-  const int kvl = (a.kv_idx && lane < nent) ? a.kv_idx[(size_t)trow * a.tab_cols + lane] : 0;
-  asm volatile("" ::"v"(kvl));                      // consume the ordinary load before any LDS-DMA is in flight
-  auto key_start = [&](int idx) __attribute__((always_inline)) {
-    const int j = idx >> 1, jj = j >> d.tshift;
-    int e = j;
-    if (a.kv_idx) e = ((nent <= 64 ? __builtin_amdgcn_readlane(kvl, jj) : a.kv_idx[(size_t)trow * a.tab_cols + jj]) << d.tshift) + (j & tmask);
-    return e * 128 + (idx & 1) * 64;
-  };
+  const BlockList kvl = block_list(a.kv_num, a.kv_idx, a.tab_cols, qb >> d.tshift, d.tshift, lane, Lk);
+  const int nsub = kvl.nsub;
 
-  // DMA descriptors: NPC 16-byte pieces per thread and tile
-  constexpr int OOB = (int)0x80000000;
-  int kvo[NPC], vvo[NPC], prow[NPC];
-#pragma unroll
-  for (int i = 0; i < NPC; ++i) {
-    const int e = i * NTS + tis, row = e >> 3, pp = e & 7;
-    prow[i] = row;
-    kvo[i] = (row * C + head * 64 + (pp ^ ((row >> 1) & 7)) * 8) * 2;
-    vvo[i] = (row * C + head * 64 + (pp ^ (4 * ((row >> 1) & 1))) * 8) * 2;
-  }
+  // DMA descriptors: K in the row image, V in the transposing image
+  const TilePieces<NPC> pcs = tile_pieces<IMG_ROW, IMG_TR, NPC, NTS>(tis, C, head);
   const i32x4 rs_k = make_rsrc((const bf16*)a.k + (size_t)b * (a.k_bstride ? (size_t)a.k_bstride : (size_t)Lk * C), Lk * C * 2);
   const i32x4 rs_v = make_rsrc((const bf16*)a.v + (size_t)b * (a.v_bstride ? (size_t)a.v_bstride : (size_t)Lk * C), Lk * C * 2);
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
   auto issue = [&](int key0, int bsel) __attribute__((always_inline)) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (st * 2 + bsel) * 2 * TB + qwv * 1024);
-    const int left = Lk - key0, so = key0 * C * 2;
-#pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-      const bool ok = prow[i] < left;
-      dma16(rs_k, ok ? kvo[i] : OOB, so, dst + i * (NTS * 16));
-      dma16(rs_v, ok ? vvo[i] : OOB, so, dst + TB + i * (NTS * 16));
-    }
+    tile_issue<NPC, NTS>(pcs, rs_k, rs_v, key0, Lk, C, __builtin_amdgcn_readfirstlane(lds0 + (st * 2 + bsel) * 2 * TB + qwv * 1024));
   };
   // fragment addresses
-  const int kb0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);                 // K rows kt*32 + r, k-step ks: ^ (ks*32), + kt*4096
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const int vb0 = (4 * hh + q4) * 128 + pcol * 2, vsw = (q4 >> 1) & 1;    // V^T: + tokbase*128 + ((dt ^ vsw)*64)
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto vtr = [&](const unsigned char* vt, int tokbase, int dt) __attribute__((always_inline)) {
-    const unsigned char* p0 = vt + vb0 + tokbase * 128 + ((dt ^ vsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * 128));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const int kb0 = row_frag_base(r, h, row_image(r));                     // K rows kt*32 + r
+  const TrLane vt = tr_lane(lane);                                       // V^T
 
   int bsel = 0;
   const int sub0 = (nsp == 1) ? 0 : (int)((long long)nsub * sp / nsp);                    // this split's tiles
   const int sub1 = (nsp == 1) ? nsub : (int)((long long)nsub * (sp + 1) / nsp);
-  if (sub0 + st < sub1) issue(key_start(sub0 + st), 0);
+  if (sub0 + st < sub1) issue(kvl.start(sub0 + st), 0);
   const int niter = (sub1 - sub0 + KS - 1) / KS;
 #pragma unroll 1
   for (int it = 0; it < niter; ++it) {
     const int idx = sub0 + it * KS + st;
     const bool act = idx < sub1;
-    const int key0 = act ? key_start(idx) : 0;
+    const int key0 = act ? kvl.start(idx) : 0;
     dma_wait();
     __syncthreads();                               // tile idx has landed for everybody; buffer bsel^1 is free again
-    if (idx + KS < sub1) issue(key_start(idx + KS), bsel ^ 1);
+    if (idx + KS < sub1) issue(kvl.start(idx + KS), bsel ^ 1);
     const unsigned char* Kt = smem + (st * 2 + bsel) * 2 * TB;
     const unsigned char* Vt = Kt + TB;
     bsel ^= 1;
@@ -255,15 +180,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnDev d) {
     // complete under the S MFMAs and the softmax, nothing in the chain below waits for LDS
     bf16x8 kf[2][4], vf[2][2][2];
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) kf[kt][ks] = *(const bf16x8*)(Kt + ((kb0 ^ (ks * 32)) + kt * 4096));
+    for (int kt = 0; kt < 2; ++kt) row_frag(kf[kt], Kt, kb0, kt * 4096);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) vf[kt][s2][dt] = vtr(Vt, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) vf[kt][s2][dt] = tr_read(Vt, vt, kt * 32 + 16 * s2, dt);
     f32x16 s[2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
@@ -324,25 +247,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnDev d) {
   if (nsp > 1) {                                   // partial of this split: [split][b][head][q][64 channels | l] fp32
     float* pw = a.split_ws + ((((size_t)sp * a.B + b) * a.heads + head) * Lq + qrow) * 65;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < 2; ++dt)                   // (rows of 65 floats: not 16-byte aligned, scalar stores)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) pw[dt * 32 + 8 * g + 4 * h + k] = o[dt][4 * g + k];
+        for (int k = 0; k < 4; ++k) pw[lane_row_ch(dt, g, h) + k] = o[dt][4 * g + k];
     if (h == 0) pw[64] = l;
     return;
   }
   const float inv = (l > 0.f) ? 1.f / l : 0.f;
-  bf16* og = (bf16*)a.out + ((size_t)b * Lq + qrow) * C + head * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 ov;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ov[k] = f2bf(o[dt][4 * g + k] * inv);
-      *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-    }
+  lane_row_store((bf16*)a.out + ((size_t)b * Lq + qrow) * C + head * 64, o, inv, h);
   if (a.lse && h == 0) a.lse[(size_t)(b * a.heads + head) * Lq + qrow] = SOFTMAX_OFF + log2f(fmaxf(l, 1e-30f));
 #endif
 }
@@ -380,7 +294,7 @@ __global__ void attn_split_reduce_kernel(const float* __restrict__ ws, bf16* __r
 // ================================================================================================================
 // backward: dQ   (the forward's structure: lane = query row, LDS-DMA double-buffered K / V tiles, KS key streams
 // whose partial dQ add up in LDS).  K is read both row-wise (S^T = K.Q^T) and transposed (dQ^T += K^T.dS^T): it is
-// staged once, in the dual-use image of attention_bwd_ws.h (conflict-free for both kinds of read); V is only read
+// staged once, in the dual-use image of attention_parts.h (conflict-free for both kinds of read); V is only read
 // row-wise (dP^T = V.dO^T).
 template <int MODE, int KS>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnDev d) {
@@ -403,16 +317,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnDev d) {
   const bf16* qg = (const bf16*)a.q + (size_t)b * Lq * C + head * 64;
   const bf16* dog = (const bf16*)a.dout + (size_t)b * Lq * C + head * 64;
   bf16x8 qf[4], dof[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u};
-    if (qrow < Lq) {
-      v = *(const u32x4*)(qg + (size_t)qrow * C + ks * 16 + h * 8);
-      w = *(const u32x4*)(dog + (size_t)qrow * C + ks * 16 + h * 8);
-    }
-    qf[ks] = __builtin_bit_cast(bf16x8, v);
-    dof[ks] = __builtin_bit_cast(bf16x8, w);
-  }
+  own_row(qf, qg + (size_t)qrow * C + h * 8, qrow < Lq);
+  own_row(dof, dog + (size_t)qrow * C + h * 8, qrow < Lq);
   float lse = 0.f, delta = 0.f;
   if (qrow < Lq) {
     lse = a.lse[(size_t)(b * a.heads + head) * Lq + qrow];
@@ -423,75 +329,33 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnDev d) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
 
-  const int trow = qb >> d.tshift, tmask = (1 << d.tshift) - 1;
-  const int nkv = a.kv_num ? (a.kv_num[trow] << d.tshift) : (Lk + 127) / 128;
-  const int nsub = nkv * 2;
-  // the row's block list sits in one VGPR (lane i = entry i; rows with more than 64 entries fall back to memory):
-  // a scalar load per tile put ~1 us of load latency into every iteration
-  const int nent = a.kv_num ? a.kv_num[trow] : 0;
-  const int kvl = (a.kv_idx && lane < nent) ? a.kv_idx[(size_t)trow * a.tab_cols + lane] : 0;
-  asm volatile("" ::"v"(kvl));                      // consume the ordinary load before any LDS-DMA is in flight
-  auto key_start = [&](int idx) __attribute__((always_inline)) {
-    const int j = idx >> 1, jj = j >> d.tshift;
-    int e = j;
-    if (a.kv_idx) e = ((nent <= 64 ? __builtin_amdgcn_readlane(kvl, jj) : a.kv_idx[(size_t)trow * a.tab_cols + jj]) << d.tshift) + (j & tmask);
-    return e * 128 + (idx & 1) * 64;
-  };
+  const BlockList kvl = block_list(a.kv_num, a.kv_idx, a.tab_cols, qb >> d.tshift, d.tshift, lane, Lk);
+  const int nsub = kvl.nsub;
 
-  constexpr int OOB = (int)0x80000000;
-  int kvo[NPC], vvo[NPC], prow[NPC];
-#pragma unroll
-  for (int i = 0; i < NPC; ++i) {
-    const int e = i * NTS + tis, row = e >> 3, pp = e & 7;
-    prow[i] = row;
-    // K is read row-wise (S^T) AND transposed (dQ^T): one image, chunk c of row R at c ^ f(R), f = bit1 << 2 | bit3 << 1 | bit2,
-    // is conflict-free for both (attention_bwd_ws.h)
-    kvo[i] = (row * C + head * 64 + (pp ^ ((((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1) | ((row >> 2) & 1))) * 8) * 2;
-    vvo[i] = (row * C + head * 64 + (pp ^ ((row >> 1) & 7)) * 8) * 2;            // V: row-read swizzle
-  }
+  // K is read row-wise (S^T) AND transposed (dQ^T): the dual-use image; V: the row image
+  const TilePieces<NPC> pcs = tile_pieces<IMG_DUAL, IMG_ROW, NPC, NTS>(tis, C, head);
   const i32x4 rs_k = make_rsrc((const bf16*)a.k + (size_t)b * Lk * C, Lk * C * 2);
   const i32x4 rs_v = make_rsrc((const bf16*)a.v + (size_t)b * Lk * C, Lk * C * 2);
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
   auto issue = [&](int key0, int bsel) __attribute__((always_inline)) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (st * 2 + bsel) * 2 * TB + qwv * 1024);
-    const int left = Lk - key0, so = key0 * C * 2;
-#pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-      const bool ok = prow[i] < left;
-      dma16(rs_k, ok ? kvo[i] : OOB, so, dst + i * (NTS * 16));
-      dma16(rs_v, ok ? vvo[i] : OOB, so, dst + TB + i * (NTS * 16));
-    }
+    tile_issue<NPC, NTS>(pcs, rs_k, rs_v, key0, Lk, C, __builtin_amdgcn_readfirstlane(lds0 + (st * 2 + bsel) * 2 * TB + qwv * 1024));
   };
-  // fragment addresses: row reads of K (tr swizzle: piece ^ 4*bit1(row)) and V (piece ^ ((row>>1)&7)); rows kt*32 + r
-  const int kr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);   // k-step ks: chunk (2ks+h) ^ f(r)
-  const int vr0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, c0 = 2 * (grp & 1) + ((lane & 3) >> 1);
-  const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (lane & 1);
-  const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (lane & 1);
-  const int tsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto ktr = [&](const unsigned char* kt_, int tokbase, int dt) __attribute__((always_inline)) {
-    const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbA + o));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbB + o));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  // fragment addresses: row reads of K (dual-use image) and V (row image), rows kt*32 + r; transposing reads of K
+  const int kr0 = row_frag_base(r, h, dual_image(r));
+  const int vr0 = row_frag_base(r, h, row_image(r));
+  const DualLane ktl = dual_lane(lane);
 
   int bsel = 0;
-  if (st < nsub) issue(key_start(st), 0);
+  if (st < nsub) issue(kvl.start(st), 0);
   const int niter = (nsub + KS - 1) / KS;
 #pragma unroll 1
   for (int it = 0; it < niter; ++it) {
     const int idx = it * KS + st;
     const bool act = idx < nsub;
-    const int key0 = act ? key_start(idx) : 0;
+    const int key0 = act ? kvl.start(idx) : 0;
     dma_wait();
     __syncthreads();
-    if (idx + KS < nsub) issue(key_start(idx + KS), bsel ^ 1);
+    if (idx + KS < nsub) issue(kvl.start(idx + KS), bsel ^ 1);
     const unsigned char* Kt = smem + (st * 2 + bsel) * 2 * TB;
     const unsigned char* Vt = Kt + TB;
     bsel ^= 1;
@@ -502,15 +366,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnDev d) {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       bf16x8 kf[4], vf[4], ktf[2][2];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        kf[ks] = *(const bf16x8*)(Kt + ((kr0 ^ (ks * 32)) + kt * 4096));
-        vf[ks] = *(const bf16x8*)(Vt + ((vr0 ^ (ks * 32)) + kt * 4096));
-      }
+      row_frag2(kf, vf, Kt, kr0, Vt, vr0, kt * 4096);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = ktr(Kt, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = dual_read(Kt, ktl, kt * 32 + 16 * s2, dt);
       f32x16 s, dp;
 #pragma unroll
       for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -554,16 +414,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnDev d) {
     for (int i = 0; i < 16; ++i) { dq[0][i] += red[(qwv * 32 + i) * 64 + lane]; dq[1][i] += red[(qwv * 32 + 16 + i) * 64 + lane]; }
   }
   if (qrow >= Lq) return;
-  bf16* og = (bf16*)a.dq + ((size_t)b * Lq + qrow) * C + head * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 ov;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ov[k] = f2bf(dq[dt][4 * g + k] * 0.125f);
-      *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-    }
+  lane_row_store((bf16*)a.dq + ((size_t)b * Lq + qrow) * C + head * 64, dq, 0.125f, h);
 #endif
 }
 
@@ -589,56 +440,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnDev d) {
   const bf16* kg = (const bf16*)a.k + (size_t)b * Lk * C + head * 64;
   const bf16* vg = (const bf16*)a.v + (size_t)b * Lk * C + head * 64;
   bf16x8 kf[4], vf[4];
+  own_row(kf, kg + (size_t)krow * C + h * 8, krow < Lk);
+  own_row(vf, vg + (size_t)krow * C + h * 8, krow < Lk);
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u};
-    if (krow < Lk) {
-      v = *(const u32x4*)(kg + (size_t)krow * C + ks * 16 + h * 8);
-      w = *(const u32x4*)(vg + (size_t)krow * C + ks * 16 + h * 8);
-    }
-    kf[ks] = __builtin_bit_cast(bf16x8, v);
-    vf[ks] = __builtin_bit_cast(bf16x8, w);
-    asm volatile("" ::"v"(kf[ks]), "v"(vf[ks]));    // consume the ordinary loads before any LDS-DMA is in flight
-  }
+  for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(kf[ks]), "v"(vf[ks]));    // consume the ordinary loads before any LDS-DMA is in flight
   f32x16 dk[2], dv[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
 
-  const int trow = kb >> d.tshift, tmask = (1 << d.tshift) - 1;
-  const int nq = a.q_num ? (a.q_num[trow] << d.tshift) : (Lq + 127) / 128;
-  const int nsub = nq * 2;
-  const int nent = a.q_num ? a.q_num[trow] : 0;      // (the row's block list in one VGPR: see attn_fwd_kernel)
-  const int qvl = (a.q_idx && lane < nent) ? a.q_idx[(size_t)trow * a.qtab_cols + lane] : 0;
-  asm volatile("" ::"v"(qvl));
-  auto q_start = [&](int idx) __attribute__((always_inline)) {
-    const int j = idx >> 1, jj = j >> d.tshift;
-    int e = j;
-    if (a.q_idx) e = ((nent <= 64 ? __builtin_amdgcn_readlane(qvl, jj) : a.q_idx[(size_t)trow * a.qtab_cols + jj]) << d.tshift) + (j & tmask);
-    return e * 128 + (idx & 1) * 64;
-  };
+  const BlockList qvl = block_list(a.q_num, a.q_idx, a.qtab_cols, kb >> d.tshift, d.tshift, lane, Lq);     // the key block's query list
+  const int nsub = qvl.nsub;
 
-  constexpr int OOB = (int)0x80000000;
-  int tvo[2], prow[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = i * 256 + tid, row = e >> 3, pp = e & 7;
-    prow[i] = row;
-    tvo[i] = (row * C + head * 64 + (pp ^ (4 * ((row >> 1) & 1))) * 8) * 2;
-  }
+  const TilePieces<2> pcs = tile_pieces<IMG_TR, IMG_TR, 2, 256>(tid, C, head);      // Q and dO: the transposing image
   const i32x4 rs_q = make_rsrc((const bf16*)a.q + (size_t)b * Lq * C, Lq * C * 2);
   const i32x4 rs_do = make_rsrc((const bf16*)a.dout + (size_t)b * Lq * C, Lq * C * 2);
   const i32x4 rs_l = make_rsrc(a.lse + (size_t)(b * a.heads + head) * Lq, Lq * 4);
   const i32x4 rs_d = make_rsrc(a.delta + (size_t)(b * a.heads + head) * Lq, Lq * 4);
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
   auto issue = [&](int q0, int bsel) __attribute__((always_inline)) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + bsel * BUFB + wave * 1024);
-    const int left = Lq - q0, so = q0 * C * 2;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool ok = prow[i] < left;
-      dma16(rs_q, ok ? tvo[i] : OOB, so, dst + i * 4096);
-      dma16(rs_do, ok ? tvo[i] : OOB, so, dst + TB + i * 4096);
-    }
+    const int left = Lq - q0;
+    tile_issue<2, 256>(pcs, rs_q, rs_do, q0, Lq, C, __builtin_amdgcn_readfirstlane(lds0 + bsel * BUFB + wave * 1024));
     if (wave == 0) {                               // lanes 0..15: lse[q0..q0+63], lanes 16..31: delta (16 B per lane)
       const unsigned sdst = __builtin_amdgcn_readfirstlane(lds0 + bsel * BUFB + 2 * TB);
       const int l16 = lane & 15;
@@ -648,30 +469,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnDev d) {
     }
   };
   // row fragments (rows qt*32 + r, 4-way conflict with this swizzle) and transposed fragments
-  const int rr0 = r * 128 + ((h ^ (4 * ((r >> 1) & 1))) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const int tb0 = (4 * hh + q4) * 128 + pcol * 2, tsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto ttr = [&](const unsigned char* t_, int tokbase, int dt) __attribute__((always_inline)) {
-    const unsigned char* p0 = t_ + tb0 + tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * 128));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const int rr0 = row_frag_base(r, h, tr_image(r));
+  const TrLane ttl = tr_lane(lane);
 
   const int i0 = (int)((long long)nsub * chunk / nch), i1 = (int)((long long)nsub * (chunk + 1) / nch);
   int bsel = 0;
-  if (i0 < i1) issue(q_start(i0), 0);
+  if (i0 < i1) issue(qvl.start(i0), 0);
 #pragma unroll 1
   for (int idx = i0; idx < i1; ++idx) {
-    const int q0 = q_start(idx);
+    const int q0 = qvl.start(idx);
     dma_wait();
     __syncthreads();
-    if (idx + 1 < i1) issue(q_start(idx + 1), bsel ^ 1);
+    if (idx + 1 < i1) issue(qvl.start(idx + 1), bsel ^ 1);
     const unsigned char* Qt = smem + bsel * BUFB;
     const unsigned char* dOt = Qt + TB;
     const float* lse_lds = (const float*)(Qt + 2 * TB);
@@ -685,17 +494,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnDev d) {
       if ((qq0 + 31 >= Lq || kw0 + 31 >= Lk) && cls == 2) cls = 1;
       if (cls == 0 || qq0 >= Lq) continue;
       bf16x8 qa[4], da[4], dotf[2][2], qtf[2][2];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        qa[ks] = *(const bf16x8*)(Qt + ((rr0 ^ (ks * 32)) + qt * 4096));
-        da[ks] = *(const bf16x8*)(dOt + ((rr0 ^ (ks * 32)) + qt * 4096));
-      }
+      row_frag2(qa, da, Qt, rr0, dOt, rr0, qt * 4096);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dotf[s2][dt] = ttr(dOt, qt * 32 + 16 * s2, dt);
-          qtf[s2][dt] = ttr(Qt, qt * 32 + 16 * s2, dt);
+          dotf[s2][dt] = tr_read(dOt, ttl, qt * 32 + 16 * s2, dt);
+          qtf[s2][dt] = tr_read(Qt, ttl, qt * 32 + 16 * s2, dt);
         }
       f32x16 s, dp;
 #pragma unroll
@@ -745,27 +550,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnDev d) {
     const size_t plane = (size_t)nch * a.B * Lk * C;
     float* pk = a.dkv_part + (((size_t)chunk * a.B + b) * Lk + krow) * C + head * 64;
     float* pv = pk + plane;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        *(float4*)(pk + dt * 32 + 8 * g + 4 * h) = make_float4(dk[dt][4 * g], dk[dt][4 * g + 1], dk[dt][4 * g + 2], dk[dt][4 * g + 3]);
-        *(float4*)(pv + dt * 32 + 8 * g + 4 * h) = make_float4(dv[dt][4 * g], dv[dt][4 * g + 1], dv[dt][4 * g + 2], dv[dt][4 * g + 3]);
-      }
+    lane_row_store_f32(pk, dk, h);
+    lane_row_store_f32(pv, dv, h);
     return;
   }
-  bf16* dkg = (bf16*)a.dk + ((size_t)b * Lk + krow) * C + head * 64;
-  bf16* dvg = (bf16*)a.dv + ((size_t)b * Lk + krow) * C + head * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 o1, o2;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { o1[k] = f2bf(dk[dt][4 * g + k] * (1.f / SCALE_LOG2)); o2[k] = f2bf(dv[dt][4 * g + k]); }   // dK^T was summed against q' = c q
-      *(bf16x4*)(dkg + dt * 32 + 8 * g + 4 * h) = o1;
-      *(bf16x4*)(dvg + dt * 32 + 8 * g + 4 * h) = o2;
-    }
+  lane_row_store((bf16*)a.dk + ((size_t)b * Lk + krow) * C + head * 64, dk, 1.f / SCALE_LOG2, h);      // dK^T was summed against q' = c q
+  lane_row_store((bf16*)a.dv + ((size_t)b * Lk + krow) * C + head * 64, dv, 1.f, h);
 #endif
 }
 

@@ -4,8 +4,8 @@
 // (oniris_attn_schedule: weight = key blocks of the table row + 1).
 //
 // Waves 4..7 = LOADERS: K | V blocks of 128 keys (32 KB) through a four-slot ring, three blocks ahead.  K carries the
-// dual-use image (chunk c of row R at c ^ f(R), f = bit1 << 2 | bit3 << 1 | bit2: conflict-free for the row reads of
-// S^T = K.Q^T AND the transposing reads of dQ^T += K^T.dS^T, see attention_bwd_ws.h), V the row-read swizzle.
+// dual-use image (conflict-free for the row reads of S^T = K.Q^T AND the transposing reads of dQ^T += K^T.dS^T, see
+// attention_parts.h), V the row image.
 //
 // Waves 0..3 = COMPUTE, wave w = query rows [32 w, 32 w + 32) of the block against EVERY key (no key split: dQ of a row
 // is finished by one lane group, nothing is merged).  Q / dO fragments and the row constants come straight from global
@@ -31,23 +31,20 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int C = a.C, Lq = a.Lq, Lk = a.Lk;
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-  const int nslots = a.sched_slots;
-  const int32_t* sched = a.sched + (size_t)blockIdx.x * nslots;
-  auto item_at = [&](int i) __attribute__((always_inline)) { return i < nslots ? __builtin_amdgcn_readfirstlane(sched[i]) : -1; };
+  const WorkList work_list{a.sched + (size_t)blockIdx.x * a.sched_slots, a.sched_slots};
   const int tmask = (1 << d.tshift) - 1;
 
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------------ loader waves
     const int lw = wave - 4;
     const int drow = 8 * lw + (lane >> 3), dpp = lane & 7;        // piece (lw + 4 i): row 32 i + drow, 16-byte part dpp
-    const int ksw = (dpp ^ ((((drow >> 1) & 1) << 2) | (((drow >> 3) & 1) << 1) | ((drow >> 2) & 1))) * 16;
-    const int vsw_ = (dpp ^ ((drow >> 1) & 7)) * 16;
-    constexpr int OOB = (int)0x80000000;
+    const int ksw = (dpp ^ dual_image(drow)) * 16;
+    const int vsw_ = (dpp ^ row_image(drow)) * 16;
     struct Src { i32x4 rs_k, rs_v; int kvo, vvo, nblk, kvl; };
     auto open_item = [&](int itm) __attribute__((always_inline)) {
       Src s;
-      const int pair = itm >> 16, qb128 = itm & 0xffff;
-      const int b = pair / a.heads, head = pair - b * a.heads;
+      const WorkItem wi = item_decode(itm, a.heads);
+      const int b = wi.b, head = wi.head, qb128 = wi.blk;
       const int trow = qb128 >> d.tshift;
       const int nent = __builtin_amdgcn_readfirstlane(a.kv_num[trow]);
       s.nblk = nent << d.tshift;
@@ -70,7 +67,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
         dma16(s.rs_v, ok ? s.vvo : OOB, so, dst + i * 4096 + 16384);
       }
     };
-    int item = item_at(0);
+    // (nothing is merged after E1 -- a dQ row is finished by one lane group: no E2)
+    int item = work_list.at(0);
     if (item < 0) return;
     Src cur = open_item(item);
 #pragma unroll 1
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
         __syncthreads();                           // barrier_j: block j + 1 landed; block j - 1 released
         if (j + 3 < nblk) issue_block(cur, j + 3);
       }
-      const int next = item_at(it + 1);
+      const int next = work_list.at(it + 1);
       Src nxt = cur;
       if (next >= 0) nxt = open_item(next);        // (nothing of this item is in flight any more)
       __syncthreads();                             // E1: the compute waves are done with the ring
@@ -103,29 +101,15 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
   // -------------------------------------------------------------------------------------------------- compute waves
   const int r = lane & 31, h = lane >> 5;
   // fragment addresses inside a slot: row reads of K (dual-use image) and V, micro-step kt = rows 32 kt + r
-  const int kr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);   // k-step ks: ^ (ks * 32)
-  const int vr0 = 16384 + r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, c0 = 2 * (grp & 1) + ((lane & 3) >> 1);
-  const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (lane & 1);
-  const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (lane & 1);
-  const int tsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto ktr = [&](const unsigned char* kt_, int tokbase, int dt) __attribute__((always_inline)) {
-    const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbA + o));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbB + o));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const int kr0 = row_frag_base(r, h, dual_image(r));
+  const int vr0 = 16384 + row_frag_base(r, h, row_image(r));
+  const DualLane ktl = dual_lane(lane);
 
-  int item = item_at(0);
+  int item = work_list.at(0);
 #pragma unroll 1
   for (int it = 0; item >= 0; ++it) {
-    const int pair = item >> 16, qb128 = item & 0xffff;
-    const int b = pair / a.heads, head = pair - b * a.heads;
+    const WorkItem wi = item_decode(item, a.heads);
+    const int b = wi.b, head = wi.head, qb128 = wi.blk;
     // per-item copy of the lane id for everything outside the block loop (see attention_ws.h: keeps hipcc from hoisting
     // lane-constant addresses out of the item loop and spilling them around the block loop)
     int le = lane;
@@ -156,17 +140,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
     bf16x8 kf[4], vf[4], ktf[2][2], pA[2], pB[2];
     f32x16 sA, dA, sB, dB;
     auto load_kv = [&](const unsigned char* S0, int kt) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        kf[ks] = *(const bf16x8*)(S0 + ((kr0 ^ (ks * 32)) + kt * 4096));
-        vf[ks] = *(const bf16x8*)(S0 + ((vr0 ^ (ks * 32)) + kt * 4096));
-      }
+      row_frag2(kf, vf, S0, kr0, S0, vr0, kt * 4096);
     };
     auto load_kt = [&](const unsigned char* S0, int kt) __attribute__((always_inline)) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = ktr(S0, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = dual_read(S0, ktl, kt * 32 + 16 * s2, dt);
     };
     // stage A of micro-step kt: both chains start from the row constants; in the list's last block the mask enters as
     // -1e30 (an accumulator register group rr = 4 g .. 4 g + 3 holds 4 consecutive, 4-aligned keys: one frame and one side
@@ -279,19 +259,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_ws_kernel(const AttnDev d)
     block(std::integral_constant<int, 2>{}, nblk - 1);
 
     __syncthreads();                               // E1: the ring is free for the next item's first blocks
-    {
-      bf16* og = (bf16*)a.dq + ((size_t)b * Lq + qrow) * C + head * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 ov;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) ov[k] = f2bf(dq[dt][4 * g + k] * 0.125f);
-          *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h_) = ov;
-        }
-    }
-    item = item_at(it + 1);
+    lane_row_store((bf16*)a.dq + ((size_t)b * Lq + qrow) * C + head * 64, dq, 0.125f, h_);
+    item = work_list.at(it + 1);
   }
 #endif
 }

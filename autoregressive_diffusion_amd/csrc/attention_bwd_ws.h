@@ -37,26 +37,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int C = a.C, Lq = a.Lq, Lk = a.Lk;
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-  const int nslots = a.sched_slots;
-  const int32_t* sched = a.sched + (size_t)blockIdx.x * nslots;
-  auto item_at = [&](int i) __attribute__((always_inline)) { return i < nslots ? __builtin_amdgcn_readfirstlane(sched[i]) : -1; };
+  const WorkList work_list{a.sched + (size_t)blockIdx.x * a.sched_slots, a.sched_slots};
   const int tmask = (1 << d.tshift) - 1;
 
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------------ loader waves
     const int lw = wave - 4;
     const int drow = 8 * lw + (lane >> 3), dpp = lane & 7;        // piece (lw + 4 i): row 32 i + drow, 16-byte part dpp
-    // ONE image for the row reads (ds_read_b128) and the transposing reads (ds_read_b64_tr_b16) of a tile: the 16-byte
-    // chunk c of row R sits at chunk c ^ f(R), f(R) = bit1(R) << 2 | bit3(R) << 1 | bit2(R) -- both kinds of read are
-    // conflict-free (bank model of MI355X_MICROARCH.md, LDS section; the transposing-read swizzle alone left the row reads
-    // 4-way conflicted, and with four compute waves on one LDS that was the kernel's bound)
-    const int tsw_ = (dpp ^ ((((drow >> 1) & 1) << 2) | (((drow >> 3) & 1) << 1) | ((drow >> 2) & 1))) * 16;
-    constexpr int OOB = (int)0x80000000;
+    // ONE image for the row reads (ds_read_b128) and the transposing reads (ds_read_b64_tr_b16) of a tile: the dual-use
+    // image of attention_parts.h, conflict-free for both
+    const int tsw_ = (dpp ^ dual_image(drow)) * 16;
     struct Src { i32x4 rs_q, rs_do, rs_l, rs_d; int qvo, nblk, qvl; };
     auto open_item = [&](int itm) __attribute__((always_inline)) {
       Src s;
-      const int pair = itm >> 16, kb64 = itm & 0xffff;                // (KEYS = 128: the index of the 128-key block)
-      const int b = pair / a.heads, head = pair - b * a.heads;
+      const WorkItem wi = item_decode(itm, a.heads);
+      const int b = wi.b, head = wi.head, kb64 = wi.blk;              // (KEYS = 128: the index of the 128-key block)
       const int trow = (KEYS == 128 ? kb64 : (kb64 >> 1)) >> d.tshift;
       const int nent = __builtin_amdgcn_readfirstlane(a.q_num[trow]);
       s.nblk = nent << d.tshift;
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
         else dma16(s.rs_d, vo, q0 * 4, sdst);
       }
     };
-    int item = item_at(0);
+    int item = work_list.at(0);
     if (item < 0) return;
     Src cur = open_item(item);
 #pragma unroll 1
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
         __syncthreads();                           // barrier_j: block j + 1 landed; block j - 1 released
         if (j + 3 < nblk) issue_block(cur, j + 3);
       }
-      const int next = item_at(it + 1);
+      const int next = work_list.at(it + 1);
       Src nxt = cur;
       if (next >= 0) nxt = open_item(next);        // (nothing of this item is in flight any more)
       __syncthreads();                             // E1: the compute waves are done with the ring
@@ -125,50 +120,26 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
 
   // -------------------------------------------------------------------------------------------------- compute waves
   const int kh = (KEYS == 128) ? wave : (wave & 1), qh = (KEYS == 128) ? 0 : (wave >> 1);
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
 
-  int item = item_at(0);
+  int item = work_list.at(0);
 #pragma unroll 1
   for (int it = 0; item >= 0; ++it) {
-    const int pair = item >> 16, kb64 = item & 0xffff;
-    const int b = pair / a.heads, head = pair - b * a.heads;
+    const WorkItem wi = item_decode(item, a.heads);
+    const int b = wi.b, head = wi.head, kb64 = wi.blk;
     // per-item copy of the lane id: keeps hipcc from hoisting (and spilling) lane-constant addresses out of the item loop
     int le = lane;
     asm volatile("" : "+v"(le));
     const int r = le & 31, h = le >> 5;
     const int kw0 = kb64 * KEYS + kh * 32;
     const int krow = kw0 + r;
-    const int rr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);
-    // transposing reads: lane (grp, q4, p) takes row tokbase + 4 hh + q4 (+ 8 for the second read), logical bytes
-    // 8 p + 32 (grp & 1) + 64 dt of it: chunk c = 2 (grp & 1) + (p >> 1) + 4 dt, stored at c ^ f(row)
-    const int grp = le >> 4, hh = grp >> 1, q4 = (le & 15) >> 2, c0 = 2 * (grp & 1) + ((le & 3) >> 1);
-    const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (le & 1);
-    const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (le & 1);
-    const int tsw = (q4 >> 1) & 1;
-    auto ttr = [&](const unsigned char* t_, int tokbase, int dt) __attribute__((always_inline)) {
-      const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t_ + tbA + o));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t_ + tbB + o));
-      s16x8 v;
-      v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-      v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-      return __builtin_bit_cast(bf16x8, v);
-    };
+    const int rr0 = row_frag_base(r, h, dual_image(r));
+    const DualLane ttl = dual_lane(le);            // transposing reads of the same tiles (from the per-item lane copy)
 
     const bf16* kg = (const bf16*)a.k + (size_t)b * Lk * C + head * 64;
     const bf16* vg = (const bf16*)a.v + (size_t)b * Lk * C + head * 64;
     bf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u};
-      if (krow < Lk) {
-        v = *(const u32x4*)(kg + (size_t)krow * C + ks * 16 + h * 8);
-        w = *(const u32x4*)(vg + (size_t)krow * C + ks * 16 + h * 8);
-      }
-      kf[ks] = __builtin_bit_cast(bf16x8, v);
-      vf[ks] = __builtin_bit_cast(bf16x8, w);
-    }
+    own_row(kf, kg + (size_t)krow * C + h * 8, krow < Lk);
+    own_row(vf, vg + (size_t)krow * C + h * 8, krow < Lk);
     f32x16 dk[2], dv[2];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
@@ -211,11 +182,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
         }
       }
       bf16x8 qa[4], da[4];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        qa[ks] = *(const bf16x8*)(Qt + ((rr0 ^ (ks * 32)) + trw * 128));
-        da[ks] = *(const bf16x8*)(dOt + ((rr0 ^ (ks * 32)) + trw * 128));
-      }
+      row_frag2(qa, da, Qt, rr0, dOt, rr0, trw * 128);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         s = mfma32(qa[ks], kf[ks], s);                   // S'[q][key]
@@ -231,7 +198,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) { dotf[s2][dt] = ttr(dOt, trw + 16 * s2, dt); qtf[s2][dt] = ttr(Qt, trw + 16 * s2, dt); }
+        for (int dt = 0; dt < 2; ++dt) { dotf[s2][dt] = dual_read(dOt, ttl, trw + 16 * s2, dt); qtf[s2][dt] = dual_read(Qt, ttl, trw + 16 * s2, dt); }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -307,20 +274,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_ws_kernel(const AttnDev d
           dv[0][i] += red[(32 + i) * 64]; dv[1][i] += red[(48 + i) * 64];
         }
       }
-      bf16* dkg = (bf16*)a.dk + ((size_t)b * Lk + krow) * C + head * 64;
-      bf16* dvg = (bf16*)a.dv + ((size_t)b * Lk + krow) * C + head * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o1, o2;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) { o1[k] = f2bf(dk[dt][4 * g + k] * (0.125f / SCALE_LOG2)); o2[k] = f2bf(dv[dt][4 * g + k]); }   // dK^T was summed against q' = c q and the unscaled P dP'; 1/8 = the score scale
-          *(bf16x4*)(dkg + dt * 32 + 8 * g + 4 * h) = o1;
-          *(bf16x4*)(dvg + dt * 32 + 8 * g + 4 * h) = o2;
-        }
+      // dK^T was summed against q' = c q and the unscaled P dP'; 1/8 = the score scale
+      lane_row_store((bf16*)a.dk + ((size_t)b * Lk + krow) * C + head * 64, dk, 0.125f / SCALE_LOG2, h);
+      lane_row_store((bf16*)a.dv + ((size_t)b * Lk + krow) * C + head * 64, dv, 1.f, h);
     }
-    item = item_at(it + 1);
+    item = work_list.at(it + 1);
   }
 #endif
 }

@@ -11,7 +11,7 @@
 // (two 32-row MFMA blocks that share every fragment read from LDS) and walks the P / 64 tiles of ITS frame.  No mask exists
 // (everything inside a frame is allowed), so the hot loop is the unmasked tile body of the grid kernels.
 //
-// Operand layouts, swizzles and the no-running-maximum softmax are those of attention.hip (helpers reused); q arrives carrying
+// Operand layouts, swizzles (attention_parts.h) and the no-running-maximum softmax are those of attention.hip; q arrives carrying
 // log2(e) / 8 (qkv_norm_kernel), lse is log2-domain.
 #pragma once
 
@@ -21,102 +21,65 @@ struct FrameAttnDev {
   int tiles;               // P / 64: key tiles per frame
 };
 
-// one burst: tile t (64 rows x 64 channels of head `head`) of tensors g0 / g1 -> LDS [t][g0 | g1], swizzled on the source side:
-// SW0 / SW1 pick the piece permutation of attention.hip's images -- 0: (row >> 1) & 7 (row reads), 1: 4 * bit1(row) (transposing
-// reads; row reads of it are 4-way conflicted), 2: bit1 << 2 | bit3 << 1 | bit2 (the dual-use image: conflict-free for both)
-template <int SW0, int SW1>
-__device__ __forceinline__ void frame_burst(const bf16* g0, const bf16* g1, long long tok0, long long ntok, int C /* row pitch */, int head,
-                                            unsigned lds0, int tid) {
-  constexpr int TB = 64 * 128, OOB = (int)0x80000000;
+// one burst of an NT-thread workgroup: tile t (64 rows x 64 channels of head `head`) of tensors g0 / g1 (row pitches C0 / C1) -> LDS
+// [t][g0 | g1], swizzled on the source side into the images IMG0 / IMG1 of attention_parts.h.  Every wave issues its copies tile by
+// tile: 8 DMA instructions per wave and burst at NT = 512 (the counted wait of the backward kernels relies on it), 16 at NT = 256.
+template <int IMG0, int IMG1, int NT>
+__device__ __forceinline__ void frame_burst(const bf16* g0, const bf16* g1, long long tok0, long long ntok, int C0, int C1, int head, unsigned lds0,
+                                            int tid) {
+  constexpr int TB = 64 * 128;
   const int wave = tid >> 6;
   const long long left = ntok - tok0;
   const int rows = left >= 256 ? 256 : (int)left;
-  const i32x4 r0 = make_rsrc(g0 + (size_t)tok0 * C, rows * C * 2);
-  const i32x4 r1 = make_rsrc(g1 + (size_t)tok0 * C, rows * C * 2);
+  const i32x4 r0 = make_rsrc(g0 + (size_t)tok0 * C0, rows * C0 * 2);
+  const i32x4 r1 = make_rsrc(g1 + (size_t)tok0 * C1, rows * C1 * 2);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = i * 256 + tid, row = e >> 3, pp = e & 7;
-      const int dual = (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1) | ((row >> 2) & 1);
-      const int sw0 = SW0 == 0 ? ((row >> 1) & 7) : SW0 == 1 ? 4 * ((row >> 1) & 1) : dual;
-      const int sw1 = SW1 == 0 ? ((row >> 1) & 7) : SW1 == 1 ? 4 * ((row >> 1) & 1) : dual;
+    for (int i = 0; i < 512 / NT; ++i) {
+      const int e = i * NT + tid, row = e >> 3, pp = e & 7;
       const bool ok = t * 64 + row < rows;
-      const unsigned dst = lds0 + t * 2 * TB + i * 4096 + wave * 1024;
-      dma16(r0, ok ? (row * C + head * 64 + (pp ^ sw0) * 8) * 2 : OOB, t * 64 * C * 2, dst);
-      dma16(r1, ok ? (row * C + head * 64 + (pp ^ sw1) * 8) * 2 : OOB, t * 64 * C * 2, dst + TB);
+      const unsigned dst = lds0 + t * 2 * TB + i * (NT * 16) + wave * 1024;
+      dma16(r0, ok ? image_src<IMG0>(row, pp, C0, head) : OOB, t * 64 * C0 * 2, dst);
+      dma16(r1, ok ? image_src<IMG1>(row, pp, C1, head) : OOB, t * 64 * C1 * 2, dst + TB);
     }
   }
 }
 
-// J = 32-row query blocks per wave: 2 = a workgroup per 256 tokens (training); 1 = a workgroup per 128 tokens of a 256-token frame
-// (round 6: one frame per sequence in the cached sampler is heads workgroups -- two query halves per frame put the launch on twice the
-// CUs with half the MFMA / softmax chain each; K | V of the frame are staged by both)
+// ---- the tile bodies, once each; the plain kernels and the raw-qkv kernels differ only in what surrounds them -------------------
+// lane roles of the forward (K row image, V transposing image) and of the backward passes (K / Q / dO dual-use image, V row image):
+// computed by the kernel, where its own address arithmetic sits, and handed to the bodies
+struct FrameFwdLane { int kb0; TrLane vt; };
+__device__ __forceinline__ FrameFwdLane frame_fwd_lane(int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  return FrameFwdLane{row_frag_base(r, h, row_image(r)), tr_lane(lane)};
+}
+struct FrameBwdLane { int kr0, vr0, h; DualLane kt; };
+__device__ __forceinline__ FrameBwdLane frame_bwd_lane(int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  return FrameBwdLane{row_frag_base(r, h, dual_image(r)), row_frag_base(r, h, row_image(r)), h, dual_lane(lane)};
+}
+// forward: tiles [t0, t0 + tiles) of the staged [tile][K (row image) | V (transposing image)] against J 32-row query blocks of this
+// wave (lane = query row); o / l2 accumulate the un-normalised O^T and the two half row sums
 template <int J>
-__global__ __launch_bounds__(256, 2) void frame_attn_fwd_kernel(const FrameAttnDev d) {
-#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void frame_fwd_tiles(f32x16 (&o)[J][2], float (&l2)[J][2], const bf16x8 (&qf)[J][4], const unsigned char* smem, int t0,
+                                                int tiles, const FrameFwdLane& ln) {
   constexpr int TB = 64 * 128;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 2 * TB];     // [tile][K | V]
-  const OnirisAttnArgs& a = d.a;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
-  const int head = blockIdx.y, C = a.C, P = a.Lq;
-  const long long tok0 = (long long)(blockIdx.x / (2 / J)) * 256;            // the 256-token block whose K | V are staged
-  const int qoff = (J == 2) ? 0 : (int)(blockIdx.x & 1) * 128;               // ... and this workgroup's query rows inside it
-  const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-  // Q fragments first (ordinary loads), consumed before any LDS-DMA is in flight
-  const bf16* qg = (const bf16*)a.q + head * 64;
-  bf16x8 qf[J][4];
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const long long qrow = tok0 + qoff + wave * (32 * J) + j * 32 + r;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 v = u32x4{0u, 0u, 0u, 0u};
-      if (qrow < d.ntok) v = *(const u32x4*)(qg + (size_t)qrow * C + ks * 16 + h * 8);
-      qf[j][ks] = __builtin_bit_cast(bf16x8, v);
-    }
-  }
-  frame_burst<0, 1>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, head, lds0, tid);
-  f32x16 o[J][2];
-  float l2[J][2];
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { o[j][0][i] = 0.f; o[j][1][i] = 0.f; }
-    l2[j][0] = 0.f; l2[j][1] = 0.f;
-  }
-  const int kb0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const int vb0 = (4 * hh + q4) * 128 + pcol * 2, vsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto vtr = [&](const unsigned char* vt, int tokbase, int dt) __attribute__((always_inline)) {
-    const unsigned char* p0 = vt + vb0 + tokbase * 128 + ((dt ^ vsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * 128));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
-  dma_wait();
-  __syncthreads();
-  const int t0 = ((qoff + wave * (32 * J)) / P) * d.tiles;  // first key tile of this wave's frame inside the super-block
+  const int kb0 = ln.kb0;
+  const TrLane vt = ln.vt;
 #pragma unroll 1
-  for (int t = t0; t < t0 + d.tiles; ++t) {
+  for (int t = t0; t < t0 + tiles; ++t) {
     const unsigned char* Kt = smem + t * 2 * TB;
     const unsigned char* Vt = Kt + TB;
     bf16x8 kf[2][4], vf[2][2][2];
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) kf[kt][ks] = *(const bf16x8*)(Kt + ((kb0 ^ (ks * 32)) + kt * 4096));
+    for (int kt = 0; kt < 2; ++kt) row_frag(kf[kt], Kt, kb0, kt * 4096);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) vf[kt][s2][dt] = vtr(Vt, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) vf[kt][s2][dt] = tr_read(Vt, vt, kt * 32 + 16 * s2, dt);
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       f32x16 s[2];
@@ -145,110 +108,47 @@ __global__ __launch_bounds__(256, 2) void frame_attn_fwd_kernel(const FrameAttnD
         }
     }
   }
+}
+// forward epilogue: rows row0 + 32 j (this lane's) of out [tok][C] and of lse [b][head][P] (lse may be null)
+template <int J>
+__device__ __forceinline__ void frame_fwd_store(const f32x16 (&o)[J][2], const float (&l2)[J][2], long long row0, long long ntok, bf16* out, float* lse,
+                                                int C, int P, int heads, int head, int h) {
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    const long long qrow = tok0 + qoff + wave * (32 * J) + j * 32 + r;
+    const long long qrow = row0 + j * 32;
     float l = l2[j][0] + l2[j][1];
     l += __shfl_xor(l, 32);
-    if (qrow >= d.ntok) continue;
+    if (qrow >= ntok) continue;
     const float inv = (l > 0.f) ? 1.f / l : 0.f;
-    bf16* og = (bf16*)a.out + (size_t)qrow * C + head * 64;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 ov;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ov[k] = f2bf(o[j][dt][4 * g + k] * inv);
-        *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-      }
-    if (a.lse && h == 0) {
+    lane_row_store(out + (size_t)qrow * C + head * 64, o[j], inv, h);
+    if (lse && h == 0) {
       const long long b = qrow / P;
-      a.lse[(size_t)(b * a.heads + head) * P + (qrow - b * P)] = SOFTMAX_OFF + log2f(fmaxf(l, 1e-30f));
+      lse[(size_t)(b * heads + head) * P + (qrow - b * P)] = SOFTMAX_OFF + log2f(fmaxf(l, 1e-30f));
     }
   }
-#endif
 }
-
-// dQ: the forward's structure (lane = query row); K in the dual-use image (row reads for S^T, transposing reads for dQ^T), V row-read
-__global__ __launch_bounds__(256, 2) void frame_attn_dq_kernel(const FrameAttnDev d) {
-#if defined(__HIP_DEVICE_COMPILE__)
+// pass A (dQ, lane = query row): tiles [t0, t0 + tiles) of the staged [tile][K (dual-use image: row reads for S^T, transposing reads
+// for dQ^T) | V (row image)] against J 32-row query blocks; dq accumulates dQ^T without the 1/8 of the score scale
+template <int J>
+__device__ __forceinline__ void frame_pass_a(f32x16 (&dq)[J][2], const bf16x8 (&qf)[J][4], const bf16x8 (&dof)[J][4], const float (&lse)[J],
+                                             const float (&delta)[J], const unsigned char* smem, int t0, int tiles, const FrameBwdLane& ln) {
   constexpr int TB = 64 * 128;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 2 * TB];     // [tile][K | V]
-  const OnirisAttnArgs& a = d.a;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
-  const int head = blockIdx.y, C = a.C, P = a.Lq;
-  const long long tok0 = (long long)blockIdx.x * 256;
-  const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-  const bf16* qg = (const bf16*)a.q + head * 64;
-  const bf16* dog = (const bf16*)a.dout + head * 64;
-  bf16x8 qf[2][4], dof[2][4];
-  float lse[2] = {0.f, 0.f}, delta[2] = {0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const long long qrow = tok0 + wave * 64 + j * 32 + r;
-    const bool in = qrow < d.ntok;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u};
-      if (in) {
-        v = *(const u32x4*)(qg + (size_t)qrow * C + ks * 16 + h * 8);
-        w = *(const u32x4*)(dog + (size_t)qrow * C + ks * 16 + h * 8);
-      }
-      qf[j][ks] = __builtin_bit_cast(bf16x8, v);
-      dof[j][ks] = __builtin_bit_cast(bf16x8, w);
-    }
-    if (in) {
-      const long long b = qrow / P;
-      const size_t li = (size_t)(b * a.heads + head) * P + (qrow - b * P);
-      lse[j] = a.lse[li];
-      delta[j] = a.delta[li];
-    }
-  }
-  frame_burst<2, 0>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, head, lds0, tid);
-  f32x16 dq[2][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dq[j][0][i] = 0.f; dq[j][1][i] = 0.f; }
-  const int kr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);
-  const int vr0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, c0 = 2 * (grp & 1) + ((lane & 3) >> 1);
-  const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (lane & 1);
-  const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (lane & 1);
-  const int tsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto ktr = [&](const unsigned char* kt_, int tokbase, int dt) __attribute__((always_inline)) {
-    const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbA + o));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbB + o));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
-  dma_wait();
-  __syncthreads();
-  const int t0 = ((wave * 64) / P) * d.tiles;
+  const int kr0 = ln.kr0, vr0 = ln.vr0;
+  const DualLane ktl = ln.kt;
 #pragma unroll 1
-  for (int t = t0; t < t0 + d.tiles; ++t) {
+  for (int t = t0; t < t0 + tiles; ++t) {
     const unsigned char* Kt = smem + t * 2 * TB;
     const unsigned char* Vt = Kt + TB;
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       bf16x8 kf[4], vf[4], ktf[2][2];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        kf[ks] = *(const bf16x8*)(Kt + ((kr0 ^ (ks * 32)) + kt * 4096));
-        vf[ks] = *(const bf16x8*)(Vt + ((vr0 ^ (ks * 32)) + kt * 4096));
-      }
+      row_frag2(kf, vf, Kt, kr0, Vt, vr0, kt * 4096);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = ktr(Kt, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = dual_read(Kt, ktl, kt * 32 + 16 * s2, dt);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int j = 0; j < J; ++j) {
         f32x16 s, dp;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
@@ -268,21 +168,174 @@ __global__ __launch_bounds__(256, 2) void frame_attn_dq_kernel(const FrameAttnDe
       }
     }
   }
+}
+// pass B (dK / dV, lane = key row) of an 8-wave workgroup: K / V row fragments of this wave's 32 keys from region A (tile wave / 2,
+// rows (wave & 1) * 32 + r), Q | dO (both in the dual-use image) of tiles [t0, t0 + tiles) from region B, the rows' lse / delta
+// from LDS; dk accumulates against q' = c q, with the 1/8 of the score scale applied
+// (dK / dV come back BY VALUE: handed back through reference parameters, hipcc fused 18 more products of the raw-qkv kernel's adjoint
+// stores into their sums than in the kernel that carried this body itself -- other bits in dqkv; scratch/attn_shared_parts_asm.py
+// compares the floating-point opcode counts of every kernel for this reason)
+struct FrameDkv { f32x16 dk[2], dv[2]; };
+__device__ __forceinline__ FrameDkv frame_pass_b(const unsigned char* regA, const unsigned char* regB, const float* lse_lds,
+                                             const float* del_lds, int wave, int t0, int tiles, const FrameBwdLane& ln) {
+  constexpr int TB = 64 * 128;
+  const int kr0 = ln.kr0, vr0 = ln.vr0, h = ln.h;
+  const DualLane ktl = ln.kt;
+  const unsigned char* Kown = regA + (wave >> 1) * 2 * TB + (wave & 1) * 4096;
+  const unsigned char* Vown = Kown + TB;
+  bf16x8 kf[4], vf[4];
+  row_frag2(kf, vf, Kown, kr0, Vown, vr0, 0);
+  f32x16 dk[2], dv[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
+#pragma unroll 1
+  for (int t = t0; t < t0 + tiles; ++t) {
+    const unsigned char* Qt = regB + t * 2 * TB;
+    const unsigned char* dOt = Qt + TB;
+#pragma unroll 1
+    for (int qt = 0; qt < 2; ++qt) {
+      bf16x8 qa[4], da[4], dotf[2][2], qtf[2][2];
+      row_frag2(qa, da, Qt, kr0, dOt, kr0, qt * 4096);
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          dotf[s2][dt] = dual_read(dOt, ktl, qt * 32 + 16 * s2, dt);
+          qtf[s2][dt] = dual_read(Qt, ktl, qt * 32 + 16 * s2, dt);
+        }
+      f32x16 s, dp, pv;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s = mfma32(qa[ks], kf[ks], s);                   // S[q][key]
+        dp = mfma32(da[ks], vf[ks], dp);                 // dP[q][key]
+      }
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int qb4 = t * 64 + qt * 32 + 8 * g4 + 4 * h;
+        const float4 ls = *(const float4*)(lse_lds + qb4), de = *(const float4*)(del_lds + qb4);
+        const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dev[4] = {de.x, de.y, de.z, de.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int rr = 4 * g4 + k;
+          const float p = __builtin_amdgcn_exp2f(s[rr] - lsv[k]);
+          pv[rr] = p;
+          s[rr] = p * (dp[rr] - dev[k]) * 0.125f;
+        }
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const bf16x8 pb = pack8(pv, s2);
+        const bf16x8 db = pack8(s, s2);
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          dv[dt] = mfma32(dotf[s2][dt], pb, dv[dt]);
+          dk[dt] = mfma32(qtf[s2][dt], db, dk[dt]);
+        }
+      }
+    }
+  }
+  return FrameDkv{{dk[0], dk[1]}, {dv[0], dv[1]}};
+}
+// the backward kernels' own rows (lane = row, this lane's half of the 64 channels): Q and dO fragments, delta = dO . O; the three loads
+// of a k-step share one branch and the products are summed inside the k-step loop, as delta has always been summed
+__device__ __forceinline__ void frame_bwd_own_rows(bf16x8 (&qf)[4], bf16x8 (&dof)[4], float& delta, const bf16* qp, const bf16* dop, const bf16* op,
+                                                   bool in) {
+  delta = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u}, o = u32x4{0u, 0u, 0u, 0u};
+    if (in) {
+      v = *(const u32x4*)(qp + ks * 16);
+      w = *(const u32x4*)(dop + ks * 16);
+      o = *(const u32x4*)(op + ks * 16);
+    }
+    qf[ks] = __builtin_bit_cast(bf16x8, v);
+    dof[ks] = __builtin_bit_cast(bf16x8, w);
+    const bf16x8 ofr = __builtin_bit_cast(bf16x8, o);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) delta += bf2f(dof[ks][e]) * bf2f(ofr[e]);
+  }
+  delta += __shfl_xor(delta, 32);
+}
+
+// J = 32-row query blocks per wave: 2 = a workgroup per 256 tokens (training); 1 = a workgroup per 128 tokens of a 256-token frame
+// (round 6: one frame per sequence in the cached sampler is heads workgroups -- two query halves per frame put the launch on twice the
+// CUs with half the MFMA / softmax chain each; K | V of the frame are staged by both)
+template <int J>
+__global__ __launch_bounds__(256, 2) void frame_attn_fwd_kernel(const FrameAttnDev d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int TB = 64 * 128;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 2 * TB];     // [tile][K | V]
+  const OnirisAttnArgs& a = d.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
+  const int head = blockIdx.y, C = a.C, P = a.Lq;
+  const long long tok0 = (long long)(blockIdx.x / (2 / J)) * 256;            // the 256-token block whose K | V are staged
+  const int qoff = (J == 2) ? 0 : (int)(blockIdx.x & 1) * 128;               // ... and this workgroup's query rows inside it
+  const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
+  // Q fragments first (ordinary loads), consumed before any LDS-DMA is in flight
+  const long long row0 = tok0 + qoff + wave * (32 * J) + r;                  // this lane's query rows: row0 + 32 j
+  bf16x8 qf[J][4];
+#pragma unroll
+  for (int j = 0; j < J; ++j) own_row(qf[j], (const bf16*)a.q + (size_t)(row0 + j * 32) * C + head * 64 + h * 8, row0 + j * 32 < d.ntok);
+  frame_burst<IMG_ROW, IMG_TR, 256>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, C, head, lds0, tid);
+  f32x16 o[J][2];
+  float l2[J][2];
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { o[j][0][i] = 0.f; o[j][1][i] = 0.f; }
+    l2[j][0] = 0.f; l2[j][1] = 0.f;
+  }
+  const FrameFwdLane ln = frame_fwd_lane(lane);
+  dma_wait();
+  __syncthreads();
+  const int t0 = ((qoff + wave * (32 * J)) / P) * d.tiles;  // first key tile of this wave's frame inside the super-block
+  frame_fwd_tiles<J>(o, l2, qf, smem, t0, d.tiles, ln);
+  frame_fwd_store<J>(o, l2, row0, d.ntok, (bf16*)a.out, a.lse, C, P, a.heads, head, h);
+#endif
+}
+
+// dQ: the forward's structure (lane = query row); K in the dual-use image (row reads for S^T, transposing reads for dQ^T), V row-read
+__global__ __launch_bounds__(256, 2) void frame_attn_dq_kernel(const FrameAttnDev d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int TB = 64 * 128;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 2 * TB];     // [tile][K | V]
+  const OnirisAttnArgs& a = d.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
+  const int head = blockIdx.y, C = a.C, P = a.Lq;
+  const long long tok0 = (long long)blockIdx.x * 256;
+  const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
+  bf16x8 qf[2][4], dof[2][4];
+  float lse[2] = {0.f, 0.f}, delta[2] = {0.f, 0.f};
+  const long long row0 = tok0 + wave * 64 + r;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const long long qrow = tok0 + wave * 64 + j * 32 + r;
-    if (qrow >= d.ntok) continue;
-    bf16* og = (bf16*)a.dq + (size_t)qrow * C + head * 64;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 ov;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ov[k] = f2bf(dq[j][dt][4 * g + k] * 0.125f);
-        *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-      }
+    const long long qrow = row0 + j * 32;
+    const bool in = qrow < d.ntok;
+    own_row(qf[j], (const bf16*)a.q + (size_t)qrow * C + head * 64 + h * 8, in);
+    own_row(dof[j], (const bf16*)a.dout + (size_t)qrow * C + head * 64 + h * 8, in);
+    if (in) {
+      const long long b = qrow / P;
+      const size_t li = (size_t)(b * a.heads + head) * P + (qrow - b * P);
+      lse[j] = a.lse[li];
+      delta[j] = a.delta[li];
+    }
   }
+  frame_burst<IMG_DUAL, IMG_ROW, 256>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, C, head, lds0, tid);
+  f32x16 dq[2][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { dq[j][0][i] = 0.f; dq[j][1][i] = 0.f; }
+  const FrameBwdLane ln = frame_bwd_lane(lane);
+  dma_wait();
+  __syncthreads();
+  frame_pass_a<2>(dq, qf, dof, lse, delta, smem, ((wave * 64) / P) * d.tiles, d.tiles, ln);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    if (row0 + j * 32 < d.ntok) lane_row_store((bf16*)a.dq + (size_t)(row0 + j * 32) * C + head * 64, dq[j], 0.125f, h);
 #endif
 }
 
@@ -292,31 +345,8 @@ __global__ __launch_bounds__(256, 2) void frame_attn_dq_kernel(const FrameAttnDe
 // dO) moved 13 tensor passes; here q, k, v, O, dO are read ONCE and dq, dk, dv written: 8 passes.
 // 8 waves = 8 x 32 rows.  Pass A (lane = query): this wave's Q / dO / O rows from global (delta = dO . O in registers, lse | delta
 // parked in LDS for pass B), K (dual-use image) | V (row image) of the super-block from LDS region A -> dQ.  Pass B (lane = key):
-// K / V row fragments of this wave's 32 keys from region A, Q | dO (transposing image) from region B -> dK, dV.  Both regions are
+// K / V row fragments of this wave's 32 keys from region A, Q | dO (dual-use images) from region B -> dK, dV.  Both regions are
 // requested up front; pass A starts as soon as region A has landed (counted vmcnt: region B's 8 copies stay in flight under it).
-template <int SW0, int SW1>
-__device__ __forceinline__ void frame_burst512(const bf16* g0, const bf16* g1, long long tok0, long long ntok, int C /* pitch of g0 */,
-                                               int C1 /* pitch of g1 */, int head, unsigned lds0, int tid) {
-  constexpr int TB = 64 * 128, OOB = (int)0x80000000;
-  const int wave = tid >> 6;
-  const long long left = ntok - tok0;
-  const int rows = left >= 256 ? 256 : (int)left;
-  const i32x4 r0 = make_rsrc(g0 + (size_t)tok0 * C, rows * C * 2);
-  const i32x4 r1 = make_rsrc(g1 + (size_t)tok0 * C1, rows * C1 * 2);
-  const int row = tid >> 3, pp = tid & 7;
-  const int dual = (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1) | ((row >> 2) & 1);
-  const int sw0 = SW0 == 0 ? ((row >> 1) & 7) : SW0 == 1 ? 4 * ((row >> 1) & 1) : dual;
-  const int sw1 = SW1 == 0 ? ((row >> 1) & 7) : SW1 == 1 ? 4 * ((row >> 1) & 1) : dual;
-  const int v0 = (row * C + head * 64 + (pp ^ sw0) * 8) * 2, v1 = (row * C1 + head * 64 + (pp ^ sw1) * 8) * 2;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const bool ok = t * 64 + row < rows;
-    const unsigned dst = lds0 + t * 2 * TB + wave * 1024;
-    dma16(r0, ok ? v0 : OOB, t * 64 * C * 2, dst);
-    dma16(r1, ok ? v1 : OOB, t * 64 * C1 * 2, dst + TB);
-  }
-}
-
 __global__ __launch_bounds__(512, 2) void frame_attn_bwd_kernel(const FrameAttnDev d) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TB = 64 * 128, REG = 4 * 2 * TB;
@@ -331,193 +361,41 @@ __global__ __launch_bounds__(512, 2) void frame_attn_bwd_kernel(const FrameAttnD
   const long long row = tok0 + wave * 32 + r;                // this lane's query row (pass A) = key row (pass B)
   const bool in = row < d.ntok;
   // ---- this wave's Q / dO / O rows, lse; delta
-  bf16x8 qf[4], dof[4];
-  float lse = 0.f, delta = 0.f;
+  bf16x8 qf[1][4], dof[1][4];
+  float lse[1] = {0.f}, delta[1];
   {
     const size_t base = (size_t)row * C + head * 64 + h * 8;
-    const bf16* qg = (const bf16*)a.q + base;
-    const bf16* dog = (const bf16*)a.dout + base;
-    const bf16* og = (const bf16*)a.out + base;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u}, o = u32x4{0u, 0u, 0u, 0u};
-      if (in) {
-        v = *(const u32x4*)(qg + ks * 16);
-        w = *(const u32x4*)(dog + ks * 16);
-        o = *(const u32x4*)(og + ks * 16);
-      }
-      qf[ks] = __builtin_bit_cast(bf16x8, v);
-      dof[ks] = __builtin_bit_cast(bf16x8, w);
-      const bf16x8 ofr = __builtin_bit_cast(bf16x8, o);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) delta += bf2f(dof[ks][e]) * bf2f(ofr[e]);
-    }
-    delta += __shfl_xor(delta, 32);
+    frame_bwd_own_rows(qf[0], dof[0], delta[0], (const bf16*)a.q + base, (const bf16*)a.dout + base, (const bf16*)a.out + base, in);
     if (in) {
       const long long b = row / P;
-      lse = a.lse[(size_t)(b * a.heads + head) * P + (row - b * P)];
+      lse[0] = a.lse[(size_t)(b * a.heads + head) * P + (row - b * P)];
     }
-    if (h == 0) { lse_lds[wave * 32 + r] = lse; del_lds[wave * 32 + r] = delta; }
+    if (h == 0) { lse_lds[wave * 32 + r] = lse[0]; del_lds[wave * 32 + r] = delta[0]; }
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[ks]));      // every ordinary load consumed before an LDS-DMA is in flight
+    for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[0][ks]));      // every ordinary load consumed before an LDS-DMA is in flight
   }
-  frame_burst512<2, 0>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, C, head, lds0, tid);
-  frame_burst512<2, 2>((const bf16*)a.q, (const bf16*)a.dout, tok0, d.ntok, C, C, head, lds0 + REG, tid);
+  frame_burst<IMG_DUAL, IMG_ROW, 512>((const bf16*)a.k, (const bf16*)a.v, tok0, d.ntok, C, C, head, lds0, tid);
+  frame_burst<IMG_DUAL, IMG_DUAL, 512>((const bf16*)a.q, (const bf16*)a.dout, tok0, d.ntok, C, C, head, lds0 + REG, tid);
   const int t0 = ((wave * 32) / P) * d.tiles;                // first tile of this wave's frame inside the super-block
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2;
-  const int kr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);     // K, dual-use image: row reads
-  const int vr0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);                                                         // V, row image
-  // transposing read of a dual-use image (K in pass A; Q and dO in pass B)
-  const int c0 = 2 * (grp & 1) + ((lane & 3) >> 1);
-  const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (lane & 1);
-  const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (lane & 1);
-  const int tsw = (q4 >> 1) & 1;
-  auto ktr = [&](const unsigned char* kt_, int tokbase, int dt) __attribute__((always_inline)) {
-    const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbA + o));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbB + o));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const FrameBwdLane ln = frame_bwd_lane(lane);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");           // region A (the first 8 copies of this wave) has landed
   __syncthreads();
   // ---- pass A: dQ
   {
-    f32x16 dq[2];
+    f32x16 dq[1][2];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
-#pragma unroll 1
-    for (int t = t0; t < t0 + d.tiles; ++t) {
-      const unsigned char* Kt = smem + t * 2 * TB;
-      const unsigned char* Vt = Kt + TB;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        bf16x8 kf[4], vf[4], ktf[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          kf[ks] = *(const bf16x8*)(Kt + ((kr0 ^ (ks * 32)) + kt * 4096));
-          vf[ks] = *(const bf16x8*)(Vt + ((vr0 ^ (ks * 32)) + kt * 4096));
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = ktr(Kt, kt * 32 + 16 * s2, dt);
-        f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          s = mfma32(kf[ks], qf[ks], s);
-          dp = mfma32(vf[ks], dof[ks], dp);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) s[rr] = __builtin_amdgcn_exp2f(s[rr] - lse) * (dp[rr] - delta);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 db = pack8(s, s2);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma32(ktf[s2][dt], db, dq[dt]);
-        }
-      }
-    }
-    if (in) {
-      bf16* og = (bf16*)a.dq + (size_t)row * C + head * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 ov;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) ov[k] = f2bf(dq[dt][4 * g + k] * 0.125f);
-          *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-        }
-    }
+    for (int i = 0; i < 16; ++i) { dq[0][0][i] = 0.f; dq[0][1][i] = 0.f; }
+    frame_pass_a<1>(dq, qf, dof, lse, delta, smem, t0, d.tiles, ln);
+    if (in) lane_row_store((bf16*)a.dq + (size_t)row * C + head * 64, dq[0], 0.125f, h);
   }
   dma_wait();                                                // region B has landed (and this wave's dQ stores are out)
   __syncthreads();
   // ---- pass B: dK, dV
   {
-    // this wave's key rows live in tile (wave / 2), rows (wave & 1) * 32 + r of region A
-    const unsigned char* Kown = smem + (wave >> 1) * 2 * TB + (wave & 1) * 4096;
-    const unsigned char* Vown = Kown + TB;
-    bf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      kf[ks] = *(const bf16x8*)(Kown + (kr0 ^ (ks * 32)));
-      vf[ks] = *(const bf16x8*)(Vown + (vr0 ^ (ks * 32)));
-    }
-    f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
-#pragma unroll 1
-    for (int t = t0; t < t0 + d.tiles; ++t) {
-      const unsigned char* Qt = smem + REG + t * 2 * TB;
-      const unsigned char* dOt = Qt + TB;
-#pragma unroll 1
-      for (int qt = 0; qt < 2; ++qt) {
-        bf16x8 qa[4], da[4], dotf[2][2], qtf[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          qa[ks] = *(const bf16x8*)(Qt + ((kr0 ^ (ks * 32)) + qt * 4096));
-          da[ks] = *(const bf16x8*)(dOt + ((kr0 ^ (ks * 32)) + qt * 4096));
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            dotf[s2][dt] = ktr(dOt, qt * 32 + 16 * s2, dt);
-            qtf[s2][dt] = ktr(Qt, qt * 32 + 16 * s2, dt);
-          }
-        f32x16 s, dp, pv;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          s = mfma32(qa[ks], kf[ks], s);                   // S[q][key]
-          dp = mfma32(da[ks], vf[ks], dp);                 // dP[q][key]
-        }
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int qb4 = t * 64 + qt * 32 + 8 * g4 + 4 * h;
-          const float4 ls = *(const float4*)(lse_lds + qb4), de = *(const float4*)(del_lds + qb4);
-          const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dev[4] = {de.x, de.y, de.z, de.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int rr = 4 * g4 + k;
-            const float p = __builtin_amdgcn_exp2f(s[rr] - lsv[k]);
-            pv[rr] = p;
-            s[rr] = p * (dp[rr] - dev[k]) * 0.125f;
-          }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 pb = pack8(pv, s2);
-          const bf16x8 db = pack8(s, s2);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            dv[dt] = mfma32(dotf[s2][dt], pb, dv[dt]);
-            dk[dt] = mfma32(qtf[s2][dt], db, dk[dt]);
-          }
-        }
-      }
-    }
+    const FrameDkv g = frame_pass_b(smem, smem + REG, lse_lds, del_lds, wave, t0, d.tiles, ln);
     if (in) {
-      bf16* dkg = (bf16*)a.dk + (size_t)row * C + head * 64;
-      bf16* dvg = (bf16*)a.dv + (size_t)row * C + head * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o1, o2;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) { o1[k] = f2bf(dk[dt][4 * g + k] * (1.f / SCALE_LOG2)); o2[k] = f2bf(dv[dt][4 * g + k]); }
-          *(bf16x4*)(dkg + dt * 32 + 8 * g + 4 * h) = o1;
-          *(bf16x4*)(dvg + dt * 32 + 8 * g + 4 * h) = o2;
-        }
+      lane_row_store((bf16*)a.dk + (size_t)row * C + head * 64, g.dk, 1.f / SCALE_LOG2, h);
+      lane_row_store((bf16*)a.dv + (size_t)row * C + head * 64, g.dv, 1.f, h);
     }
   }
 #endif
@@ -605,17 +483,17 @@ __global__ __launch_bounds__(256, 2) void frame_attn_qkv_fwd_kernel(const FrameQ
   FSTAMP(0);
   // K | V of the super-block are requested first; this wave's Q rows are loaded and normalised under the copy (the compiler's
   // wait for these ordinary loads also covers the older LDS-DMA copies: both are needed before the barrier anyway)
-  frame_burst<0, 1>(d.qkv + C, d.qkv + 2 * C, tok0, d.ntok, C3, head, lds0, tid);
+  frame_burst<IMG_ROW, IMG_TR, 256>(d.qkv + C, d.qkv + 2 * C, tok0, d.ntok, C3, C3, head, lds0, tid);
   FSTAMP(1);
-  const bf16* qg = d.qkv + head * 64;
+  const long long row0 = tok0 + wave * 64 + r;                         // this lane's query rows: row0 + 32 j
   bf16x8 qf[2][4];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const long long qrow = tok0 + wave * 64 + j * 32 + r;
+  for (int j = 0; j < 2; ++j) {            // (not own_row: with it hipcc fuses 54 more products of frame_row_norm's sums of squares below)
+    const long long qrow = row0 + j * 32;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       u32x4 v = u32x4{0u, 0u, 0u, 0u};
-      if (qrow < d.ntok) v = *(const u32x4*)(qg + (size_t)qrow * C3 + ks * 16 + h * 8);
+      if (qrow < d.ntok) v = *(const u32x4*)(d.qkv + head * 64 + (size_t)qrow * C3 + ks * 16 + h * 8);
       qf[j][ks] = __builtin_bit_cast(bf16x8, v);
     }
   }
@@ -628,20 +506,7 @@ __global__ __launch_bounds__(256, 2) void frame_attn_qkv_fwd_kernel(const FrameQ
 #pragma unroll
     for (int i = 0; i < 16; ++i) { o[j][0][i] = 0.f; o[j][1][i] = 0.f; }
   float l2[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-  const int kb0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const int vb0 = (4 * hh + q4) * 128 + pcol * 2, vsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto vtr = [&](const unsigned char* vt, int tokbase, int dt) __attribute__((always_inline)) {
-    const unsigned char* p0 = vt + vb0 + tokbase * 128 + ((dt ^ vsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * 128));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const FrameFwdLane ln = frame_fwd_lane(lane);
   dma_wait();
   __syncthreads();
   FSTAMP(3);
@@ -649,73 +514,9 @@ __global__ __launch_bounds__(256, 2) void frame_attn_qkv_fwd_kernel(const FrameQ
   frame_lds_norm<256>(smem + TB, 1.f, tid);            // V
   __syncthreads();
   FSTAMP(4);
-  const int t0 = ((wave * 64) / P) * d.tiles;
-#pragma unroll 1
-  for (int t = t0; t < t0 + d.tiles; ++t) {
-    const unsigned char* Kt = smem + t * 2 * TB;
-    const unsigned char* Vt = Kt + TB;
-    bf16x8 kf[2][4], vf[2][2][2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) kf[kt][ks] = *(const bf16x8*)(Kt + ((kb0 ^ (ks * 32)) + kt * 4096));
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) vf[kt][s2][dt] = vtr(Vt, kt * 32 + 16 * s2, dt);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      f32x16 s[2];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[kt][i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) s[kt] = mfma32(kf[kt][ks], qf[j][ks], s[kt]);
-      }
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          const float p = __builtin_amdgcn_exp2f(s[kt][rr] - SOFTMAX_OFF);
-          s[kt][rr] = p;
-          l2[j][rr & 1] += p;
-        }
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 pb = pack8(s[kt], s2);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) o[j][dt] = mfma32(vf[kt][s2][dt], pb, o[j][dt]);
-        }
-    }
-  }
+  frame_fwd_tiles<2>(o, l2, qf, smem, ((wave * 64) / P) * d.tiles, d.tiles, ln);
   FSTAMP(5);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const long long qrow = tok0 + wave * 64 + j * 32 + r;
-    float l = l2[j][0] + l2[j][1];
-    l += __shfl_xor(l, 32);
-    if (qrow >= d.ntok) continue;
-    const float inv = (l > 0.f) ? 1.f / l : 0.f;
-    bf16* og = d.out + (size_t)qrow * C + head * 64;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 ov;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ov[k] = f2bf(o[j][dt][4 * g + k] * inv);
-        *(bf16x4*)(og + dt * 32 + 8 * g + 4 * h) = ov;
-      }
-    if (h == 0) {
-      const long long b = qrow / P;
-      d.lse[(size_t)(b * d.heads + head) * P + (qrow - b * P)] = SOFTMAX_OFF + log2f(fmaxf(l, 1e-30f));
-    }
-  }
+  frame_fwd_store<2>(o, l2, row0, d.ntok, d.out, d.lse, C, P, d.heads, head, h);
   FSTAMP(6);
 #endif
 }
@@ -728,7 +529,7 @@ __device__ __forceinline__ void frame_norm_adjoint_store(const f32x16 (&g)[2], f
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      const bf16x4 v = *(const bf16x4*)(src + dt * 32 + 8 * g4 + 4 * h);
+      const bf16x4 v = *(const bf16x4*)(src + lane_row_ch(dt, g4, h));
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float f = bf2f(v[k]);
@@ -748,7 +549,7 @@ __device__ __forceinline__ void frame_norm_adjoint_store(const f32x16 (&g)[2], f
       bf16x4 ov;
 #pragma unroll
       for (int k = 0; k < 4; ++k) ov[k] = f2bf(g[dt][4 * g4 + k] * gscale * k1 - x[dt][4 * g4 + k] * k2);
-      *(bf16x4*)(dst + dt * 32 + 8 * g4 + 4 * h) = ov;
+      *(bf16x4*)(dst + lane_row_ch(dt, g4, h)) = ov;
     }
 }
 
@@ -764,57 +565,24 @@ __global__ __launch_bounds__(512, 2) void frame_attn_qkv_bwd_kernel(const FrameQ
   float* del_lds = lse_lds + 256;
   const long long row = tok0 + wave * 32 + r;                // this lane's query row (pass A) = key row (pass B)
   const bool in = row < d.ntok;
-  frame_burst512<2, 0>(d.qkv + C, d.qkv + 2 * C, tok0, d.ntok, C3, C3, head, lds0, tid);      // region A; the own rows load under it
-  bf16x8 qf[4], dof[4];
-  float lse = 0.f, delta = 0.f;
+  frame_burst<IMG_DUAL, IMG_ROW, 512>(d.qkv + C, d.qkv + 2 * C, tok0, d.ntok, C3, C3, head, lds0, tid);      // region A; the own rows load under it
+  bf16x8 qf[1][4], dof[1][4];
+  float lse[1] = {0.f}, delta[1];
   {
-    const bf16* qg = d.qkv + (size_t)row * C3 + head * 64 + h * 8;
-    const bf16* dog = d.dout + (size_t)row * C + head * 64 + h * 8;
-    const bf16* og = d.out + (size_t)row * C + head * 64 + h * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      u32x4 v = u32x4{0u, 0u, 0u, 0u}, w = u32x4{0u, 0u, 0u, 0u}, o = u32x4{0u, 0u, 0u, 0u};
-      if (in) {
-        v = *(const u32x4*)(qg + ks * 16);
-        w = *(const u32x4*)(dog + ks * 16);
-        o = *(const u32x4*)(og + ks * 16);
-      }
-      qf[ks] = __builtin_bit_cast(bf16x8, v);
-      dof[ks] = __builtin_bit_cast(bf16x8, w);
-      const bf16x8 ofr = __builtin_bit_cast(bf16x8, o);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) delta += bf2f(dof[ks][e]) * bf2f(ofr[e]);
-    }
-    delta += __shfl_xor(delta, 32);
-    frame_row_norm(qf, SCALE_LOG2);
+    frame_bwd_own_rows(qf[0], dof[0], delta[0], d.qkv + (size_t)row * C3 + head * 64 + h * 8, d.dout + (size_t)row * C + head * 64 + h * 8,
+                       d.out + (size_t)row * C + head * 64 + h * 8, in);
+    frame_row_norm(qf[0], SCALE_LOG2);
     if (in) {
       const long long b = row / P;
-      lse = d.lse[(size_t)(b * d.heads + head) * P + (row - b * P)];
+      lse[0] = d.lse[(size_t)(b * d.heads + head) * P + (row - b * P)];
     }
-    if (h == 0) { lse_lds[wave * 32 + r] = lse; del_lds[wave * 32 + r] = delta; }
+    if (h == 0) { lse_lds[wave * 32 + r] = lse[0]; del_lds[wave * 32 + r] = delta[0]; }
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[ks]));      // every ordinary load consumed before region B is requested
+    for (int ks = 0; ks < 4; ++ks) asm volatile("" ::"v"(qf[0][ks]));      // every ordinary load consumed before region B is requested
   }
-  frame_burst512<2, 2>(d.qkv, d.dout, tok0, d.ntok, C3, C, head, lds0 + REG, tid);             // region B: lands under pass A
+  frame_burst<IMG_DUAL, IMG_DUAL, 512>(d.qkv, d.dout, tok0, d.ntok, C3, C, head, lds0 + REG, tid);             // region B: lands under pass A
   const int t0 = ((wave * 32) / P) * d.tiles;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2;
-  const int kr0 = r * 128 + ((h ^ ((((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 1) | ((r >> 2) & 1))) << 4);
-  const int vr0 = r * 128 + ((h ^ ((r >> 1) & 7)) << 4);
-  const int c0 = 2 * (grp & 1) + ((lane & 3) >> 1);
-  const int tbA = (4 * hh + q4) * 128 + ((c0 ^ hh) << 4) + 8 * (lane & 1);
-  const int tbB = (4 * hh + q4 + 8) * 128 + ((c0 ^ hh ^ 2) << 4) + 8 * (lane & 1);
-  const int tsw = (q4 >> 1) & 1;
-  auto ktr = [&](const unsigned char* kt_, int tokbase, int dt) __attribute__((always_inline)) {
-    const int o = tokbase * 128 + ((dt ^ tsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbA + o));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(kt_ + tbB + o));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const FrameBwdLane ln = frame_bwd_lane(lane);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");           // region A (the first 8 copies of this wave) has landed
   __syncthreads();
   frame_lds_norm<512>(smem, 1.f, tid);                        // K
@@ -822,44 +590,11 @@ __global__ __launch_bounds__(512, 2) void frame_attn_qkv_bwd_kernel(const FrameQ
   __syncthreads();
   // ---- pass A: dQ
   {
-    f32x16 dq[2];
+    f32x16 dq[1][2];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
-#pragma unroll 1
-    for (int t = t0; t < t0 + d.tiles; ++t) {
-      const unsigned char* Kt = smem + t * 2 * TB;
-      const unsigned char* Vt = Kt + TB;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        bf16x8 kf[4], vf[4], ktf[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          kf[ks] = *(const bf16x8*)(Kt + ((kr0 ^ (ks * 32)) + kt * 4096));
-          vf[ks] = *(const bf16x8*)(Vt + ((vr0 ^ (ks * 32)) + kt * 4096));
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) ktf[s2][dt] = ktr(Kt, kt * 32 + 16 * s2, dt);
-        f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          s = mfma32(kf[ks], qf[ks], s);
-          dp = mfma32(vf[ks], dof[ks], dp);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) s[rr] = __builtin_amdgcn_exp2f(s[rr] - lse) * (dp[rr] - delta);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 db = pack8(s, s2);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma32(ktf[s2][dt], db, dq[dt]);
-        }
-      }
-    }
-    if (in) frame_norm_adjoint_store(dq, 0.125f, d.qkv + (size_t)row * C3 + head * 64, d.dqkv + (size_t)row * C3 + head * 64, h);
+    for (int i = 0; i < 16; ++i) { dq[0][0][i] = 0.f; dq[0][1][i] = 0.f; }
+    frame_pass_a<1>(dq, qf, dof, lse, delta, smem, t0, d.tiles, ln);
+    if (in) frame_norm_adjoint_store(dq[0], 0.125f, d.qkv + (size_t)row * C3 + head * 64, d.dqkv + (size_t)row * C3 + head * 64, h);
   }
   dma_wait();                                                // region B has landed (and this wave's dq stores are out)
   __syncthreads();
@@ -867,72 +602,10 @@ __global__ __launch_bounds__(512, 2) void frame_attn_qkv_bwd_kernel(const FrameQ
   __syncthreads();
   // ---- pass B: dK, dV
   {
-    const unsigned char* Kown = smem + (wave >> 1) * 2 * TB + (wave & 1) * 4096;
-    const unsigned char* Vown = Kown + TB;
-    bf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      kf[ks] = *(const bf16x8*)(Kown + (kr0 ^ (ks * 32)));
-      vf[ks] = *(const bf16x8*)(Vown + (vr0 ^ (ks * 32)));
-    }
-    f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dk[0][i] = 0.f; dk[1][i] = 0.f; dv[0][i] = 0.f; dv[1][i] = 0.f; }
-#pragma unroll 1
-    for (int t = t0; t < t0 + d.tiles; ++t) {
-      const unsigned char* Qt = smem + REG + t * 2 * TB;
-      const unsigned char* dOt = Qt + TB;
-#pragma unroll 1
-      for (int qt = 0; qt < 2; ++qt) {
-        bf16x8 qa[4], da[4], dotf[2][2], qtf[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          qa[ks] = *(const bf16x8*)(Qt + ((kr0 ^ (ks * 32)) + qt * 4096));
-          da[ks] = *(const bf16x8*)(dOt + ((kr0 ^ (ks * 32)) + qt * 4096));
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            dotf[s2][dt] = ktr(dOt, qt * 32 + 16 * s2, dt);
-            qtf[s2][dt] = ktr(Qt, qt * 32 + 16 * s2, dt);
-          }
-        f32x16 s, dp, pv;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          s = mfma32(qa[ks], kf[ks], s);
-          dp = mfma32(da[ks], vf[ks], dp);
-        }
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int qb4 = t * 64 + qt * 32 + 8 * g4 + 4 * h;
-          const float4 ls = *(const float4*)(lse_lds + qb4), de = *(const float4*)(del_lds + qb4);
-          const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dev[4] = {de.x, de.y, de.z, de.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int rr = 4 * g4 + k;
-            const float p = __builtin_amdgcn_exp2f(s[rr] - lsv[k]);
-            pv[rr] = p;
-            s[rr] = p * (dp[rr] - dev[k]) * 0.125f;
-          }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 pb = pack8(pv, s2);
-          const bf16x8 db = pack8(s, s2);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            dv[dt] = mfma32(dotf[s2][dt], pb, dv[dt]);
-            dk[dt] = mfma32(qtf[s2][dt], db, dk[dt]);
-          }
-        }
-      }
-    }
+    const FrameDkv g = frame_pass_b(smem, smem + REG, lse_lds, del_lds, wave, t0, d.tiles, ln);
     if (in) {
-      frame_norm_adjoint_store(dk, 1.f / SCALE_LOG2, d.qkv + (size_t)row * C3 + C + head * 64, d.dqkv + (size_t)row * C3 + C + head * 64, h);
-      frame_norm_adjoint_store(dv, 1.f, d.qkv + (size_t)row * C3 + 2 * C + head * 64, d.dqkv + (size_t)row * C3 + 2 * C + head * 64, h);
+      frame_norm_adjoint_store(g.dk, 1.f / SCALE_LOG2, d.qkv + (size_t)row * C3 + C + head * 64, d.dqkv + (size_t)row * C3 + C + head * 64, h);
+      frame_norm_adjoint_store(g.dv, 1.f, d.qkv + (size_t)row * C3 + 2 * C + head * 64, d.dqkv + (size_t)row * C3 + 2 * C + head * 64, h);
     }
   }
 #endif

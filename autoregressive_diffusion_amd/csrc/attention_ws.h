@@ -47,23 +47,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int C = a.C, Lq = a.Lq, Lk = a.Lk;
   const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-  const int nslots = a.sched_slots;
-  const int32_t* sched = a.sched + (size_t)blockIdx.x * nslots;
-  auto item_at = [&](int i) __attribute__((always_inline)) { return i < nslots ? __builtin_amdgcn_readfirstlane(sched[i]) : -1; };
+  const WorkList work_list{a.sched + (size_t)blockIdx.x * a.sched_slots, a.sched_slots};
   const int tmask = (1 << d.tshift) - 1;
 
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------------ loader waves
     const int lw = wave - 4;
     const int drow = 8 * lw + (lane >> 3), dpp = lane & 7;        // piece (lw + 4 i): row 32 i + drow, 16-byte part dpp
-    const int ksw = (dpp ^ ((drow >> 1) & 7)) * 16, vsw_ = (dpp ^ (4 * ((drow >> 1) & 1))) * 16;
-    constexpr int OOB = (int)0x80000000;
+    const int ksw = (dpp ^ row_image(drow)) * 16, vsw_ = (dpp ^ tr_image(drow)) * 16;     // K, Q: row image; V: transposing image
     // everything of item `itm` that block / Q requests need (wave-uniform values + the table row in a VGPR)
     struct Src { i32x4 rs_k, rs_v, rs_q; int kvo, vvo, qvo, qrow0, nblk, kvl; };
     auto open_item = [&](int itm) __attribute__((always_inline)) {
       Src s;
-      const int pair = itm >> 16, qb128 = itm & 0xffff;
-      const int b = pair / a.heads, head = pair - b * a.heads;
+      const WorkItem wi = item_decode(itm, a.heads);
+      const int b = wi.b, head = wi.head, qb128 = wi.blk;
       const int trow = qb128 >> d.tshift;
       const int nent = __builtin_amdgcn_readfirstlane(a.kv_num[trow]);
       s.nblk = nent << d.tshift;
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
         dma16(s.rs_q, ok ? s.qvo : OOB, (s.qrow0 + 32 * i) * C * 2, dst + i * 4096);
       }
     };
-    int item = item_at(0);
+    int item = work_list.at(0);
     if (item < 0) return;
     Src cur = open_item(item);
     issue_q(cur, 0);
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
         __syncthreads();                           // barrier_j: block j + 1 landed; block j - 1 released
         if (j + 3 < nblk) issue_block(cur, j + 3);
       }
-      const int next = item_at(it + 1);
+      const int next = work_list.at(it + 1);
       Src nxt = cur;
       if (next >= 0) {
         nxt = open_item(next);                     // (nothing of this item is in flight any more)
@@ -135,20 +132,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
   // -------------------------------------------------------------------------------------------------- compute waves
   const int r = lane & 31, h = lane >> 5;
   const int qw = wave & 1, st = wave >> 1;
-  const int kb0 = (64 * st + r) * 128 + ((h ^ ((r >> 1) & 7)) << 4);
+  const int kb0 = (64 * st + r) * 128 + ((h ^ row_image(r)) << 4);
   const int grp = lane >> 4, hh = grp >> 1, q4 = (lane & 15) >> 2, pcol = (lane & 3) * 4 + 16 * (grp & 1);
-  const int vb0 = 128 * 128 + (64 * st + 4 * hh + q4) * 128 + pcol * 2, vsw = (q4 >> 1) & 1;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  auto vtr = [&](const unsigned char* slot, int tokbase, int dt) __attribute__((always_inline)) {
-    const unsigned char* p0 = slot + vb0 + tokbase * 128 + ((dt ^ vsw) * 64);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * 128));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const TrLane vt{128 * 128 + (64 * st + 4 * hh + q4) * 128 + pcol * 2, (q4 >> 1) & 1};
   f32x16 zero16;
 #pragma unroll
   for (int i = 0; i < 16; ++i) zero16[i] = 0.f;
@@ -161,12 +147,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
   for (int e = 0; e < 8; ++e) sel16[e] = f2bf((((lane >> 4) ^ ((lane & 15) >> 2)) & 1) ? 0.f : 1.f);
   typedef __attribute__((ext_vector_type(4))) float f32x4_;
 
-  int item = item_at(0);
+  int item = work_list.at(0);
   WS_STAMP_DECL
 #pragma unroll 1
   for (int it = 0; item >= 0; ++it) {
-    const int pair = item >> 16, qb128 = item & 0xffff;
-    const int b = pair / a.heads, head = pair - b * a.heads;
+    const WorkItem wi = item_decode(item, a.heads);
+    const int b = wi.b, head = wi.head, qb128 = wi.blk;
     const int qw0 = qb128 * 128 + qw * 64;          // lane r of query block x: row qw0 + 32 x + r
     // per-item copy of the lane id for everything OUTSIDE the block loop (Q fragment addresses, mask, epilogue): hipcc
     // otherwise hoists ~40 lane-constant address registers out of the item loop and spills them to scratch around the
@@ -187,14 +173,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
     for (int i = 0; i < 4; ++i) { osum[0][i] = 0.f; osum[1][i] = 0.f; }
 
     auto load_k = [&](bf16x8 (&kf)[4], const unsigned char* S0, int kt) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) kf[ks] = *(const bf16x8*)(S0 + ((kb0 ^ (ks * 32)) + kt * 4096));
+      row_frag(kf, S0, kb0, kt * 4096);
     };
     auto load_v = [&](bf16x8 (&vf)[2][2], const unsigned char* S0, int kt) __attribute__((always_inline)) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) vf[s2][dt] = vtr(S0, kt * 32 + 16 * s2, dt);
+        for (int dt = 0; dt < 2; ++dt) vf[s2][dt] = tr_read(S0, vt, kt * 32 + 16 * s2, dt);
     };
     // mask of the list's last block as start values of S^T (x, kt): 0 (allowed) / -1e30.  An accumulator register group
     // rr = 4 g .. 4 g + 3 holds 4 consecutive, 4-aligned keys: one frame (P is a power of two >= 4) and one side of Lk (a
@@ -251,7 +236,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
           const int row = 64 * qw + 32 * x + r_;
-          qf[x][ks] = *(const bf16x8*)(Qt + row * 128 + (((2 * ks + h_) ^ ((row >> 1) & 7)) << 4));   // (q carries log2(e)/8)
+          qf[x][ks] = *(const bf16x8*)(Qt + row * 128 + (((2 * ks + h_) ^ row_image(row)) << 4));   // (q carries log2(e)/8)
         }
     }
     // register sets: kA = K fragments of half kt = 0, kB of kt = 1; vA = V^T fragments of kt = 0, vB of kt = 1;
@@ -381,7 +366,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ws_kernel(const AttnDev d) {
         if (q0 + row0 + 8 * i < Lq) *(u32x4*)(og + (size_t)(8 * i) * C) = v;
       }
     }
-    item = item_at(it + 1);
+    item = work_list.at(it + 1);
     WS_STAMP(6)
   }
 #ifdef ATTN_STAMP

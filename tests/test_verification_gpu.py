@@ -163,7 +163,7 @@ def test_attention_core_bf16_faithful(kind, B, T, H, m):
     e = sd(out, ref)
     # replayed: the kernels exponentiate without a row maximum (unit vectors: |score| <= 11.6 in the log2 domain) and round
     # P = 2^s to bf16 for the P V product; the persistent training kernel forms the row sum from the ROUNDED values on the matrix
-    # pipe (csrc/attention_ws.h:22-25, 231), the grid kernel from the fp32 ones (csrc/attention.hip:281-287)
+    # pipe (csrc/attention_ws.h: the header and `pv` of attn_fwd_ws_kernel), the grid kernel from the fp32 ones (`softmax` of attn_fwd_kernel)
     p32 = torch.exp2((q.float() @ k.float().transpose(-1, -2)).masked_fill(torch.isinf(s), float("-inf")))
     pr = bfr(p32).double()
     den = pr.sum(-1, keepdim=True) if kind == "video" else p32.double().sum(-1, keepdim=True)
@@ -250,7 +250,7 @@ def _gated_backward_bf16_faithful_case(B, T, H, W, cin, cout):
 def test_attention_core_backward_bf16_faithful(kind, B, T, H, m):
     """dQ, dK, dV of the flash backward (persistent dQ and dK/dV kernels for the training table, grid kernels per frame) replayed on
     their own operands: P = 2^(s - lse) from the forward's stored row constants, delta = <dO, O> from the forward's bf16 output,
-    P and dS rounded to bf16 in front of their products (csrc/attention.hip:519-534, 708-731), the 1/8 of the score scale where
+    P and dS rounded to bf16 in front of their products (`dsoft` of attn_bwd_dq_kernel and attn_bwd_dkv_kernel), the 1/8 of the score scale where
     each kernel applies it."""
     from autoregressive_diffusion_amd import ops
     torch.manual_seed(9)
@@ -592,7 +592,7 @@ def test_qkv_norm_hd_bf16_faithful(B, T, H, m, d):
     """The same pass for heads of 8 / 16 / 32 channels (Block(channels_per_head=), networks_edm2.py:28; the reference's tests use
     16): per-head norm over d channels, rotary embedding with its partner d/2 channels away, q scaled by log2(e)/sqrt(d), heads
     zero-padded to the 64 channels the attention kernels are written for; and the adjoint, which takes dq as the 64-channel
-    kernels return it (scaled by 8: csrc/attention.hip:556) and the padded dk, dv."""
+    kernels return it (scaled by 8: the epilogue of attn_bwd_dq_kernel) and the padded dk, dv."""
     from autoregressive_diffusion_amd import ops
     from autoregressive_diffusion_amd._lib import lib, check
     torch.manual_seed(16 + d)
