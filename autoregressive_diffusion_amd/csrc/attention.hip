@@ -587,571 +587,8 @@ __global__ void attn_dkv_reduce_kernel(const float* __restrict__ part, bf16* __r
 }
 
 // ================================================================================================================
-// small HBM-bound helpers
-
-// qkv [tok][3C] (channel = s*C + head*64 + c) -> q,k,v [tok][C], each 64-vector normalised: x / (eps + |x|/8)
-// kv_tpb > 0: k and v go to a KV ring -- token r of batch b lands at element b * kv_bstride + (kv_off + r) * C
-__global__ void qkv_norm_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ q, bf16* __restrict__ k,
-                                bf16* __restrict__ v, long long nvec, int C, long long kv_tpb, long long kv_bstride,
-                                long long kv_off) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;
-  const int hpt = 3 * C / 64;                       // vectors per token
-  const long long tok = vec / hpt;
-  const int vi = (int)(vec % hpt);                  // = s*heads + head
-  const int s = vi / (C / 64), hd = vi % (C / 64);
-  const bf16x8 x = *(const bf16x8*)(qkv + tok * 3 * C + (size_t)vi * 64 + part * 8);
-  float f[8], ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { f[i] = bf2f(x[i]); ss += f[i] * f[i]; }
-  ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
-  // q leaves with the softmax scale folded in (one rounding): q' = log2(e)/8 * normalised q, so that every attention kernel
-  // gets its log2-domain scores straight out of the MFMA (exp2(q'.k - lse), no multiply per score element)
-  const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = f2bf(f[i] * inv);
-  bf16* dst = (s == 0) ? q : (s == 1) ? k : v;
-  long long row = tok * C;
-  if (s != 0 && kv_tpb > 0) row = (tok / kv_tpb) * kv_bstride + (kv_off + tok % kv_tpb) * C;
-  *(bf16x8*)(dst + row + hd * 64 + part * 8) = o;
-}
-
-__global__ void qkv_norm_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dq,
-                                    const bf16* __restrict__ dk, const bf16* __restrict__ dv,
-                                    bf16* __restrict__ dqkv, long long nvec, int C) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;
-  const int hpt = 3 * C / 64;
-  const long long tok = vec / hpt;
-  const int vi = (int)(vec % hpt);
-  const int s = vi / (C / 64), hd = vi % (C / 64);
-  const bf16x8 x = *(const bf16x8*)(qkv + tok * 3 * C + (size_t)vi * 64 + part * 8);
-  const bf16* src = (s == 0) ? dq : (s == 1) ? dk : dv;
-  const bf16x8 g = *(const bf16x8*)(src + tok * C + hd * 64 + part * 8);
-  float f[8], gg[8], ss = 0.f, dot = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { f[i] = bf2f(x[i]); gg[i] = bf2f(g[i]); ss += f[i] * f[i]; dot += f[i] * gg[i]; }
-  ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
-  dot += __shfl_xor(dot, 1); dot += __shfl_xor(dot, 2); dot += __shfl_xor(dot, 4);
-  const float n = sqrtf(ss), sden = 1e-4f + n * 0.125f;
-  const float k1 = 1.f / sden, k2 = (n > 0.f) ? dot * 0.125f / (sden * sden * n) : 0.f;
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = f2bf(gg[i] * k1 - f[i] * k2);
-  *(bf16x8*)(dqkv + tok * 3 * C + (size_t)vi * 64 + part * 8) = o;
-}
-
-// qkv_norm_kernel + the rotary embedding of q and k in one pass (training: position = (token / P) mod pos_mod; tables
-// [pos][64] fp32: cos, sin, scale, scale duplicated over the two halves like RoPe.py:21-32).  The rotation partner of
-// channel c is c ^ 32 = the same register of lane ^ 4 (8 lanes x 8 channels cover a head).  The normalised value is
-// rotated in fp32: q, k are rounded to bf16 once (the two-kernel path rounds the normalised vector first).
-//   q' = log2(e)/8 * (u cos + rot(u) sin) * scale,   k' = (u cos + rot(u) sin) / scale,   v' = u      (u = x/(eps+|x|/8))
-__global__ void qkv_norm_rope_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ q, bf16* __restrict__ k,
-                                     bf16* __restrict__ v, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                     const float* __restrict__ scale_t, long long nvec, int C, int P, int pos_mod) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;                            // (nvec * 8 is a multiple of 64: whole waves leave together)
-  const int hpt = 3 * C / 64;
-  const long long tok = vec / hpt;
-  const int vi = (int)(vec % hpt);
-  const int s = vi / (C / 64), hd = vi % (C / 64);
-  const bf16x8 x = *(const bf16x8*)(qkv + tok * 3 * C + (size_t)vi * 64 + part * 8);
-  float f[8], ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { f[i] = bf2f(x[i]); ss += f[i] * f[i]; }
-  ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
-  const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
-  const size_t tb = (size_t)((tok / P) % pos_mod) * 64 + part * 8;
-  const float sg = (part < 4) ? -1.f : 1.f;          // rotate_half: [-x2, x1]
-  // the three table rows of this lane's 8 channels as 16-byte loads (element-wise 4-byte loads made the pass VMEM-issue
-  // bound: 24 table loads per 16 bytes of output, 1.7 TB/s)
-  float cs[8], sn[8], sc[8];
-  if (s != 2) {
-    *(float4*)&cs[0] = *(const float4*)(cos_t + tb); *(float4*)&cs[4] = *(const float4*)(cos_t + tb + 4);
-    *(float4*)&sn[0] = *(const float4*)(sin_t + tb); *(float4*)&sn[4] = *(const float4*)(sin_t + tb + 4);
-    *(float4*)&sc[0] = *(const float4*)(scale_t + tb); *(float4*)&sc[4] = *(const float4*)(scale_t + tb + 4);
-  }
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float u = f[i] * inv;
-    const float up = __shfl_xor(u, 4);                // (every lane of the 8-lane group takes part: no divergence above)
-    float val = u;
-    if (s != 2) {
-      val = u * cs[i] + sg * up * sn[i];
-      val = (s == 0) ? val * sc[i] : val / sc[i];
-    }
-    o[i] = f2bf(val);
-  }
-  bf16* dst = (s == 0) ? q : (s == 1) ? k : v;
-  *(bf16x8*)(dst + tok * C + hd * 64 + part * 8) = o;
-}
-
-// One NEW frame per sequence of the KV-cached sampler (attention_modules.py:51-70): normalisation of q, k, v and the rotary
-// embedding of q and k at the frame's position `pos` (= n_keys - 1: tables row pos) in one pass.  Outputs: q rotated (with
-// the softmax scale), k UN-rotated and v into the KV ring behind the committed frames (the cache keeps un-rotated keys:
-// every later frame count re-rotates them, RoPe.py:55-57), k rotated into the ring's ROTATED image `kr`, whose committed
-// frames were rotated once for this frame count (KVRing.rotate_committed) instead of once per UNet evaluation.
-__global__ void qkv_norm_rope_eval_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ q, bf16* __restrict__ k,
-                                          bf16* __restrict__ v, bf16* __restrict__ kr, const float* __restrict__ cos_t,
-                                          const float* __restrict__ sin_t, const float* __restrict__ scale_t, long long nvec,
-                                          int C, long long kv_tpb, long long kv_bstride, long long kv_off, int pos) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;                            // (nvec * 8 is a multiple of 64: whole waves leave together)
-  const int hpt = 3 * C / 64;
-  const long long tok = vec / hpt;
-  const int vi = (int)(vec % hpt);
-  const int s = vi / (C / 64), hd = vi % (C / 64);
-  const bf16x8 x = *(const bf16x8*)(qkv + tok * 3 * C + (size_t)vi * 64 + part * 8);
-  float f[8], ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { f[i] = bf2f(x[i]); ss += f[i] * f[i]; }
-  ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
-  const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
-  const size_t tb = (size_t)pos * 64 + part * 8;
-  const float sg = (part < 4) ? -1.f : 1.f;          // rotate_half: [-x2, x1]
-  bf16x8 plain, rot;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    // like the two-launch path (qkv_norm, then rope on its bf16 output) the rotation sees the bf16-rounded vector, so that
-    // the rotated key of a frame is the same number whether it is rotated now or re-rotated from the ring later
-    const float u = bf2f(f2bf(f[i] * inv));
-    const float up = __shfl_xor(u, 4);
-    plain[i] = f2bf(u);
-    float val = u;
-    if (s != 2) {
-      val = u * cos_t[tb + i] + sg * up * sin_t[tb + i];
-      const float scl = scale_t[tb + i];
-      val = (s == 0) ? val * scl : val / scl;
-    }
-    rot[i] = f2bf(val);
-  }
-  const long long ring = (tok / kv_tpb) * kv_bstride + (kv_off + tok % kv_tpb) * C + hd * 64 + part * 8;
-  if (s == 0) *(bf16x8*)(q + tok * C + hd * 64 + part * 8) = rot;
-  else if (s == 1) { *(bf16x8*)(k + ring) = plain; *(bf16x8*)(kr + ring) = rot; }
-  else *(bf16x8*)(v + ring) = plain;
-}
-
-// The sampler's attention input in ONE launch (31 evaluations per generated frame, every graph node costs ~5 us): the
-// attn_qkv 1x1 convolution of the new frame(s) (MPConv, attention_modules.py:47), the per-head normalisation and -- when
-// tables are given -- the rotary embedding at table row `pos`, written where qkv_norm_rope_eval_kernel / qkv_norm_kernel
-// write: q [tok][C] (with the softmax scale), k / v dense or behind the committed frames of the KV ring, kr = the rotated
-// key into the ring's rotated image.  One workgroup = 128 tokens x one (q|k|v, head) slice of 64 output channels; wave w
-// owns tokens 32w..32w+31 (MFMA D[channel][token]: a lane holds 32 of the head's 64 channels of ONE token, lane ^ 32 the
-// others; the rotation partner c + 32 of channel c is the other accumulator of the same lane).  The convolution result is
-// rounded to bf16 before the normalisation, like the tensor the two-launch path stores in between.
-template <int KC>
-__global__ __launch_bounds__(256) void qkv_eval_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                       bf16* __restrict__ q, bf16* __restrict__ k, bf16* __restrict__ v,
-                                                       bf16* __restrict__ kr, const float* __restrict__ cos_t,
-                                                       const float* __restrict__ sin_t, const float* __restrict__ scale_t,
-                                                       long long M, int C, int CinP, long long kv_tpb, long long kv_bstride,
-                                                       long long kv_off, int pos, long long split, bf16* __restrict__ q2,
-                                                       bf16* __restrict__ k2, bf16* __restrict__ v2) {
-  // K is staged KC input channels at a time (the whole K for C <= 256: every load of the tile is in flight at once -- the
-  // launch is pure latency, ~10 us with four 64-channel rounds of load / barrier / multiply, half of that in one round)
-  constexpr int ROWB = KC * 2 + 16;                          // + 16 bytes: conflict-free 16-byte fragment reads
-  constexpr int PCS = KC / 8;                                // 16-byte pieces per row
-  __shared__ __attribute__((aligned(16))) unsigned char xs[128 * ROWB];
-  __shared__ __attribute__((aligned(16))) unsigned char ws[64 * ROWB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const long long m0 = (long long)blockIdx.x * 128;
-  // (slot and head from the grid: a division by a run-time value is ~40 instructions in front of the first address of a launch that
-  // lasts 17 K cycles; round 6)
-  const int hd = blockIdx.y, s = blockIdx.z, vi = s * (int)gridDim.y + hd;
-  const bf16* wrow = w + (size_t)vi * 64 * CinP;
-  const int mrows = (M - m0 < 128) ? (int)(M - m0) : 128;    // rows beyond M are never read back by a valid token
-  f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
-  // the rotation's table values depend on the lane only: requested FIRST, so that their round trip runs under the tile loads instead
-  // of behind the MFMAs (round 6: the launch is a latency chain, 129 of them make an evaluation)
-  const bool rope = cos_t != nullptr && s != 2;
-  const size_t tb = (size_t)pos * 64;
-  float tc0[16], ts0[16], tc1[16], ts1[16], tq0[16], tq1[16];
-  if (rope) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int c = 8 * g + 4 * h;
-      const float4 a0 = *(const float4*)(cos_t + tb + c), a1 = *(const float4*)(cos_t + tb + c + 32);
-      const float4 b0 = *(const float4*)(sin_t + tb + c), b1 = *(const float4*)(sin_t + tb + c + 32);
-      const float4 q0 = *(const float4*)(scale_t + tb + c), q1 = *(const float4*)(scale_t + tb + c + 32);
-      tc0[4 * g] = a0.x; tc0[4 * g + 1] = a0.y; tc0[4 * g + 2] = a0.z; tc0[4 * g + 3] = a0.w;
-      tc1[4 * g] = a1.x; tc1[4 * g + 1] = a1.y; tc1[4 * g + 2] = a1.z; tc1[4 * g + 3] = a1.w;
-      ts0[4 * g] = b0.x; ts0[4 * g + 1] = b0.y; ts0[4 * g + 2] = b0.z; ts0[4 * g + 3] = b0.w;
-      ts1[4 * g] = b1.x; ts1[4 * g + 1] = b1.y; ts1[4 * g + 2] = b1.z; ts1[4 * g + 3] = b1.w;
-      tq0[4 * g] = q0.x; tq0[4 * g + 1] = q0.y; tq0[4 * g + 2] = q0.z; tq0[4 * g + 3] = q0.w;
-      tq1[4 * g] = q1.x; tq1[4 * g + 1] = q1.y; tq1[4 * g + 2] = q1.z; tq1[4 * g + 3] = q1.w;
-    }
-  }
-  for (int c0 = 0; c0 < C; c0 += KC) {
-    if (c0) __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 64 * PCS / 256; ++i) {               // weight tile: 64 rows
-      const int e = i * 256 + tid, row = e / PCS, pc = e % PCS;
-      *(u32x4*)(ws + row * ROWB + pc * 16) = *(const u32x4*)(wrow + (size_t)row * CinP + c0 + pc * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < 128 * PCS / 256; ++i) {              // x tile: 128 rows
-      const int e = i * 256 + tid, row = e / PCS, pc = e % PCS;
-      if (row < mrows) *(u32x4*)(xs + row * ROWB + pc * 16) = *(const u32x4*)(x + (size_t)(m0 + row) * C + c0 + pc * 8);
-    }
-    __syncthreads();
-    if (wave * 32 < mrows) {
-#pragma unroll
-      for (int ks = 0; ks < KC / 16; ++ks) {
-        const bf16x8 xf = *(const bf16x8*)(xs + (wave * 32 + r) * ROWB + (ks * 2 + h) * 16);
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-          const bf16x8 wf = *(const bf16x8*)(ws + (n * 32 + r) * ROWB + (ks * 2 + h) * 16);
-          acc[n] = mfma32(wf, xf, acc[n]);
-        }
-      }
-    }
-  }
-  const long long tok = m0 + wave * 32 + r;
-  float f[2][16], ss = 0.f;
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { f[n][i] = bf2f(f2bf(acc[n][i])); ss += f[n][i] * f[n][i]; }
-  ss += __shfl_xor(ss, 32);
-  const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
-  if (tok >= M) return;
-  // tokens >= split: the 2-D rows of a guided pair launch (oniris_qkv_eval_pair) -- normalised, un-rotated q | k | v, dense
-  // [token - split][C] in the side buffers (what the frame form of this launch writes)
-  const bool side = tok >= split;
-  bf16* const qo = side ? q2 : q;
-  bf16* const ko = side ? k2 : k;
-  bf16* const vo = side ? v2 : v;
-  const bool rot_on = rope && !side;
-  const long long dense = (side ? tok - split : tok) * C + hd * 64;
-  long long ring = dense;
-  if (kv_tpb > 0 && !side) {                                          // (one sequence: tok < kv_tpb, no 64-bit division on the way to the stores)
-    const long long sq = (tok < kv_tpb) ? 0 : tok / kv_tpb;
-    ring = sq * kv_bstride + (kv_off + tok - sq * kv_tpb) * C + hd * 64;
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    bf16x4 plain[2], rot[2];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int i = 4 * g + kk, c = 8 * g + 4 * h + kk;       // channel c (first half) and c + 32 (second half) of the head
-      // (as in qkv_norm_rope_eval_kernel the rotation sees the bf16-rounded normalised vector)
-      const float u0 = bf2f(f2bf(f[0][i] * inv)), u1 = bf2f(f2bf(f[1][i] * inv));
-      plain[0][kk] = f2bf(u0); plain[1][kk] = f2bf(u1);
-      float v0 = u0, v1 = u1;
-      if (rot_on) {
-        v0 = u0 * tc0[i] - u1 * ts0[i];                       // rotate_half: [-x2, x1]
-        v1 = u1 * tc1[i] + u0 * ts1[i];
-        const float s0 = tq0[i], s1 = tq1[i];
-        v0 = (s == 0) ? v0 * s0 : v0 / s0;
-        v1 = (s == 0) ? v1 * s1 : v1 / s1;
-      }
-      rot[0][kk] = f2bf(v0); rot[1][kk] = f2bf(v1);
-    }
-    const int co = 8 * g + 4 * h;
-    if (s == 0) {
-      *(bf16x4*)(qo + dense + co) = rot[0]; *(bf16x4*)(qo + dense + co + 32) = rot[1];
-    } else if (s == 1) {
-      *(bf16x4*)(ko + ring + co) = plain[0]; *(bf16x4*)(ko + ring + co + 32) = plain[1];
-      if (kr && !side) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
-    } else {
-      *(bf16x4*)(vo + ring + co) = plain[0]; *(bf16x4*)(vo + ring + co + 32) = plain[1];
-    }
-  }
-}
-
-// qkv_eval_kernel for a FEW tiles (one frame per sequence in the cached sampler; round 6, after conv1x1_few.h): a workgroup owns 32 tokens x
-// the 64 channels of one (slot, head) and its four waves split the K -- wave w takes the 64-channel rounds w, w + 4, ... with every operand
-// loaded global -> registers in MFMA fragment layout (no LDS staging, no barrier in the K loop); the partial tiles meet in LDS once and
-// wave 0 runs the epilogue of qkv_eval_kernel (same operations, same order; the conv result sums K in another order).
-__global__ __launch_bounds__(256) void qkv_eval_few_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                           bf16* __restrict__ q, bf16* __restrict__ k, bf16* __restrict__ v,
-                                                           bf16* __restrict__ kr, const float* __restrict__ cos_t,
-                                                           const float* __restrict__ sin_t, const float* __restrict__ scale_t,
-                                                           long long M, int C, int CinP, long long kv_tpb, long long kv_bstride,
-                                                           long long kv_off, int pos, long long split, bf16* __restrict__ q2,
-                                                           bf16* __restrict__ k2, bf16* __restrict__ v2) {
-  __shared__ float red[3 * 2 * 16 * 64];           // waves 1..3 -> wave 0: [wave - 1][n-tile][accumulator register][lane]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
-  const long long tok = (long long)blockIdx.x * 32 + r;
-  const int hd = blockIdx.y, s = blockIdx.z, vi = s * (int)gridDim.y + hd;
-  const bool tvalid = tok < M;
-  const bf16* xrow = x + (size_t)(tvalid ? tok : 0) * C;
-  const bf16* wrow0 = w + ((size_t)vi * 64 + r) * CinP;
-  const bf16* wrow1 = wrow0 + (size_t)32 * CinP;
-  const bool rope = cos_t != nullptr && s != 2;
-  const size_t tb = (size_t)pos * 64;
-  // (wave 0 runs the epilogue: its rotary-table values are requested first, like qkv_eval_kernel's)
-  float tc0[16], ts0[16], tc1[16], ts1[16], tq0[16], tq1[16];
-  if (rope && wave == 0) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int c = 8 * g + 4 * h;
-      const float4 a0 = *(const float4*)(cos_t + tb + c), a1 = *(const float4*)(cos_t + tb + c + 32);
-      const float4 b0 = *(const float4*)(sin_t + tb + c), b1 = *(const float4*)(sin_t + tb + c + 32);
-      const float4 q0 = *(const float4*)(scale_t + tb + c), q1 = *(const float4*)(scale_t + tb + c + 32);
-      tc0[4 * g] = a0.x; tc0[4 * g + 1] = a0.y; tc0[4 * g + 2] = a0.z; tc0[4 * g + 3] = a0.w;
-      tc1[4 * g] = a1.x; tc1[4 * g + 1] = a1.y; tc1[4 * g + 2] = a1.z; tc1[4 * g + 3] = a1.w;
-      ts0[4 * g] = b0.x; ts0[4 * g + 1] = b0.y; ts0[4 * g + 2] = b0.z; ts0[4 * g + 3] = b0.w;
-      ts1[4 * g] = b1.x; ts1[4 * g + 1] = b1.y; ts1[4 * g + 2] = b1.z; ts1[4 * g + 3] = b1.w;
-      tq0[4 * g] = q0.x; tq0[4 * g + 1] = q0.y; tq0[4 * g + 2] = q0.z; tq0[4 * g + 3] = q0.w;
-      tq1[4 * g] = q1.x; tq1[4 * g + 1] = q1.y; tq1[4 * g + 2] = q1.z; tq1[4 * g + 3] = q1.w;
-    }
-  }
-  f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
-  const int nround = C >> 6;
-#pragma unroll 1
-  for (int ch = wave; ch < nround; ch += 4) {
-    const int c0 = ch * 64 + h * 8;
-    u32x4 w0[4], w1[4], xv[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int c = c0 + ks * 16;
-      w0[ks] = *(const u32x4*)(wrow0 + c);
-      w1[ks] = *(const u32x4*)(wrow1 + c);
-      xv[ks] = tvalid ? *(const u32x4*)(xrow + c) : u32x4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8 xf = __builtin_bit_cast(bf16x8, xv[ks]);
-      acc[0] = mfma32(__builtin_bit_cast(bf16x8, w0[ks]), xf, acc[0]);
-      acc[1] = mfma32(__builtin_bit_cast(bf16x8, w1[ks]), xf, acc[1]);
-    }
-  }
-  if (wave != 0) {
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) red[(((wave - 1) * 2 + n) * 16 + i) * 64 + lane] = acc[n][i];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      acc[n][i] = ((acc[n][i] + red[((0 * 2 + n) * 16 + i) * 64 + lane]) + red[((1 * 2 + n) * 16 + i) * 64 + lane]) +
-                  red[((2 * 2 + n) * 16 + i) * 64 + lane];
-  float f[2][16], ss = 0.f;
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { f[n][i] = bf2f(f2bf(acc[n][i])); ss += f[n][i] * f[n][i]; }
-  ss += __shfl_xor(ss, 32);
-  const float inv = ((s == 0) ? SCALE_LOG2 : 1.f) / (1e-4f + sqrtf(ss) * 0.125f);
-  if (!tvalid) return;
-  // tokens >= split: the 2-D rows of a guided pair launch (oniris_qkv_eval_pair) -- normalised, un-rotated q | k | v, dense
-  // [token - split][C] in the side buffers (what the frame form of this launch writes)
-  const bool side = tok >= split;
-  bf16* const qo = side ? q2 : q;
-  bf16* const ko = side ? k2 : k;
-  bf16* const vo = side ? v2 : v;
-  const bool rot_on = rope && !side;
-  const long long dense = (side ? tok - split : tok) * C + hd * 64;
-  long long ring = dense;
-  if (kv_tpb > 0 && !side) {
-    const long long sq = (tok < kv_tpb) ? 0 : tok / kv_tpb;
-    ring = sq * kv_bstride + (kv_off + tok - sq * kv_tpb) * C + hd * 64;
-  }
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    bf16x4 plain[2], rot[2];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int i = 4 * g + kk;
-      const float u0 = bf2f(f2bf(f[0][i] * inv)), u1 = bf2f(f2bf(f[1][i] * inv));
-      plain[0][kk] = f2bf(u0); plain[1][kk] = f2bf(u1);
-      float v0 = u0, v1 = u1;
-      if (rot_on) {
-        v0 = u0 * tc0[i] - u1 * ts0[i];
-        v1 = u1 * tc1[i] + u0 * ts1[i];
-        const float s0 = tq0[i], s1 = tq1[i];
-        v0 = (s == 0) ? v0 * s0 : v0 / s0;
-        v1 = (s == 0) ? v1 * s1 : v1 / s1;
-      }
-      rot[0][kk] = f2bf(v0); rot[1][kk] = f2bf(v1);
-    }
-    const int co = 8 * g + 4 * h;
-    if (s == 0) {
-      *(bf16x4*)(qo + dense + co) = rot[0]; *(bf16x4*)(qo + dense + co + 32) = rot[1];
-    } else if (s == 1) {
-      *(bf16x4*)(ko + ring + co) = plain[0]; *(bf16x4*)(ko + ring + co + 32) = plain[1];
-      if (kr && !side) { *(bf16x4*)(kr + ring + co) = rot[0]; *(bf16x4*)(kr + ring + co + 32) = rot[1]; }
-    } else {
-      *(bf16x4*)(vo + ring + co) = plain[0]; *(bf16x4*)(vo + ring + co + 32) = plain[1];
-    }
-  }
-}
-
-// adjoint of qkv_norm_rope_kernel: dq (w.r.t. the UNSCALED rotated q, as the attention backward returns it), dk, dv ->
-// dqkv.  R^T g = g cos - rot(g sin) and the scale vector is equal in both halves, so it commutes with the rotation.
-__global__ void qkv_norm_rope_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dq,
-                                         const bf16* __restrict__ dk, const bf16* __restrict__ dv, bf16* __restrict__ dqkv,
-                                         const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                         const float* __restrict__ scale_t, long long nvec, int C, int P, int pos_mod) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;
-  const int hpt = 3 * C / 64;
-  const long long tok = vec / hpt;
-  const int vi = (int)(vec % hpt);
-  const int s = vi / (C / 64), hd = vi % (C / 64);
-  const bf16x8 x = *(const bf16x8*)(qkv + tok * 3 * C + (size_t)vi * 64 + part * 8);
-  const bf16* gsrc = (s == 0) ? dq : (s == 1) ? dk : dv;
-  const bf16x8 g = *(const bf16x8*)(gsrc + tok * C + hd * 64 + part * 8);
-  const size_t tb = (size_t)((tok / P) % pos_mod) * 64 + part * 8;
-  const float sg = (part < 4) ? 1.f : -1.f;          // adjoint of rotate_half
-  float cs[8], sn[8], sc[8];                          // (16-byte table loads, see qkv_norm_rope_kernel)
-  if (s != 2) {
-    *(float4*)&cs[0] = *(const float4*)(cos_t + tb); *(float4*)&cs[4] = *(const float4*)(cos_t + tb + 4);
-    *(float4*)&sn[0] = *(const float4*)(sin_t + tb); *(float4*)&sn[4] = *(const float4*)(sin_t + tb + 4);
-    *(float4*)&sc[0] = *(const float4*)(scale_t + tb); *(float4*)&sc[4] = *(const float4*)(scale_t + tb + 4);
-  }
-  float f[8], gg[8], ss = 0.f, dot = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    f[i] = bf2f(x[i]);
-    float gv = bf2f(g[i]);
-    if (s != 2) gv = (s == 0) ? gv * sc[i] : gv / sc[i];
-    const float gs = (s != 2) ? gv * sn[i] : 0.f;
-    const float gp = __shfl_xor(gs, 4);               // (g sin) of the partner channel
-    gg[i] = (s != 2) ? gv * cs[i] + sg * gp : gv;
-    ss += f[i] * f[i]; dot += f[i] * gg[i];
-  }
-  ss += __shfl_xor(ss, 1); ss += __shfl_xor(ss, 2); ss += __shfl_xor(ss, 4);
-  dot += __shfl_xor(dot, 1); dot += __shfl_xor(dot, 2); dot += __shfl_xor(dot, 4);
-  const float n = sqrtf(ss), sden = 1e-4f + n * 0.125f;
-  const float k1 = 1.f / sden, k2 = (n > 0.f) ? dot * 0.125f / (sden * sden * n) : 0.f;
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = f2bf(gg[i] * k1 - f[i] * k2);
-  *(bf16x8*)(dqkv + tok * 3 * C + (size_t)vi * 64 + part * 8) = o;
-}
-
-// rotary embedding over the frame index (+ optional transposed copy); one workgroup = 64 tokens x 1 head
-__global__ __launch_bounds__(256) void rope_kernel(const bf16* __restrict__ x, bf16* __restrict__ xr,
-                                                   bf16* __restrict__ xt, const float* __restrict__ cos_t,
-                                                   const float* __restrict__ sin_t, const float* __restrict__ scale_t,
-                                                   int mode, int L, int P, int C, int heads, int pos_offset,
-                                                   int pos_mod, long long x_bstride, long long xr_bstride) {
-  __shared__ float tile[64][65];
-  const int tid = threadIdx.x;
-  const int tok0 = blockIdx.x * 64, head = blockIdx.y, b = blockIdx.z;
-  const bf16* xg = x + (size_t)b * x_bstride + head * 64;
-  {
-    const int row = tid >> 2, part = tid & 3;       // 16 channels per thread
-    const int tok = tok0 + row;
-    bf16x8 v0, v1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { v0[i] = f2bf(0.f); v1[i] = f2bf(0.f); }
-    if (tok < L) {
-      v0 = *(const bf16x8*)(xg + (size_t)tok * C + part * 16);
-      v1 = *(const bf16x8*)(xg + (size_t)tok * C + part * 16 + 8);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { tile[row][part * 16 + i] = bf2f(v0[i]); tile[row][part * 16 + 8 + i] = bf2f(v1[i]); }
-  }
-  __syncthreads();
-  if (mode != 0) {
-    const int row = tid >> 2, part = tid & 3;
-    const int tok = tok0 + row;
-    float out[16];
-    if (tok < L) {
-      const int pos = pos_offset + ((tok / P) % pos_mod);
-      const float* cs = cos_t + (size_t)pos * 64;
-      const float* sn = sin_t + (size_t)pos * 64;
-      const float* sc = scale_t + (size_t)pos * 64;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int c = part * 16 + i;
-        const float a0 = tile[row][c];
-        const float a1 = tile[row][c ^ 32];
-        float sg = (c < 32) ? -1.f : 1.f;            // rotate_half: [-x2, x1]
-        if (mode >= 3) sg = -sg;                     // adjoint
-        float val = a0 * cs[c] + sg * a1 * sn[c];
-        const float scl = sc[c];
-        val = (mode == 1 || mode == 3) ? val * scl : val / scl;
-        out[i] = val;
-      }
-    }
-    __syncthreads();
-    if (tok < L) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) tile[row][part * 16 + i] = out[i];
-    }
-    __syncthreads();
-  }
-  if (xr) {
-    const int row = tid >> 2, part = tid & 3;
-    const int tok = tok0 + row;
-    if (tok < L) {
-      bf16x8 v0, v1;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { v0[i] = f2bf(tile[row][part * 16 + i]); v1[i] = f2bf(tile[row][part * 16 + 8 + i]); }
-      bf16* dst = xr + (size_t)b * xr_bstride + head * 64 + (size_t)tok * C + part * 16;
-      *(bf16x8*)dst = v0;
-      *(bf16x8*)(dst + 8) = v1;
-    }
-  }
-  if (xt) {
-    const int ch = tid >> 2, part = tid & 3;        // 16 tokens per thread
-    bf16* dst = xt + ((size_t)(b * heads + head) * 64 + ch) * L + tok0 + part * 16;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      if (tok0 + part * 16 + hh * 8 < L) {
-        bf16x8 v;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = f2bf(tile[part * 16 + hh * 8 + i][ch]);
-        *(bf16x8*)(dst + hh * 8) = v;
-      }
-    }
-  }
-}
-
-// delta[b][h][tok] = sum_c dO * O
-__global__ void attn_delta_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ out, float* __restrict__ delta,
-                                  const float* __restrict__ lse, float* __restrict__ neg, long long nvec, int L, int C,
-                                  int heads) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long vec = gid >> 3;
-  const int part = (int)(gid & 7);
-  if (vec >= nvec) return;
-  const long long tokg = vec / heads;                // b*L + tok
-  const int hd = (int)(vec % heads);
-  const bf16x8 a = *(const bf16x8*)(dout + tokg * C + hd * 64 + part * 8);
-  const bf16x8 o = *(const bf16x8*)(out + tokg * C + hd * 64 + part * 8);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += bf2f(a[i]) * bf2f(o[i]);
-  s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-  if (part == 0) {
-    const long long bb = tokg / L, tok = tokg % L;
-    const long long at = (bb * heads + hd) * L + tok;
-    delta[at] = s;
-    if (neg) {                                     // row constants of the persistent dK/dV kernel: [0] = -lse, [1] = -delta
-      neg[at] = -lse[at];
-      neg[nvec + at] = -s;
-    }
-  }
-}
+// the prologue of attention: q | k | v normalisation, rotary embedding, KV-ring placement and their adjoints
+#include "attention_qkv.h"
 
 // ================================================================================================================
 // host entry points
@@ -1410,13 +847,17 @@ extern "C" int oniris_attn_bwd_dkv(const OnirisAttnArgs* args, oniris_stream_t s
   return ONIRIS_OK;
 }
 
+// the kernels of the 8-lane layout (attention_qkv.h): 8 threads per head vector, 256 per workgroup
+static long long qkv_nvec(int64_t n_tokens, int C) { return (long long)n_tokens * 3 * C / 64; }
+static dim3 lane8_grid(long long nvec) { return dim3((unsigned)((nvec * 8 + 255) / 256)); }
+
 extern "C" int oniris_qkv_norm_rope(const void* qkv, void* q, void* k, void* v, const float* cos_t, const float* sin_t,
                                     const float* scale_t, int64_t n_tokens, int C, int P, int pos_mod, oniris_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   ONIRIS_CHECK_ARG(qkv && q && k && v && cos_t && sin_t && scale_t && n_tokens > 0 && C > 0 && C % 64 == 0 && P > 0 && pos_mod > 0,
                    "qkv_norm_rope: bad arguments");
-  const long long nvec = (long long)n_tokens * 3 * C / 64;
-  ONIRIS_KLAUNCH(qkv_norm_rope_kernel, dim3((unsigned)((nvec * 8 + 255) / 256)), dim3(256), 0, stream, (const bf16*)qkv,
+  const long long nvec = qkv_nvec(n_tokens, C);
+  ONIRIS_KLAUNCH(qkv_norm_rope_kernel, lane8_grid(nvec), dim3(256), 0, stream, (const bf16*)qkv,
                      (bf16*)q, (bf16*)k, (bf16*)v, cos_t, sin_t, scale_t, nvec, C, P, pos_mod);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
@@ -1430,8 +871,8 @@ extern "C" int oniris_qkv_norm_rope_eval(const void* qkv, void* q, void* k, void
   ONIRIS_CHECK_ARG(qkv && q && k && v && kr && cos_t && sin_t && scale_t && n_tokens > 0 && C % 64 == 0 && pos >= 0 &&
                    kv_tokens_per_batch > 0 && n_tokens % kv_tokens_per_batch == 0 && n_tokens % 8 == 0 &&
                    kv_batch_stride >= (kv_token_offset + kv_tokens_per_batch) * C, "qkv_norm_rope_eval: bad arguments");
-  const long long nvec = (long long)n_tokens * (3 * C / 64);
-  ONIRIS_KLAUNCH(qkv_norm_rope_eval_kernel, dim3((unsigned)((nvec * 8 + 255) / 256)), dim3(256), 0, stream,
+  const long long nvec = qkv_nvec(n_tokens, C);
+  ONIRIS_KLAUNCH(qkv_norm_rope_eval_kernel, lane8_grid(nvec), dim3(256), 0, stream,
                      (const bf16*)qkv, (bf16*)q, (bf16*)k, (bf16*)v, (bf16*)kr, cos_t, sin_t, scale_t, nvec, C,
                      (long long)kv_tokens_per_batch, (long long)kv_batch_stride, (long long)kv_token_offset, pos);
   ONIRIS_LAUNCH_CHECK();
@@ -1501,8 +942,8 @@ extern "C" int oniris_qkv_norm_rope_bwd(const void* qkv, const void* dq, const v
   hipStream_t stream = (hipStream_t)stream_;
   ONIRIS_CHECK_ARG(qkv && dq && dk && dv && dqkv && cos_t && sin_t && scale_t && n_tokens > 0 && C > 0 && C % 64 == 0 && P > 0 &&
                    pos_mod > 0, "qkv_norm_rope_bwd: bad arguments");
-  const long long nvec = (long long)n_tokens * 3 * C / 64;
-  ONIRIS_KLAUNCH(qkv_norm_rope_bwd_kernel, dim3((unsigned)((nvec * 8 + 255) / 256)), dim3(256), 0, stream, (const bf16*)qkv,
+  const long long nvec = qkv_nvec(n_tokens, C);
+  ONIRIS_KLAUNCH(qkv_norm_rope_bwd_kernel, lane8_grid(nvec), dim3(256), 0, stream, (const bf16*)qkv,
                      (const bf16*)dq, (const bf16*)dk, (const bf16*)dv, (bf16*)dqkv, cos_t, sin_t, scale_t, nvec, C, P, pos_mod);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
@@ -1516,9 +957,8 @@ extern "C" int oniris_qkv_norm(const void* qkv, void* q, void* k, void* v, int64
   ONIRIS_CHECK_ARG(kv_tokens_per_batch == 0 || (kv_tokens_per_batch > 0 && n_tokens % kv_tokens_per_batch == 0 &&
                    kv_token_offset >= 0 && kv_batch_stride >= (kv_token_offset + kv_tokens_per_batch) * C),
                    "qkv_norm: bad KV ring description");
-  const long long nvec = (long long)n_tokens * 3 * C / 64;
-  const long long nthr = nvec * 8;
-  ONIRIS_KLAUNCH(qkv_norm_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, (const bf16*)qkv,
+  const long long nvec = qkv_nvec(n_tokens, C);
+  ONIRIS_KLAUNCH(qkv_norm_kernel, lane8_grid(nvec), dim3(256), 0, stream, (const bf16*)qkv,
                      (bf16*)q, (bf16*)k, (bf16*)v, nvec, C, (long long)kv_tokens_per_batch, (long long)kv_batch_stride,
                      (long long)kv_token_offset);
   ONIRIS_LAUNCH_CHECK();
@@ -1529,9 +969,8 @@ extern "C" int oniris_qkv_norm_bwd(const void* qkv, const void* dq, const void* 
                                    int64_t n_tokens, int C, oniris_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   ONIRIS_CHECK_ARG(qkv && dq && dk && dv && dqkv && n_tokens > 0 && C > 0 && C % 64 == 0, "qkv_norm_bwd: bad arguments");
-  const long long nvec = (long long)n_tokens * 3 * C / 64;
-  const long long nthr = nvec * 8;
-  ONIRIS_KLAUNCH(qkv_norm_bwd_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
+  const long long nvec = qkv_nvec(n_tokens, C);
+  ONIRIS_KLAUNCH(qkv_norm_bwd_kernel, lane8_grid(nvec), dim3(256), 0, stream,
                      (const bf16*)qkv, (const bf16*)dq, (const bf16*)dk, (const bf16*)dv, (bf16*)dqkv, nvec, C);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
@@ -1563,7 +1002,7 @@ extern "C" int oniris_attn_bwd_prep(const void* dout, const void* out, float* de
   ONIRIS_CHECK_ARG(dout && out && delta && B > 0 && heads > 0 && L > 0 && C == heads * 64, "attn_bwd_prep: bad arguments");
   ONIRIS_CHECK_ARG(!neg || lse, "attn_bwd_prep: the negated row constants need lse");
   const long long nvec = (long long)B * L * heads;
-  ONIRIS_KLAUNCH(attn_delta_kernel, dim3((unsigned)((nvec * 8 + 255) / 256)), dim3(256), 0, stream,
+  ONIRIS_KLAUNCH(attn_delta_kernel, lane8_grid(nvec), dim3(256), 0, stream,
                      (const bf16*)dout, (const bf16*)out, delta, lse, neg, nvec, L, C, heads);
   ONIRIS_LAUNCH_CHECK();
   if (doutt) return oniris_rope(dout, nullptr, doutt, nullptr, nullptr, nullptr, 0, B, L, 1, C, 0, 1, 0, 0, stream_);

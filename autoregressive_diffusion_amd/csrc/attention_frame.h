@@ -521,6 +521,8 @@ __global__ __launch_bounds__(256, 2) void frame_attn_qkv_fwd_kernel(const FrameQ
 #endif
 }
 
+__device__ __forceinline__ void qkv_norm_adjoint(float ss, float dot, float& k1, float& k2);     // (attention_qkv.h)
+
 // adjoint of x -> x / (eps + |x| / 8) on this lane's half of a row held as fp32 accumulators g[dt][4 g4 + k] <-> channel
 // dt * 32 + 8 g4 + 4 h + k (qkv_norm_bwd_kernel: o = g k1 - x k2), written to `dst` (the row's 64-channel slot of dqkv); x from `src`
 __device__ __forceinline__ void frame_norm_adjoint_store(const f32x16 (&g)[2], float gscale, const bf16* src, bf16* dst, int h) {
@@ -540,8 +542,8 @@ __device__ __forceinline__ void frame_norm_adjoint_store(const f32x16 (&g)[2], f
     }
   ss += __shfl_xor(ss, 32);
   dot += __shfl_xor(dot, 32);
-  const float n = sqrtf(ss), sden = 1e-4f + n * 0.125f;
-  const float k1 = 1.f / sden, k2 = (n > 0.f) ? dot * 0.125f / (sden * sden * n) : 0.f;
+  float k1, k2;
+  qkv_norm_adjoint(ss, dot, k1, k2);
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll

@@ -2236,6 +2236,37 @@ def _decode_splits(a, B, heads, Lq, Lk, dev):
         a._keep = ws                                # (keeps the workspace alive until the launch is queued)
 
 
+def _ring_commit(ring, nk, kv_cache, update_cache):
+    """The cache after an evaluation that wrote its new frames behind the ring's committed ones: with them (nk frames) or as it was."""
+    if not update_cache:
+        return kv_cache
+    ring.n = nk
+    return ring.views()
+
+
+def _ring_decode(q, ring, nk, rows, B, heads, kv_cache, update_cache):
+    """One new frame per sequence, q (B, P, C) rotated and its k | v already behind the committed frames of the ring (rotated image
+    ready for nk keys): commit it or not, dense attention straight over the ring.  -> (out (rows, P, C) with rows [0, B) written,
+    the cache after the call)"""
+    P, C, dev = ring.P, ring.C, q.device
+    new_cache = _ring_commit(ring, nk, kv_cache, update_cache)
+    out = torch.empty((rows, P, C), dtype=BF16, device=dev)
+    a = _attn_args(q, ring.KR, ring.V, None, None, None, out[:B], None, None, B, heads, P, nk * P, C, 0, P, 0)
+    a.v_bstride = a.k_bstride = ring.cap * P * C
+    _decode_splits(a, B, heads, P, nk * P, dev)
+    check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
+    return out, new_cache
+
+
+def _infer_mask(t, Lq, Lk, P, dev):
+    """(mask_mode, block tables) of the inference mask for t new frames (attention_modules.py:69-75)"""
+    if t == 1:
+        return 0, None                                          # one new frame: dense SDPA over all keys (:69-70)
+    if Lq == Lk:
+        return 1, device_tables("infer", t, P, dev)             # causal prefill (:72-75)
+    raise NotImplementedError("The inference mask is not implemented for this case")
+
+
 FUSED_QKV_EVAL = int(_os.environ.get("ONIRIS_FUSED_QKV_EVAL", "1"))     # 0: conv + qkv_norm[_rope_eval] as separate launches (A/B aid)
 
 
@@ -2262,17 +2293,7 @@ def attention_eval_x(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P):
     q = torch.empty((N, P, C), dtype=BF16, device=dev)
     _qkv_eval(x.contiguous(), pw, q, ring.K, ring.V, ring.KR, rope_tables(rope_bufs[0], rope_bufs[1], nk, dev), N * P, C, P,
               bstride, n * P, n)
-    if update_cache:
-        ring.n = nk
-        new_cache = ring.views()
-    else:
-        new_cache = kv_cache
-    out = torch.empty((N, P, C), dtype=BF16, device=dev)
-    a = _attn_args(q, ring.KR, ring.V, None, None, None, out, None, None, B, heads, P, nk * P, C, 0, P, 0)
-    a.v_bstride = a.k_bstride = bstride
-    _decode_splits(a, B, heads, P, nk * P, dev)
-    check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
-    return out, new_cache
+    return _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
 
 
 @torch.no_grad()
@@ -2299,16 +2320,7 @@ def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P)
     xc = x.contiguous()
     check(lib.oniris_qkv_eval_pair(_p(xc), _p(pw.wf), _p(q), _p(ring.K), _p(ring.V), _p(ring.KR), _p(cs_), _p(sn_), _p(sc_), N * P,
                                    B * P, C, pw.CinP, P, bstride, n * P, n, _p(q2), _p(k2), _p(v2), _stream()), "qkv_eval_pair")
-    if update_cache:
-        ring.n = nk
-        new_cache = ring.views()
-    else:
-        new_cache = kv_cache
-    out = torch.empty((N, P, C), dtype=BF16, device=dev)
-    a = _attn_args(q, ring.KR, ring.V, None, None, None, out[:B], None, None, B, heads, P, nk * P, C, 0, P, 0)
-    a.v_bstride = a.k_bstride = bstride
-    _decode_splits(a, B, heads, P, nk * P, dev)
-    check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
+    out, new_cache = _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
     lse = torch.empty((B, heads, P), dtype=torch.float32, device=dev)
     a2 = _attn_args(q2, k2, v2, None, None, None, out[B:], lse, None, B, heads, P, P, C, 0, P, 1)
     check(lib.oniris_attn_fwd(ctypes.byref(a2), _stream()), "attn_fwd")
@@ -2364,12 +2376,7 @@ def _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
     check(lib.oniris_rope_hd(_p(K), _p(kr), _p(cs_), _p(sn_), _p(sc_), B * nk * P, heads, d, P, nk, 0, 2, nk, _stream()), "rope_hd")
     Lq, Lk = t * P, nk * P
     out = torch.empty((N, P, Cp), dtype=BF16, device=dev)
-    if t == 1:
-        mask_mode, tabs = 0, None                               # one new frame: dense SDPA over all keys (:69-70)
-    elif Lq == Lk:
-        mask_mode, tabs = 1, device_tables("infer", t, P, dev)  # causal prefill (:72-75)
-    else:
-        raise NotImplementedError("The inference mask is not implemented for this case")
+    mask_mode, tabs = _infer_mask(t, Lq, Lk, P, dev)
     a = _attn_args(q, kr, V, None, None, None, out, None, tabs, B, heads, Lq, Lk, Cp, mask_mode, P, 0)
     if t == 1:
         _decode_splits(a, B, heads, Lq, Lk, dev)
@@ -2402,23 +2409,9 @@ def attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
         cs_, sn_, sc_ = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
         check(lib.oniris_qkv_norm_rope_eval(_p(qkv), _p(q), _p(ring.K), _p(ring.V), _p(ring.KR), _p(cs_), _p(sn_), _p(sc_),
                                             N * P, C, P, bstride, n * P, n, _stream()), "qkv_norm_rope_eval")
-        if update_cache:
-            ring.n = nk
-            new_cache = ring.views()
-        else:
-            new_cache = kv_cache
-        out = torch.empty((N, P, C), dtype=BF16, device=dev)
-        a = _attn_args(q, ring.KR, ring.V, None, None, None, out, None, None, B, heads, P, nk * P, C, 0, P, 0)
-        a.v_bstride = a.k_bstride = bstride
-        _decode_splits(a, B, heads, P, nk * P, dev)
-        check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
-        return out, new_cache
+        return _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
     check(lib.oniris_qkv_norm(_p(qkv), _p(q), _p(ring.K), _p(ring.V), N * P, C, t * P, bstride, n * P, _stream()), "qkv_norm")
-    if update_cache:
-        ring.n = nk
-        new_cache = ring.views()
-    else:
-        new_cache = kv_cache
+    new_cache = _ring_commit(ring, nk, kv_cache, update_cache)
     Lq, Lk = t * P, nk * P
     tabs_r = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
     qr = torch.empty_like(q)
@@ -2426,13 +2419,7 @@ def attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
     _rope(q, qr, None, tabs_r, 1, B, t, P, C, nk - t, nk)
     _rope(ring.K, kr, None, tabs_r, 2, B, nk, P, C, 0, nk, x_bstride=bstride)
     out = torch.empty((N, P, C), dtype=BF16, device=dev)
-    if t == 1:
-        mask_mode, tabs = 0, None                               # one new frame: dense SDPA over all keys (:69-70)
-    elif Lq == Lk:
-        mask_mode = 1                                           # causal prefill (:72-75)
-        tabs = device_tables("infer", t, P, dev)
-    else:
-        raise NotImplementedError("The inference mask is not implemented for this case")
+    mask_mode, tabs = _infer_mask(t, Lq, Lk, P, dev)
     a = _attn_args(qr, kr, ring.V, None, None, None, out, None, tabs, B, heads, Lq, Lk, C, mask_mode, P, 0)
     a.v_bstride = bstride
     if t == 1:

@@ -71,14 +71,93 @@ def stats(ins):
 FLOAT_OPS = re.compile(r"^v_(pk_)?(fma|fmac|fmamk|fmaak|mac|mad|mul|add|sub|exp|log|rcp|rsq|sqrt|cvt|max|min|dot)\w*_(f32|f16|bf16)")
 
 
+PK_FLOAT = re.compile(r"^v_pk_(fma|mul|add)_f32")
+ALL_READS = re.compile(r"^(global_store|global_atomic|flat_store|buffer_store|scratch_store|ds_write|v_cmp|v_readlane|v_readfirstlane|s_|exp)")
+READS_DEST = re.compile(r"^(v_fmac|v_mac|v_pk_fmac|v_dot\w*c_|v_movrel)|d16|sdwa")
+
+
+def vregs(operand):
+    """VGPR numbers an operand names"""
+    out = []
+    for a, b, c in re.findall(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]", operand):
+        out += [int(a)] if a else list(range(int(b), int(c) + 1))
+    return out
+
+
+def operands(t):
+    rest = t.split(None, 1)[1] if " " in t else ""
+    return [o.strip() for o in re.split(r"\s+[a-z_0-9]+:", rest)[0].split(",")]
+
+
+def modifier(t, name, n):
+    m = re.search(r"\b" + name + r":\[([01,]+)\]", t)
+    return [int(x) for x in m.group(1).split(",")] if m else None
+
+
+def reads(t, r):
+    """does instruction t read VGPR r?  A source pair of a packed fp32 instruction is read per half: the low lane takes the half op_sel
+    names (default low), the high lane the half op_sel_hi names (default high)"""
+    op, ops = t.split()[0], operands(t)
+    if ALL_READS.match(op):
+        return any(r in vregs(o) for o in ops)
+    if READS_DEST.search(op) and r in vregs(ops[0]):
+        return True
+    if PK_FLOAT.match(op):
+        sel, sel_hi = modifier(t, "op_sel", 3) or [0, 0, 0], modifier(t, "op_sel_hi", 3) or [1, 1, 1]
+        for k, o in enumerate(ops[1:]):
+            v = vregs(o)
+            if len(v) == 2 and r in v:
+                if {sel[k], sel_hi[k]} & {v.index(r)}:
+                    return True
+            elif r in v:
+                return True
+        return False
+    return any(r in vregs(o) for o in ops[1:])
+
+
+def live_after(ins, i, r):
+    """is the value instruction i leaves in VGPR r read on any path before it is overwritten?  (walks the branches of the kernel's own
+    labels; a register still unread at s_endpgm is dead)"""
+    at = {t[:-1]: j for j, t in enumerate(ins) if t.endswith(":")}
+    seen, stack = set(), [i + 1]
+    while stack:
+        j = stack.pop()
+        while j < len(ins) and j not in seen:
+            seen.add(j)
+            t = ins[j]
+            if t.endswith(":"):
+                j += 1
+                continue
+            if reads(t, r):
+                return True
+            op = t.split()[0]
+            if op == "s_endpgm" or (not ALL_READS.match(op) and r in vregs(operands(t)[0])):
+                break
+            m = re.match(r"s_c?branch\S*\s+(\.LBB\d+_\d+)$", t)
+            if m and op == "s_branch":
+                j = at[m.group(1)]
+                continue
+            if m:
+                stack.append(at[m.group(1)])
+            j += 1
+    return False
+
+
 def float_ops(ins):
     """multiset of the floating-point opcodes: what decides, next to the order of the sums, whether results can differ by a bit (hipcc
-    contracts a * b + c where it finds both in one basic block, so moving code can change which products are fused)"""
+    contracts a * b + c where it finds both in one basic block, so moving code can change which products are fused).  v_fmac is v_fma
+    with the addend in the destination.  A packed instruction is two scalar ones -- or one, where the other half of its result is
+    never read (hipcc emits such a v_pk_fma_f32 for a scalar fma whose operands sit in register pairs)."""
     out = collections.Counter()
-    for t in ins:
-        if FLOAT_OPS.match(t):                    # a packed instruction is two scalar ones; encodings (_e32, _e64, _dpp) do not matter
+    for i, t in enumerate(ins):
+        if FLOAT_OPS.match(t):                    # encodings (_e32, _e64, _dpp) do not matter
             op = re.sub(r"_(e32|e64|dpp|sdwa)$", "", t.split()[0])
-            out[op.replace("v_pk_", "v_")] += 2 if op.startswith("v_pk_") else 1
+            n = 1
+            if op.startswith("v_pk_"):
+                n = 2
+                if PK_FLOAT.match(op):
+                    n = max(1, sum(live_after(ins, i, r) for r in vregs(operands(t)[0])))
+            out[op.replace("v_pk_", "v_").replace("v_fmac_", "v_fma_")] += n
     return out
 
 
