@@ -260,10 +260,12 @@ __device__ __forceinline__ void disc_bias_rows(float& bsum, const float* dyl) {
 }
 
 // The four waves' accumulators summed through hl, wave 0 first, into taps tap0 .. tap0 + TAPS - 1 of slab[taps_total][Cin][Cout];
-// the workgroup that owns the bias adds its row sums through dyl and writes them behind the weights.
+// the workgroup that owns the bias adds its row sums through dyl and writes them behind the weights, at row bias_off / Cout of a
+// bias that has several (the wide VAE's [gl][C] and [sub][C]).
 template <int TAPS>
 __device__ __forceinline__ void disc_wgrad_store(const f32x16 (&acc)[TAPS], float bsum, float* hl, float* dyl, float* slab,
-                                                 int tap0, int taps_total, bool bias_wg, int Cin, int Cout, int ci0, int co0) {
+                                                 int tap0, int taps_total, bool bias_wg, int Cin, int Cout, int ci0, int co0,
+                                                 size_t bias_off = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31;
   __syncthreads();
   for (int w = 0; w < 4; ++w) {
@@ -288,7 +290,7 @@ __device__ __forceinline__ void disc_wgrad_store(const f32x16 (&acc)[TAPS], floa
     if (threadIdx.x < 32 && co0 + threadIdx.x < Cout) {
       float s = 0.f;
       for (int q = 0; q < 8; ++q) s += dyl[q * 32 + threadIdx.x];
-      slab[(size_t)taps_total * Cin * Cout + co0 + threadIdx.x] = s;
+      slab[(size_t)taps_total * Cin * Cout + bias_off + co0 + threadIdx.x] = s;
     }
   }
 }

@@ -1,5 +1,6 @@
-// VAE decoder and encoder at block widths above 64 channels (reference: edm2/vae/vae.py EncoderDecoder, :56-204), inference
-// only, fp32 throughout, channels-last [B][T][H][W][C].  include/oniris.h: oniris_vae_wide_*.  Per wide ResBlock:
+// VAE decoder and encoder at block widths above 64 channels (reference: edm2/vae/vae.py EncoderDecoder, :56-204): inference, and
+// the training forward (the backward is csrc/vae_wide_train.hip; the launch helpers both share are at the end of
+// csrc/vae_wide_conv.h), fp32 throughout, channels-last [B][T][H][W][C].  include/oniris.h: oniris_vae_wide_*.  Per wide ResBlock:
 //   oniris_vae_wide_temb    oniris_vae_temb for ResBlocks of any width (one launch per decode of a model with a wide block)
 //   oniris_vae_wide_act     y = SiLU(RMS(x) (1 + scale) + shift) into the sequence buffer S = [g prefix frames ++ y] and the cache
 //   oniris_vae_wide_conv_a  a = bias + the group-causal (2g, 3, 3) conv of S                (vae_wide_kernel<NB, VW_CONV_A>)
@@ -76,34 +77,6 @@ __global__ __launch_bounds__(128) void vae_wide_temb_kernel(const float* __restr
   }
 }
 
-// ---- host side
-static inline bool vae_wide_c_ok(int c) { return c > 0 && c <= 65536; }
-static inline int vae_wide_nb(int CP) { return CP % 64 == 0 ? 2 : 1; }
-
-template <int NB, int MODE>
-static int vae_wide_launch(const char* what, const VaeWideParams& p, dim3 grid, hipStream_t stream) {
-  constexpr int WP = NB == 2 ? 96 : 32, TAPS = MODE == VW_CONV_A ? 9 : 1;
-  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)TAPS * DISC_KC * WP) * sizeof(float);
-  if (int rc = disc_raise_lds(vae_wide_kernel<NB, MODE>, bytes, what)) return rc;
-  ONIRIS_KLAUNCH((vae_wide_kernel<NB, MODE>), grid, dim3(256), bytes, stream, p);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
-}
-
-// planes: the output planes a workgroup column walks; p.nsub, p.Cout, p.H, p.W set
-template <int MODE>
-static int vae_wide_dispatch(const char* what, VaeWideParams& p, long long planes, hipStream_t stream) {
-  p.CinP = roundup(p.Cin, 2);
-  p.CP = roundup(p.Cout, 32);
-  p.tiles_x = cdiv(p.W, DISC_TILE); p.tiles_y = cdiv(p.H, DISC_TILE);
-  const int nb = vae_wide_nb(p.CP);
-  p.nblk = p.CP / (32 * nb);
-  const long long wgs = planes * p.tiles_x * p.tiles_y;
-  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && (long long)p.nsub * p.nblk <= 65535, "%s: %lld tiles", what, wgs);
-  const dim3 grid((unsigned)wgs, p.nsub * p.nblk);
-  return nb == 2 ? vae_wide_launch<2, MODE>(what, p, grid, stream) : vae_wide_launch<1, MODE>(what, p, grid, stream);
-}
-
 extern "C" int oniris_vae_wide_temb(const float* params, const int32_t* table, int n_res_blocks, int max_c2, const float* t, int B,
                                     float* emb, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(params && table && t && emb, "vae_wide_temb: null pointer");
@@ -142,30 +115,12 @@ extern "C" int oniris_vae_wide_conv_a(const float* S, const float* w, const floa
   return vae_wide_dispatch<VW_CONV_A>("vae_wide_conv_a", p, (long long)B * (T / g), (hipStream_t)stream);
 }
 
-template <int NB>
-static int vae_wide_conv_b_launch(const DiscConvParams& p, dim3 grid, hipStream_t stream) {
-  constexpr int WP = NB == 2 ? 96 : 32;
-  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)p.taps * DISC_KC * WP) * sizeof(float);
-  if (int rc = disc_raise_lds(disc_conv_kernel<NB>, bytes, "vae_wide_conv_b")) return rc;
-  ONIRIS_KLAUNCH(disc_conv_kernel<NB>, grid, dim3(256), bytes, stream, p);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
-}
-
 extern "C" int oniris_vae_wide_conv_b(const float* u, const float* res, const float* w, const float* bias, float* out, int B, int T,
                                       int H, int W, int C, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(u && res && w && bias && out && (const float*)out != u, "vae_wide_conv_b: null pointer or out aliases u");
   ONIRIS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0 && vae_wide_c_ok(C), "vae_wide_conv_b: bad sizes (B %d T %d H %d W %d C %d)", B, T,
                    H, W, C);
-  DiscConvParams p;
-  p.x = u; p.w = w; p.bias = bias; p.pro_s = nullptr; p.pro_t = nullptr; p.res = res; p.out = out; p.part = nullptr;
-  p.N = B * T; p.H = H; p.W = W; p.Cin = C; p.CinP = roundup(C, 2); p.Cout = C; p.CoutP = roundup(C, 32); p.taps = 9;
-  p.tiles_x = cdiv(W, DISC_TILE); p.tiles_y = cdiv(H, DISC_TILE); p.res_scale = 1.f;
-  const long long wgs = (long long)B * T * p.tiles_x * p.tiles_y;
-  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL, "vae_wide_conv_b: %lld tiles", wgs);
-  const int nb = vae_wide_nb(p.CoutP);
-  const dim3 grid((unsigned)wgs, p.CoutP / (32 * nb));
-  return nb == 2 ? vae_wide_conv_b_launch<2>(p, grid, (hipStream_t)stream) : vae_wide_conv_b_launch<1>(p, grid, (hipStream_t)stream);
+  return vae_wide_conv3_run("vae_wide_conv_b", u, res, w, bias, out, (long long)B * T, H, W, C, (hipStream_t)stream);
 }
 
 extern "C" int oniris_vae_wide_up(const float* x, const float* w, const float* bias, float* out, int B, int T, int H, int W, int C,
@@ -194,22 +149,6 @@ extern "C" int oniris_vae_wide_out(const float* x, const float* w, const float* 
   return vae_wide_dispatch<VW_OUT>("vae_wide_out", p, (long long)B * T, (hipStream_t)stream);
 }
 
-template <int NB, typename TIN, bool VEC>
-static int vae_wide_down_launch(const VaeWideDownParams& p, dim3 grid, hipStream_t stream) {
-  constexpr int WP = NB == 2 ? 96 : 32;
-  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)DISC_KC * WP) * sizeof(float);
-  if (int rc = disc_raise_lds(vae_wide_down_kernel<NB, TIN, VEC>, bytes, "vae_wide_down")) return rc;
-  ONIRIS_KLAUNCH((vae_wide_down_kernel<NB, TIN, VEC>), grid, dim3(256), bytes, stream, p);
-  ONIRIS_LAUNCH_CHECK();
-  return ONIRIS_OK;
-}
-
-template <int NB>
-static int vae_wide_down_pick(const VaeWideDownParams& p, int x_is_u8, bool vec, dim3 grid, hipStream_t stream) {
-  if (x_is_u8) return vae_wide_down_launch<NB, unsigned char, false>(p, grid, stream);
-  return vec ? vae_wide_down_launch<NB, float, true>(p, grid, stream) : vae_wide_down_launch<NB, float, false>(p, grid, stream);
-}
-
 extern "C" int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B,
                                     int To, int Ho, int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w,
                                     const float* bias, int Cout, float* out, oniris_stream_t stream) {
@@ -221,16 +160,5 @@ extern "C" int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int6
   p.x = x; p.w = w; p.bias = bias; p.out = out;
   p.sb = sb; p.st = st; p.sh = sh; p.sw = sw; p.sc = sc;
   p.B = B; p.To = To; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.Cout = Cout; p.tc = tcomp; p.scm = scomp; p.normalize = normalize;
-  p.CinP = roundup(Cin, 2);
-  p.CP = roundup(Cout, 32);
-  p.tiles_x = cdiv(Wo, DISC_TILE); p.tiles_y = cdiv(Ho, DISC_TILE);
-  const int nb = vae_wide_nb(p.CP);
-  p.nblk = p.CP / (32 * nb);
-  const long long wgs = (long long)B * To * p.tiles_x * p.tiles_y;
-  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && p.nblk <= 65535, "vae_wide_down: %lld tiles", wgs);
-  const bool vec = !x_is_u8 && !normalize && sc == 1 && Cin % 32 == 0 && sb % 4 == 0 && st % 4 == 0 && sh % 4 == 0 && sw % 4 == 0 &&
-                   ((uintptr_t)x & 15) == 0;
-  const dim3 grid((unsigned)wgs, p.nblk);
-  return nb == 2 ? vae_wide_down_pick<2>(p, x_is_u8, vec, grid, (hipStream_t)stream)
-                 : vae_wide_down_pick<1>(p, x_is_u8, vec, grid, (hipStream_t)stream);
+  return vae_wide_down_run<true>("vae_wide_down", p, x_is_u8, (hipStream_t)stream);
 }

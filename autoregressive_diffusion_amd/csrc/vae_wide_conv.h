@@ -20,7 +20,7 @@
 // Every output is summed in the order time tap, channel chunk, spatial tap, channel pair, then the bias (and the residual); it
 // depends on neither T, nor B, nor where a sequence was cut: a decode in chunks through the cache is bit-identical to the whole.
 #pragma once
-#include "disc_parts.h"
+#include "disc_conv3.h"
 
 enum { VW_CONV_A = 0, VW_UP = 1, VW_OUT = 2 };
 
@@ -161,8 +161,8 @@ __device__ __forceinline__ float vae_wide_load_in(const TIN* p, int normalize) {
 
 // Channels c0 .. c0 + kc - 1 of the tile's 256 input pixels at one sub-position (xs: the sample's plane t tc + tq moved by hq rows
 // and wq columns; ysh / xsw: the strides of one OUTPUT row / column) into the interior of hl; channels >= Cin and pixels outside
-// the output plane are 0.
-template <typename TIN>
+// the output plane are 0.  PITCH: the stage's pixel pitch (the weight gradient of csrc/vae_wide_train.hip stages 32 channels at 33).
+template <typename TIN, int PITCH = DISC_APITCH>
 __device__ __forceinline__ void vae_wide_stage_down(float* hl, const TIN* xs, long long ysh, long long xsw, long long sc, int normalize,
                                                     int y0, int x0, int Ho, int Wo, int Cin, int c0, int kc) {
   for (int idx = threadIdx.x; idx < DISC_TILE * DISC_TILE * kc; idx += 256) {
@@ -170,7 +170,7 @@ __device__ __forceinline__ void vae_wide_stage_down(float* hl, const TIN* xs, lo
     const int y = y0 + py, xx = x0 + px;
     float v = 0.f;
     if (y < Ho && xx < Wo && c0 + c < Cin) v = vae_wide_load_in(xs + y * ysh + xx * xsw + (c0 + c) * sc, normalize);
-    hl[((py + 1) * DISC_HALO + px + 1) * DISC_APITCH + c] = v;
+    hl[((py + 1) * DISC_HALO + px + 1) * PITCH + c] = v;
   }
 }
 
@@ -235,7 +235,8 @@ __device__ __forceinline__ float vae_wide_area(const TIN* xp, int s0, int s1, co
   return area;
 }
 
-template <int NB, typename TIN, bool VEC>
+// RES = false: out = conv + bias alone, the adjoint of `up` (csrc/vae_wide_train.hip: the sub-positions of d up gathered through W^T).
+template <int NB, typename TIN, bool VEC, bool RES = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void vae_wide_down_kernel(VaeWideDownParams p) {
   extern __shared__ __attribute__((aligned(16))) float disc_lds[];
   float* hl = disc_lds;                                          // [324][17], the interior only
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
         const int i = mfma_row(r, lane);
         const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
         float area = 0.f;
-        if (y < p.Ho && xx < p.Wo) area = vae_wide_area<TIN, VEC>(xn + y * ysh + xx * xsw, s0, s1, p);
+        if (RES && y < p.Ho && xx < p.Wo) area = vae_wide_area<TIN, VEC>(xn + y * ysh + xx * xsw, s0, s1, p);
         al[r * 256 + threadIdx.x] = area;
       }
 #pragma unroll
@@ -292,8 +293,96 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
         const int i = mfma_row(r, lane);
         const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
         if (y >= p.Ho || xx >= p.Wo) continue;
-        p.out[(((size_t)pl * p.Ho + y) * p.Wo + xx) * p.Cout + co] = (acc[mb][nb][r] + bv) + al[r * 256 + threadIdx.x] / len;
+        const float v = acc[mb][nb][r] + bv;
+        p.out[(((size_t)pl * p.Ho + y) * p.Wo + xx) * p.Cout + co] = RES ? v + al[r * 256 + threadIdx.x] / len : v;
       }
     }
   }
+}
+
+// ---- host side (csrc/vae_wide.hip, csrc/vae_wide_train.hip)
+static inline bool vae_wide_c_ok(int c) { return c > 0 && c <= 65536; }
+static inline int vae_wide_nb(int CP) { return CP % 64 == 0 ? 2 : 1; }
+
+template <int NB, int MODE>
+static int vae_wide_launch(const char* what, const VaeWideParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32, TAPS = MODE == VW_CONV_A ? 9 : 1;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)TAPS * DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(vae_wide_kernel<NB, MODE>, bytes, what)) return rc;
+  ONIRIS_KLAUNCH((vae_wide_kernel<NB, MODE>), grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+// planes: the output planes a workgroup column walks; p.nsub, p.Cin, p.Cout, p.H, p.W set
+template <int MODE>
+static int vae_wide_dispatch(const char* what, VaeWideParams& p, long long planes, hipStream_t stream) {
+  p.CinP = roundup(p.Cin, 2);
+  p.CP = roundup(p.Cout, 32);
+  p.tiles_x = cdiv(p.W, DISC_TILE); p.tiles_y = cdiv(p.H, DISC_TILE);
+  const int nb = vae_wide_nb(p.CP);
+  p.nblk = p.CP / (32 * nb);
+  const long long wgs = planes * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && (long long)p.nsub * p.nblk <= 65535, "%s: %lld tiles", what, wgs);
+  const dim3 grid((unsigned)wgs, p.nsub * p.nblk);
+  return nb == 2 ? vae_wide_launch<2, MODE>(what, p, grid, stream) : vae_wide_launch<1, MODE>(what, p, grid, stream);
+}
+
+template <int NB, typename TIN, bool VEC, bool RES>
+static int vae_wide_down_launch(const char* what, const VaeWideDownParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(vae_wide_down_kernel<NB, TIN, VEC, RES>, bytes, what)) return rc;
+  ONIRIS_KLAUNCH((vae_wide_down_kernel<NB, TIN, VEC, RES>), grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+template <int NB, bool RES>
+static int vae_wide_down_pick(const char* what, const VaeWideDownParams& p, int x_is_u8, bool vec, dim3 grid, hipStream_t stream) {
+  if (RES && x_is_u8) return vae_wide_down_launch<NB, unsigned char, false, RES>(what, p, grid, stream);
+  return vec ? vae_wide_down_launch<NB, float, true, RES>(what, p, grid, stream)
+             : vae_wide_down_launch<NB, float, false, RES>(what, p, grid, stream);
+}
+
+// p: the operands, strides and sizes set; RES = false takes fp32 only
+template <bool RES>
+static int vae_wide_down_run(const char* what, VaeWideDownParams& p, int x_is_u8, hipStream_t stream) {
+  p.CinP = roundup(p.Cin, 2);
+  p.CP = roundup(p.Cout, 32);
+  p.tiles_x = cdiv(p.Wo, DISC_TILE); p.tiles_y = cdiv(p.Ho, DISC_TILE);
+  const int nb = vae_wide_nb(p.CP);
+  p.nblk = p.CP / (32 * nb);
+  const long long wgs = (long long)p.B * p.To * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && p.nblk <= 65535, "%s: %lld tiles", what, wgs);
+  const bool vec = !x_is_u8 && !p.normalize && p.sc == 1 && p.Cin % 32 == 0 && p.sb % 4 == 0 && p.st % 4 == 0 && p.sh % 4 == 0 &&
+                   p.sw % 4 == 0 && ((uintptr_t)p.x & 15) == 0;
+  const dim3 grid((unsigned)wgs, p.nblk);
+  return nb == 2 ? vae_wide_down_pick<2, RES>(what, p, x_is_u8, vec, grid, stream)
+                 : vae_wide_down_pick<1, RES>(what, p, x_is_u8, vec, grid, stream);
+}
+
+// The 3x3 conv of disc_conv_kernel at a wide VAE width over `planes` planes: out = (res +) (bias +) conv3x3(x), res and bias or NULL;
+// w packed [9][CinP][CP].  Conv B of a ResBlock, and its data gradient on flipped, transposed weights.
+template <int NB>
+static int vae_wide_conv3_launch(const char* what, const DiscConvParams& p, dim3 grid, hipStream_t stream) {
+  constexpr int WP = NB == 2 ? 96 : 32;
+  const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)p.taps * DISC_KC * WP) * sizeof(float);
+  if (int rc = disc_raise_lds(disc_conv_kernel<NB>, bytes, what)) return rc;
+  ONIRIS_KLAUNCH(disc_conv_kernel<NB>, grid, dim3(256), bytes, stream, p);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+static int vae_wide_conv3_run(const char* what, const float* x, const float* res, const float* w, const float* bias, float* out,
+                              long long planes, int H, int W, int C, hipStream_t stream) {
+  DiscConvParams p;
+  p.x = x; p.w = w; p.bias = bias; p.pro_s = nullptr; p.pro_t = nullptr; p.res = res; p.out = out; p.part = nullptr;
+  p.N = (int)planes; p.H = H; p.W = W; p.Cin = C; p.CinP = roundup(C, 2); p.Cout = C; p.CoutP = roundup(C, 32); p.taps = 9;
+  p.tiles_x = cdiv(W, DISC_TILE); p.tiles_y = cdiv(H, DISC_TILE); p.res_scale = 1.f;
+  const long long wgs = planes * p.tiles_x * p.tiles_y;
+  ONIRIS_CHECK_ARG(planes <= 0x7fffffffLL && wgs <= 0x7fffffffLL, "%s: %lld tiles", what, wgs);
+  const int nb = vae_wide_nb(p.CoutP);
+  const dim3 grid((unsigned)wgs, p.CoutP / (32 * nb));
+  return nb == 2 ? vae_wide_conv3_launch<2>(what, p, grid, stream) : vae_wide_conv3_launch<1>(what, p, grid, stream);
 }

@@ -13,8 +13,9 @@ ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` lau
 Blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip, on
 both sides: the `up`, `out` and `down` stages as GEMMs and four launches per ResBlock (activation, conv A, activation, conv B; the
 encoder passes a null FiLM pointer), with the same cache entries.  An encoder `down` also takes the GEMM when it compresses more
-than 512 channels, whatever its output width.  A model that has such a block runs for inference only: the training path of
-`forward` raises NotImplementedError (include/oniris.h: oniris_vae_wide_*).
+than 512 channels, whatever its output width.  A model that has such a block runs for inference only by default: the training
+path of `forward` raises NotImplementedError until `VAE.wide_training()` switches it on for that model (include/oniris.h:
+oniris_vae_wide_*, oniris_vae_wide_*_bwd).
 
 `forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
 enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
@@ -342,8 +343,8 @@ class VAE(BetterModule):
     channels, time and spatial compressions in {1, 2}, any n_res_blocks, any latent height / width; anything else raises
     NotImplementedError here.  Blocks of up to 64 channels run on the register-tile kernels (csrc/vae.hip, csrc/vae_encoder.hip),
     wider ones on the fp32 MFMA tile kernels (csrc/vae_wide.hip), encoder and decoder alike; a model may mix them.  A model
-    with a width above 64 runs for inference only: the training path of `forward` raises NotImplementedError (training at
-    those widths, and 512 channels, the full-size Counter-Strike VAE, are out of scope)."""
+    with a width above 64 runs for inference only unless `wide_training()` was called on it: until then the training path of
+    `forward` raises NotImplementedError (512 channels, the full-size Counter-Strike VAE, are out of scope)."""
 
     def __init__(self, channels, n_res_blocks, time_compressions=[1, 2, 2], spatial_compressions=[1, 2, 2], mean=None, std=None):
         super().__init__()
@@ -360,6 +361,7 @@ class VAE(BetterModule):
                                       f"on the narrow kernels, which take 1..{MAX_NARROW} channels")
         self.latent_channels = channels[-1]
         self._wide = max(widths) if max(widths) > MAX_NARROW else 0
+        self._wide_training = False
         self.encoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="encoder")
         self.decoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="decoder")
         self.time_compression = np.prod(time_compressions)
@@ -370,6 +372,15 @@ class VAE(BetterModule):
         frame = inspect.currentframe()
         args, _, _, values = inspect.getargvalues(frame)
         self.kwargs = {arg: values[arg] for arg in args if arg != "self"}
+
+    def wide_training(self, enabled=True):
+        """Switch the training path of `forward` on (or off again) for a model with a block wider than MAX_NARROW: the backward on
+        the fp32 MFMA kernels of csrc/vae_wide_train.hip (vae_train.py).  Off by default, so that a wide model refuses to train as
+        it always has until asked: `VAE.from_pretrained(path).to("cuda").wide_training()`.  A plain attribute: copy.deepcopy keeps
+        it, state_dict and kwargs do not hold it.  A model without a wide block trains either way, on the same kernels.  Returns
+        self."""
+        self._wide_training = bool(enabled)
+        return self
 
     # ---- encode + mix + decode (vae.py:228-237)
     def forward(self, x, t=0.1, cache=None, *, t_sample=None, noise=None):
@@ -386,14 +397,16 @@ class VAE(BetterModule):
 
         In eval mode or under torch.no_grad() it is encode -> mix -> decode on the inference kernels: real caches are carried
         under cache["encoder"] / cache["decoder"] and the outputs have no grad_fn.  A model with a block wider than MAX_NARROW has
-        this path only: its training path raises NotImplementedError that names the width."""
+        this path only, and its training path raises NotImplementedError that names the width, until `wide_training()` switches
+        its training path on: then everything said above holds for it too (csrc/vae_wide_train.hip)."""
         self._check_frames("forward", x.shape, "x (B, {c}, T, H, W)", *(x.shape if x.dim() == 5 else (None,) * 5))
         if self._wide:                                       # said before anything else is looked at, wherever the model lives
             self._encoder_device("forward", x)
-            if self.training and torch.is_grad_enabled():
+            if self.training and torch.is_grad_enabled() and not self.__dict__.get("_wide_training", False):
                 raise NotImplementedError(f"VAE.forward: this model has a block of {self._wide} channels: above {MAX_NARROW} the "
                                           f"encoder and decoder run for inference only (eval mode or torch.no_grad()); for "
-                                          f"training at that width use {_REF}")
+                                          f"training at that width use {_REF}.  VAE.wide_training() switches the fp32 MFMA "
+                                          f"training kernels on for this model")
         B = x.shape[0]
         if t_sample is not None and (t_sample.dim() != 1 or t_sample.shape[0] != B):
             raise ValueError(f"VAE.forward: t_sample must be ({B},), got {tuple(t_sample.shape)}")

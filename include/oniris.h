@@ -709,6 +709,45 @@ int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int
                          int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w, const float* bias, int Cout,
                          float* out, oniris_stream_t stream);
 
+/* Backward of the wide VAE stages, added within ABI 14 (nothing above changed).  csrc/vae_wide_train.hip, csrc/vae_wide_train.h.
+ * The training forward of a wide ResBlock is oniris_vae_wide_act (cache_in NULL: the prefix is the first g activated frames) /
+ * _conv_a / _act / _conv_b above; the backward stores x and a and forms S and u again with oniris_vae_wide_act.
+ * oniris_vae_wide_conv_b_bwd: du = conv3x3(dout) on w packed [9][CinP][CP] = [ky][kx][co][ci] <- conv3d1.weight[co][ci][2 - ky][2 - kx].
+ * oniris_vae_wide_act_bwd: the adjoint of y = SiLU(RMS(x) (1 + scale) + shift) (emb NULL: y = SiLU(RMS(x))), one wave per pixel, the
+ *   channel sums in the order of oniris_vae_wide_act: dz = dy SiLU'(z), dn = dz (1 + scale), dx = (dn - n mean_c(dn n)) / d + add
+ *   (add or NULL), n = x / d.  x, dy, add [B][T][H][W][C]; dx [B][out_T][H][W][C], out_T >= T (frames T.. are left alone: the zero
+ *   frames behind da).  part (or NULL; needs emb) [ceil(T H W / 256)][B][2C] = per workgroup sum dz n | sum dz over its 256 pixels
+ *   of one sample; their sum over the first axis (oniris_vae_slab_sum_bwd) is d emb.  C <= 256.
+ * The data gradient of conv A is oniris_vae_wide_conv_a itself on D = [da (T frames) ++ g zero frames] with a zero bias and w packed
+ *   [j 9 + ky 3 + kx][c][r CP + ci] <- conv3d0.weight[c g + gl][ci][kt][2 - ky][2 - kx], (gl, kt) = (j, g + r) for j < g, (j - g, r)
+ *   for j >= g: output frame tau g + r is d y of that frame.
+ * oniris_vae_wide_conv3_wgrad_bwd: causal = 1 (conv A): xin = S [B][x_T = g + T] frames, dA = D [B][dA_T] frames; slab element
+ *   [kt][gl][ky][kx][ci][c] = d conv3d0.weight[c g + gl][ci][kt][ky][kx], then [gl][c] = d bias[c g + gl].  causal = 0 (conv B, g = 1):
+ *   xin = u, dA = dout, slab [ky][kx][ci][c] then [c].  slab [nslab][2g g 9 C C + g C] ([9 C C + C]): workgroup s adds the work items
+ *   (b, time group, 16x16 tile) s, s + nslab, ... in that order and writes all of slab s; oniris_vae_slab_sum_bwd sums the slabs.
+ * oniris_vae_wide_down_bwd: dx [B][T tc][H sc][W sc][Cx] at sub-position sub = (tq sc + hq) sc + wq = sum_n dy[.][n] w[n][sub CP + c]
+ *   + zero_bias: the adjoint of `down` (w: the conv weight plus the area matrix, transposed, packed as for oniris_vae_wide_up with
+ *   Cin = Cy) and, at tc = sc = 1, of `out`.  zero_bias [tc sc^2][CP] zeros.
+ * oniris_vae_wide_up_bwd: dx [B][T][H][W][C] = sum_{sub, co} dup[sub-position sub][co] w[sub][co][c] + zero_bias: the adjoint of `up`
+ *   (w: the conv weight transposed, packed as for oniris_vae_wide_down, no residual); dup contiguous [B][T tc][H sc][W sc][C].
+ * oniris_vae_wide_lin_wgrad_bwd: the weight and bias gradient of a 1x1 stage over the views of oniris_vae_lin_dw_bwd, x through
+ *   element strides (b, t, h, w, c) of the fine tensor, dy contiguous: slab [nslab][px][py][Cx][Cy] then [py][Cy], px / py the
+ *   sub-positions of the x / dy view; [px][py][k][n] = sum_row x_view[row][px Cx + k] dy_view[row][py Cy + n]; work items (b, t,
+ *   16x16 tile of the coarse grid) as above.
+ * Every sum has a fixed order, nothing is accumulated with atomics, and no activation gradient of a sample depends on B.       */
+int oniris_vae_wide_act_bwd(const float* x, const float* emb, const float* dy, const float* add, float* dx, float* part, int B, int T,
+                            int H, int W, int C, int out_T, oniris_stream_t stream);
+int oniris_vae_wide_conv_b_bwd(const float* dout, const float* w, float* du, int B, int T, int H, int W, int C, oniris_stream_t stream);
+int oniris_vae_wide_conv3_wgrad_bwd(const float* xin, int x_T, const float* dA, int dA_T, int B, int T, int H, int W, int C, int g,
+                                    int causal, float* slab, int nslab, oniris_stream_t stream);
+int oniris_vae_wide_down_bwd(const float* dy, const float* w, const float* zero_bias, float* dx, int B, int T, int H, int W, int Cy,
+                             int Cx, int tcomp, int scomp, oniris_stream_t stream);
+int oniris_vae_wide_up_bwd(const float* dup, const float* w, const float* zero_bias, float* dx, int B, int T, int H, int W, int C,
+                           int tcomp, int scomp, oniris_stream_t stream);
+int oniris_vae_wide_lin_wgrad_bwd(const float* x, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int Cx, int tcx, int scx,
+                                  const float* dy, int Cy, int tcy, int scy, int B, int T, int H, int W, float* slab, int nslab,
+                                  oniris_stream_t stream);
+
 /* VAE encoder (reference: EncoderDecoder(type='encoder') vae.py:96-204, VAE.encode :239-241), inference, fp32 throughout.
  * csrc/vae_encoder.hip.  Its ResBlocks are oniris_vae_res_a / oniris_vae_res_b with a zero emb buffer (the encoder passes
  * t = None, vae.py:78-82; v (1 + 0) + 0 is exact) and the group sizes cumprod(time_compressions) reversed (vae.py:180-181).
