@@ -457,8 +457,74 @@ __global__ __launch_bounds__(256) void gconv_bwd_prep_kernel(const bf16* __restr
 //   mode 1 (EPI_EMB_SILU): g = d u, u = silu(y*c)/0.596  ->  dout = g*silu'(y*c)/0.596*c ; dc[n][co] += sum_pixels(...)*y
 //   mode 2 (EPI_MPSUM):    g = d out, out = clip(ta*res + tb*v) -> dres = ta*g*mask ; dout = tb*g*mask
 // then S1/S2/dy3 exactly as gconv_bwd_prep_kernel.  raw = y (mode 1) or v (mode 2).
-template <int MODE, bool NT>
-__global__ __launch_bounds__(1024) void gconv_bwd_fused_kernel(const bf16* g, const bf16* __restrict__ raw,
+//
+// The pixel loop is a software pipeline.  The grid is fixed (at most two slices per frame, so that the slices' float atomics
+// commute): 1024 blocks of 256 threads at the gym shape, every lane walking its pixel steps p, p + npl, ... < p1.  Written as
+// "load, compute, store" per step, hipcc keeps that order -- g and dout may alias -- and since loads and stores retire through
+// one in-order counter (s_waitcnt vmcnt) every step was two dependent memory round trips behind the previous step's stores
+// (4.1 TB/s at 64x64, mode 1; the 128-VGPR cap of __launch_bounds__(1024) also spilled 11 registers into that loop).
+// Now the loads of step k + GCONV_FUSED_AHEAD -- y3, then g and raw (and xo when masked) of both slots -- are requested before
+// step k is computed and stored, so the wait for step k's data leaves the younger loads and the older stores in flight.  The
+// steps, and the slots within a step, are worked in exactly the order of the plain loop and each by the same lane: every sum
+// keeps its order of additions.
+//   load(slot, p)   issues every global load of pixel step p into `slot` (nothing else)
+//   work(slot, p)   the arithmetic and the stores of step p
+// The ring of AHEAD + 1 slots is indexed with compile-time constants only (the main loop is unrolled AHEAD + 1 times), so it
+// lives in registers and no slot is ever copied: a register copy would wait for the load behind it.  No address past p1 is
+// ever formed: the main loop runs whole rounds while all they request is in range, the steps after it check each request.
+// AHEAD = 1 and 2 measured the same within 2 %, 3 up to 8 % slower at 16x16 and 8x8 (profiles/prepass_pipeline_ab.txt): 1 it is.
+#ifndef GCONV_FUSED_AHEAD
+#define GCONV_FUSED_AHEAD 1
+#endif
+// Registers: the budget is 3 waves per SIMD (168 VGPRs; 156 / 164 used, no scratch), i.e. 3 blocks of 256 threads per CU instead
+// of the 4 that 128 VGPRs would allow.  Under a 128-VGPR cap hipcc spills 22 (mode 1) / 41 (mode 2) registers into the loop even
+// at AHEAD = 1, and that form measured 9 % slower at 64x64 and slower than the plain loop from 16x16 down; with 768 of the 1024
+// blocks resident each CU still has 12 waves x 64 lanes x 2 steps x 80 B = 120 KB requested (profiles/prepass_pipeline_ab.txt).
+#ifndef GCONV_FUSED_MIN_WAVES
+#define GCONV_FUSED_MIN_WAVES 3
+#endif
+template <int AHEAD, typename Slot, typename Load, typename Work>
+__device__ __forceinline__ void gconv_bwd_pipeline(int p, const int p1, const int step, Load load, Work work) {
+  Slot ring[AHEAD + 1];                              // slot j % (AHEAD + 1) holds the j-th step from the start of a round
+#pragma unroll
+  for (int j = 0; j < AHEAD; ++j)
+    if (p + j * step < p1) load(ring[j], p + j * step);
+  // full rounds of AHEAD + 1 steps: every step requested by a round is in range, so nothing in this loop is predicated
+  while (p + 2 * AHEAD * step < p1) {
+#pragma unroll
+    for (int j = 0; j <= AHEAD; ++j) {
+      load(ring[(j + AHEAD) % (AHEAD + 1)], p + AHEAD * step);
+      __builtin_amdgcn_sched_barrier(0);             // (the requests stay ahead of the step, and the next step's behind it:
+      work(ring[j], p);                              //  left alone the scheduler moves later steps' loads up, for registers)
+      __builtin_amdgcn_sched_barrier(0);
+      p += step;
+    }
+  }
+  // the last <= 2 AHEAD steps, the ring in the phase a round starts with; the last AHEAD of them load nothing
+#pragma unroll
+  for (int j = 0; j < 2 * AHEAD; ++j) {
+    if (p < p1) {
+      if (p + AHEAD * step < p1) load(ring[(j + AHEAD) % (AHEAD + 1)], p + AHEAD * step);
+      work(ring[j % (AHEAD + 1)], p);
+    }
+    p += step;
+  }
+}
+// 16 bytes at (base: uniform over the block) + (byte offset: 32 bits).  The base stays in scalar registers, so one vector register
+// addresses every stream of a step; as 64-bit pointers the eight streams held 16 VGPRs.
+template <bool NT>
+__device__ __forceinline__ bf16x8 ldv_at(const bf16* base, uint32_t byte_off) {
+  return ldv<NT>((const bf16x8*)((const char*)base + byte_off));
+}
+template <bool NT>
+__device__ __forceinline__ void stv_at(bf16* base, uint32_t byte_off, bf16x8 v) {
+  stv<NT>((bf16x8*)((char*)base + byte_off), v);
+}
+// NTH_MAX: the block size the kernel is compiled for (256, or 1024 behind ONIRIS_GCONV_BWD_THREADS: 128 VGPRs at most then).
+template <bool MASKED> struct GconvBwdStep { bf16x8 y3, g[2], r[2]; };
+template <> struct GconvBwdStep<true> { bf16x8 y3, g[2], r[2], x[2]; };          // (mode 2 after a forward that clipped: xo as well)
+template <int MODE, bool NT, int NTH_MAX>
+__global__ __launch_bounds__(NTH_MAX, GCONV_FUSED_MIN_WAVES) void gconv_bwd_fused_kernel(const bf16* g, const bf16* __restrict__ raw,
                                                               const bf16* __restrict__ y3, const float* __restrict__ ca,
                                                               const float* __restrict__ cb, const float* __restrict__ cs,
                                                               const bf16* __restrict__ xo, bf16* dout,
@@ -468,18 +534,27 @@ __global__ __launch_bounds__(1024) void gconv_bwd_fused_kernel(const bf16* g, co
                                                               float tb, float clip, int pix_per_block, int cs_pitch,
                                                               const int* __restrict__ clip_flag, float* __restrict__ ca_scaled) {
   // mode 2, aliasing protocol (include/oniris.h): dgrad / wgrad read g itself with tb folded into the own-frame coefficient;
-  // only a forward that really clipped something makes this pass read xo and write the masked gradient (in place)
+  // only a forward that really clipped something makes this pass read xo and write the masked gradient (in place).
+  // In place (dout == g) a lane rewrites only the 16 bytes it has itself read for that pixel step, and the loads of a step are
+  // complete before its arithmetic; the loads requested ahead belong to later steps of the same lane, i.e. to other addresses,
+  // which no lane has written yet -- so issuing loads ahead of the stores reads what the plain loop read.
   const bool alias = MODE == 2 && ca_scaled != nullptr;
   const bool masked = MODE == 2 && clip > 0.f && (!alias || *clip_flag != 0);
   __shared__ float red[16];
   __shared__ float accs[2][512];
+  __shared__ __attribute__((aligned(16))) float cvs[2][512];       // mode 1: the emb scales c[n][co] of both slots
   const int bt = blockIdx.x, b = bt / T, t = bt % T;
   const size_t PC = (size_t)P * C;
   const int G8 = C >> 3;
-  const int NTH = blockDim.x;                      // 256 or 1024 threads (the host picks: see oniris_gconv_bwd_fused)
+  const int NTH = blockDim.x;                      // <= NTH_MAX threads (the host picks: see oniris_gconv_bwd_fused)
   const int cg = threadIdx.x % G8, pl = threadIdx.x / G8, npl = NTH / G8;
-  if (MODE == 1)
+  size_t nn[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) nn[s] = (size_t)(b * 2 + s) * T + t;
+  if (MODE == 1) {
     for (int i = threadIdx.x; i < 2 * 512; i += NTH) (&accs[0][0])[i] = 0.f;
+    for (int i = threadIdx.x; i < C; i += NTH) { cvs[0][i] = cs[nn[0] * cs_pitch + i]; cvs[1][i] = cs[nn[1] * cs_pitch + i]; }
+  }
   __syncthreads();
   float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
   float part[2][8];
@@ -487,65 +562,83 @@ __global__ __launch_bounds__(1024) void gconv_bwd_fused_kernel(const bf16* g, co
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int i = 0; i < 8; ++i) part[s][i] = 0.f;
-  size_t nn[2];
-  float cbv[2], cv[2][8];
+  float cbv[2];
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    nn[s] = (size_t)(b * 2 + s) * T + t;
-    cbv[s] = cb[nn[s]];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cv[s][i] = 1.f;
-    if (MODE == 1 && pl < npl) {
-      const float4 c0 = *(const float4*)(cs + nn[s] * cs_pitch + cg * 8), c1 = *(const float4*)(cs + nn[s] * cs_pitch + cg * 8 + 4);
-      cv[s][0] = c0.x; cv[s][1] = c0.y; cv[s][2] = c0.z; cv[s][3] = c0.w;
-      cv[s][4] = c1.x; cv[s][5] = c1.y; cv[s][6] = c1.z; cv[s][7] = c1.w;
-    }
-  }
+  for (int s = 0; s < 2; ++s) cbv[s] = cb[nn[s]];
   if (pl < npl) {
     const int p0 = blockIdx.y * pix_per_block, p1 = min(P, p0 + pix_per_block);
-    for (int p = p0 + pl; p < p1; p += npl) {
-      const size_t off = (size_t)p * C + cg * 8;
-      const bf16x8 yv3 = ldv<NT>((const bf16x8*)(y3 + (size_t)bt * PC + off));
+    // every tensor is addressed as (its frame: uniform over the block) + (byte offset within the frame: 32 bits, P * C < 2^31 is
+    // checked by the host), so that one register addresses all streams of a pixel step
+    const bf16* y3f = y3 + (size_t)bt * PC;
+    bf16* dy3f = dy3 + (size_t)bt * PC;
+    auto load = [&](auto& st, int p) __attribute__((always_inline)) {
+      constexpr bool MASKED = sizeof(st) == sizeof(GconvBwdStep<true>);
+      const uint32_t off = ((uint32_t)p * C + cg * 8) * 2;
+      st.y3 = ldv_at<NT>(y3f, off);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        st.g[s] = ldv_at<NT>(g + nn[s] * PC, off);
+        st.r[s] = ldv_at<NT>(raw + nn[s] * PC, off);
+        if constexpr (MASKED) st.x[s] = ldv_at<NT>(xo + nn[s] * PC, off);
+      }
+    };
+    // (every multiply-add is spelled out and contraction is off: the copies of this body -- AHEAD + 1 in the main loop, 2 AHEAD
+    // after it -- must round alike, and as the plain loop did, where hipcc fused exactly these; left to the compiler the copies
+    // differed from each other in the last bits of the sums)
+    auto work = [&](const auto& st, int p) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+      constexpr bool MASKED = sizeof(st) == sizeof(GconvBwdStep<true>);
+      const uint32_t off = ((uint32_t)p * C + cg * 8) * 2;
+      // (mode 1: the emb scales are re-read from LDS at every step, 8 registers at a time, instead of 16 held through the loop --
+      // the index is hidden from the compiler, which would otherwise hoist the reads out of the loop again)
+      int ci = cg * 8;
+      if (MODE == 1) asm volatile("" : "+v"(ci));
+      const bf16x8 yv3 = st.y3;
       float acc3[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc3[i] = 0.f;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const size_t o = nn[s] * PC + off;
-        const bf16x8 gv = ldv<NT>((const bf16x8*)(g + o));
-        const bf16x8 rv = ldv<NT>((const bf16x8*)(raw + o));
+        const bf16x8 gv = st.g[s], rv = st.r[s];
         bf16x8 dv, drv;
-        bf16x8 xv;
-        if (masked) xv = ldv<NT>((const bf16x8*)(xo + o));
+        float cv[8];
+        if (MODE == 1) {
+          const f32x4 c0 = *(const f32x4*)&cvs[s][ci], c1 = *(const f32x4*)&cvs[s][ci + 4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { cv[i] = c0[i]; cv[4 + i] = c1[i]; }
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const float r_ = bf2f(rv[i]);
           float d;
           if (MODE == 1) {
-            const float z = r_ * cv[s][i];
+            const float z = r_ * cv[i];
             const float sg = sigmoid_fast(z);
-            const float dz = bf2f(gv[i]) * (sg * (1.f + z * (1.f - sg))) * (1.0f / 0.596f);
-            part[s][i] += dz * r_;
-            d = dz * cv[s][i];
+            const float dz = bf2f(gv[i]) * (sg * __builtin_fmaf(z, 1.f - sg, 1.f)) * (1.0f / 0.596f);
+            part[s][i] = __builtin_fmaf(dz, r_, part[s][i]);
+            d = dz * cv[i];
           } else {
             float gg = bf2f(gv[i]);
-            if (masked && !(fabsf(bf2f(xv[i])) < clip)) gg = 0.f;
+            if constexpr (MASKED) { if (!(fabsf(bf2f(st.x[s][i])) < clip)) gg = 0.f; }
             drv[i] = f2bf(gg * ta);
             d = gg * tb;
             if (alias) dv[i] = f2bf(gg);                // (what dgrad / wgrad read: the gradient itself, masked if need be)
           }
           float dr = d;                                 // aliasing: tb * (bf16 gradient), exact in fp32
           if (!alias) { dv[i] = f2bf(d); dr = bf2f(dv[i]); }      // else: the rounded value is what dgrad / wgrad will consume
-          s1[s] += dr * r_; s2[s] += dr * bf2f(yv3[i]); acc3[i] += cbv[s] * dr;
+          s1[s] = __builtin_fmaf(dr, r_, s1[s]); s2[s] = __builtin_fmaf(dr, bf2f(yv3[i]), s2[s]);
+          acc3[i] = __builtin_fmaf(cbv[s], dr, acc3[i]);
         }
-        if (!alias || masked) stv<NT>((bf16x8*)(dout + o), dv);   // (aliasing + masked: dout IS g -- every element is read
-        if (MODE == 2 && dres) stv<NT>((bf16x8*)(dres + o), drv); //  and rewritten by the same lane)
+        if (!alias || masked) stv_at<NT>(dout + nn[s] * PC, off, dv);   // (aliasing + masked: dout IS g -- every element is read
+        if (MODE == 2 && dres) stv_at<NT>(dres + nn[s] * PC, off, drv); //  and rewritten by the same lane)
       }
       bf16x8 o3;
 #pragma unroll
       for (int i = 0; i < 8; ++i) o3[i] = f2bf(acc3[i]);
-      stv<NT>((bf16x8*)(dy3 + (size_t)bt * PC + off), o3);
-    }
+      stv_at<NT>(dy3f, off, o3);
+    };
+    if (masked) gconv_bwd_pipeline<GCONV_FUSED_AHEAD, GconvBwdStep<true>>(p0 + pl, p1, npl, load, work);
+    else gconv_bwd_pipeline<GCONV_FUSED_AHEAD, GconvBwdStep<false>>(p0 + pl, p1, npl, load, work);
   }
   // the partial sums meet in a FIXED order (no float atomics in LDS): the result does not depend on wave scheduling
   if (MODE == 1 && (G8 & (G8 - 1)) == 0) {
@@ -597,7 +690,8 @@ extern "C" int oniris_gconv_bwd_fused(int mode, const void* g, const void* raw, 
                                       const int32_t* clip_flag, float* coef_own_scaled, oniris_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   ONIRIS_CHECK_ARG((mode == 1 || mode == 2) && g && raw && y3 && coef_own && coef_ctx && dout && dy3 && d_coef_own &&
-                   d_coef_ctx && B > 0 && T > 0 && P > 0 && C % 8 == 0 && C <= 512, "gconv_bwd_fused: bad arguments");
+                   d_coef_ctx && B > 0 && T > 0 && P > 0 && C % 8 == 0 && C <= 512 && (long long)P * C < (1LL << 31),
+                   "gconv_bwd_fused: bad arguments");
   ONIRIS_CHECK_ARG(mode != 1 || (cscale && d_cscale), "gconv_bwd_fused: mode 1 needs cscale / d_cscale");
   ONIRIS_CHECK_ARG(mode != 2 || ((dres || coef_own_scaled) && (clip <= 0.f || xo)),
                    "gconv_bwd_fused: mode 2 needs dres (optional under the aliasing protocol) and xo when clipping");
@@ -625,10 +719,11 @@ extern "C" int oniris_gconv_bwd_fused(int mode, const void* g, const void* raw, 
   const int csp = cscale_pitch > 0 ? cscale_pitch : C;
   ONIRIS_CHECK_ARG(csp >= C && csp % 4 == 0, "gconv_bwd_fused: cscale_pitch must be a multiple of 4 and >= C");
   const bool nt = 2LL * B * T * P * C * 2 >= oniris_ew_nt_bytes();       // (the gradient tensor: both slots)
-#define GCONV_BWD_LAUNCH(MODE_, NT_, NTH_, FLAG_, CAS_) ONIRIS_KLAUNCH((gconv_bwd_fused_kernel<MODE_, NT_>), dim3(B * T, slices), dim3(NTH_), 0, stream, (const bf16*)g, \
+#define GCONV_BWD_LAUNCH(MODE_, NT_, NTH_, FLAG_, CAS_) ONIRIS_KLAUNCH((gconv_bwd_fused_kernel<MODE_, NT_, NTH_>), dim3(B * T, slices), dim3(nth), 0, stream, (const bf16*)g, \
                        (const bf16*)raw, (const bf16*)y3, coef_own, coef_ctx, cscale, (const bf16*)xo, (bf16*)dout, \
                        (bf16*)dres, (bf16*)dy3, d_coef_own, d_coef_ctx, d_cscale, T, P, C, ta, tb, clip, ppb, csp, FLAG_, CAS_)
-  if (mode == 1) { if (nt) GCONV_BWD_LAUNCH(1, true, nth, nullptr, nullptr); else GCONV_BWD_LAUNCH(1, false, nth, nullptr, nullptr); }
+  if (mode == 1 && nth > 256) { if (nt) GCONV_BWD_LAUNCH(1, true, 1024, nullptr, nullptr); else GCONV_BWD_LAUNCH(1, false, 1024, nullptr, nullptr); }
+  else if (mode == 1) { if (nt) GCONV_BWD_LAUNCH(1, true, 256, nullptr, nullptr); else GCONV_BWD_LAUNCH(1, false, 256, nullptr, nullptr); }
   else { if (nt) GCONV_BWD_LAUNCH(2, true, 256, (const int*)clip_flag, coef_own_scaled); else GCONV_BWD_LAUNCH(2, false, 256, (const int*)clip_flag, coef_own_scaled); }
 #undef GCONV_BWD_LAUNCH
   ONIRIS_LAUNCH_CHECK();
