@@ -78,6 +78,11 @@ def _area_windows(K, N):
     return [((o * K) // N, -((-(o + 1) * K) // N)) for o in range(N)]
 
 
+def _cp(c):
+    """c channels rounded up to a multiple of 32: the padded output width CP of csrc/vae_wide_conv.h."""
+    return -(-c // 32) * 32
+
+
 def _pack_res(rb, C, g, f32):
     """The two convolutions of a ResBlock in the layouts of vae_conv3_kernel (csrc/vae_conv3.h)."""
     nch, gpt = _nch(C), _gpt(C, g)
@@ -97,7 +102,7 @@ def _pack_res(rb, C, g, f32):
 def _pack_res_wide(rb, C, g, f32):
     """The two convolutions of a ResBlock wider than MAX_NARROW in the layouts of csrc/vae_wide_conv.h: output channels
     [sub][CP] (CP = C rounded up to a multiple of 32), input channels rounded up to even, zero where padded."""
-    CP, CinP = -(-C // 32) * 32, C + (C & 1)
+    CP, CinP = _cp(C), C + (C & 1)
     w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gl
     wa = torch.zeros(2 * g, 3, 3, CinP, g, CP, **f32)
     wa[:, :, :, :C, :, :C] = w.reshape(C, g, C, 2 * g, 3, 3).permute(3, 4, 5, 2, 1, 0)   # kt, ky, kx, ci, gl, c
@@ -112,7 +117,7 @@ def _pack_res_wide(rb, C, g, f32):
 
 def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
     """A 1x1 conv Cin -> nsub Cout (conv channel sub Cout + c) as w [CinP][nsub CP], bias [nsub][CP] (csrc/vae_wide_conv.h)."""
-    CP, CinP = -(-Cout // 32) * 32, Cin + (Cin & 1)
+    CP, CinP = _cp(Cout), Cin + (Cin & 1)
     w = torch.zeros(CinP, nsub, CP, **f32)
     w[:Cin, :, :Cout] = weight.detach().to(**f32).reshape(nsub, Cout, Cin).permute(2, 0, 1)
     b = torch.zeros(nsub, CP, **f32)
@@ -123,7 +128,7 @@ def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
 def _pack_down_wide(weight, bias, Cin, Cout, npos, f32):
     """The compression 1x1 conv npos Cin -> Cout (rearranged channel k = pos Cin + c) as w [npos][CinP][CP], bias [CP]
     (vae_wide_down_kernel of csrc/vae_wide_conv.h)."""
-    CP, CinP = -(-Cout // 32) * 32, Cin + (Cin & 1)
+    CP, CinP = _cp(Cout), Cin + (Cin & 1)
     w = torch.zeros(npos, CinP, CP, **f32)
     w[:, :Cin, :Cout] = weight.detach().to(**f32).reshape(Cout, npos, Cin).permute(1, 2, 0)
     b = torch.zeros(CP, **f32)
@@ -132,45 +137,39 @@ def _pack_down_wide(weight, bias, Cin, Cout, npos, f32):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# launches: thin wrappers, one per entry point, on channels-last fp32 tensors (B, T, H, W, C) of the GPU.  bk: a packed block
-# (VAE._pack, VAE._pack_encoder), rb: one of its packed ResBlocks, pk: the decoder's pack, dims: the coarse grid (B, T, H, W),
+# launches: thin wrappers on channels-last fp32 tensors (B, T, H, W, C) of the GPU, one per stage (temb, up, res, out, down: each
+# picks the narrow or the wide entry point from the packed block it is given) and one per entry point of a ResBlock.  bk: a packed
+# block (VAE._pack, VAE._pack_encoder), rb: one of its packed ResBlocks, pk: the decoder's pack, dims: the coarse grid (B, T, H, W),
 # strides: element strides (b, t, h, w, c) of an operand in any layout, s: the stream.  Each allocates what it writes and returns it.
 
 def _new(x, *shape, dtype=torch.float32):
     return torch.empty(*shape, dtype=dtype, device=x.device)
 
 
-def temb(pk, t, s):
-    """oniris_vae_temb: t (B,) -> the FiLM scale | shift of every ResBlock, [ResBlock][B][2C] flat."""
+def temb(pk, width, t, s):
+    """oniris_vae_temb: t (B,) -> the FiLM scale | shift of every ResBlock, [ResBlock][B][2C] flat; oniris_vae_wide_temb for a
+    model whose widest block has `width` > MAX_NARROW channels (0: none has; the narrow kernel holds the Fourier features of 64)."""
     emb = _new(t, t.shape[0] * pk["emb_per_row"])
-    _lib.check(_lib.lib.oniris_vae_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], _p(t), t.shape[0], _p(emb), s), "vae_temb")
-    return emb
-
-
-def wide_temb(pk, width, t, s):
-    """oniris_vae_wide_temb: as temb, for a model whose widest block has `width` channels (temb holds the Fourier features of 64)."""
-    emb = _new(t, t.shape[0] * pk["emb_per_row"])
-    _lib.check(_lib.lib.oniris_vae_wide_temb(_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"], 2 * width, _p(t), t.shape[0], _p(emb), s),
-               "vae_wide_temb")
+    head = (_p(pk["tparams"]), _p(pk["table"]), pk["n_rb"])
+    if width:
+        _lib.check(_lib.lib.oniris_vae_wide_temb(*head, 2 * width, _p(t), t.shape[0], _p(emb), s), "vae_wide_temb")
+    else:
+        _lib.check(_lib.lib.oniris_vae_temb(*head, _p(t), t.shape[0], _p(emb), s), "vae_temb")
     return emb
 
 
 def up(x, strides, dims, bk, s, scale=None, shift=None):
-    """oniris_vae_up: x over `dims` by `strides` (times scale plus shift per channel) -> (B, T tc, H sc, W sc, C)."""
+    """oniris_vae_up: x over `dims` by `strides` (times scale plus shift per channel) -> (B, T tc, H sc, W sc, C); or
+    oniris_vae_wide_up where bk["wide"]: x is then contiguous (`strides` is not read) and scale / shift are not taken."""
     B, T, H, W = dims
     C, tc, sc = bk["C"], bk["tc"], bk["sc"]
     y = _new(x, B, T * tc, H * sc, W * sc, C)
-    _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]), tc, sc, _p(y),
-                                      s), "vae_up")
-    return y
-
-
-def wide_up(x, bk, s):
-    """oniris_vae_wide_up: contiguous x (B, T, H, W, C) -> (B, T tc, H sc, W sc, C)."""
-    B, T, H, W, C = x.shape
-    tc, sc = bk["tc"], bk["sc"]
-    y = _new(x, B, T * tc, H * sc, W * sc, C)
-    _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(y), B, T, H, W, C, tc, sc, s), "vae_wide_up")
+    if bk["wide"]:
+        assert scale is None and shift is None and x.is_contiguous()
+        _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(y), B, T, H, W, C, tc, sc, s), "vae_wide_up")
+    else:
+        _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]), tc, sc,
+                                          _p(y), s), "vae_up")
     return y
 
 
@@ -215,6 +214,18 @@ def wide_conv_b(a, x, rb, s):
     y = torch.empty_like(x)
     _lib.check(_lib.lib.oniris_vae_wide_conv_b(_p(a), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(y), B, T, H, W, C, s), "vae_wide_conv_b")
     return y
+
+
+def res(x, cin, emb, rb, bk, s):
+    """One ResBlock: x, the cache entry cin or None, the address emb of the FiLM scale | shift (a wide block takes None for none)
+    -> (x + conv B(u), the new cache entry).  Two launches, or where bk["wide"] four: act, conv A, act, conv B."""
+    if not bk.get("wide"):
+        u, cout = res_a(x, cin, emb, rb, bk, s)
+        return res_b(u, x, rb, bk, s), cout
+    seq, cout = wide_act(x, s, emb, cin, bk["g"])
+    u = wide_conv_a(seq, rb, bk["g"], s)
+    a2, _ = wide_act(u, s, out=seq.view(-1)[:x.numel()].view(x.shape))    # S is free again: SiLU(RMS(a)) goes there
+    return wide_conv_b(a2, x, rb, s), cout
 
 
 def out(x, bk, s, lvm=None, want="next"):
@@ -490,14 +501,7 @@ class VAE(BetterModule):
             if cin is not None and (tuple(cin.shape) != (B, g, H, W, C) or cin.device != x.device or cin.dtype != torch.float32):
                 raise ValueError(f"VAE {side} cache entry encoder_block_{i}.res_block_{j} has shape {tuple(cin.shape)}, "
                                  f"expected {(B, g, H, W, C)} (a cache from another batch or resolution)")
-            if bk.get("wide"):                                   # act, conv A, act, conv B (csrc/vae_wide.hip)
-                seq, cout = wide_act(x, s, emb_of(rb), cin, g)
-                u = wide_conv_a(seq, rb, g, s)
-                a2, _ = wide_act(u, s, out=seq.view(-1)[:x.numel()].view(x.shape))    # S is free again: SiLU(RMS(a)) goes there
-                x = wide_conv_b(a2, x, rb, s)
-            else:
-                u, cout = res_a(x, cin, emb_of(rb), rb, bk, s)
-                x = res_b(u, x, rb, bk, s)
+            x, cout = res(x, cin, emb_of(rb), rb, bk, s)
             new_cache[f"res_block_{j}"] = {"conv3d_res0": cout}
         return x, new_cache
 
@@ -512,8 +516,7 @@ class VAE(BetterModule):
         s = _stream()
         t = torch.as_tensor(t, dtype=torch.float32, device=dev)
         t = (t.expand(B) if t.dim() == 0 else t.reshape(B)).contiguous()
-        # oniris_vae_temb holds the 2C Fourier features of up to 64 channels
-        emb = wide_temb(pk, self._wide, t, s) if self._wide else temb(pk, t, s)
+        emb = temb(pk, self._wide, t, s)
         cache = {} if cache is None else cache
         new_cache = {}
         scale = shift = None
@@ -526,7 +529,7 @@ class VAE(BetterModule):
         nblk = len(pk["blocks"])
         for i, bk in enumerate(pk["blocks"]):
             # a wide block is never block 0: its x is the contiguous output of the block before
-            x = wide_up(x, bk, s) if bk["wide"] else up(x, strides, (B, T, H, W), bk, s, scale, shift)
+            x = up(x, strides, (B, T, H, W), bk, s, scale, shift)
             T, H, W = x.shape[1:4]
             scale = shift = None
             x, new_cache[f"encoder_block_{i}"] = self._res_blocks("decoder", i, bk, x, cache.get(f"encoder_block_{i}", {}),

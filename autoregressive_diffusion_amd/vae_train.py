@@ -8,12 +8,18 @@ oniris_vae_train_*, oniris_vae_*_bwd).
 
 Gradients are summed in a fixed order into a bounded number of partial slabs and then over the slabs; nothing uses atomics.
 
-A block wider than vae.MAX_NARROW runs WideRes / WideUp / WideOut / WideDown instead (below): the forward of csrc/vae_wide.hip and
-the backward of csrc/vae_wide_train.hip, for a model on which VAE.wide_training() was called."""
+Down, Up, Out and Res each serve both kernel families and read the family from the packed block they are given, as the launchers
+of vae.py do.  A block wider than vae.MAX_NARROW (bk["wide"]; an encoder `down` that takes the GEMM: bk["wide_down"]) runs the
+forward of csrc/vae_wide.hip, the inference launch sequence without a cache, and the backward on the fp32 MFMA kernels of
+csrc/vae_wide_train.hip (include/oniris.h: oniris_vae_wide_*_bwd), for a model on which VAE.wide_training() was called.  Its
+data-gradient layouts are packed once per parameter version: they live in the packed block / ResBlock of VAE._pack /
+VAE._pack_encoder, which are rebuilt when a parameter changes."""
+from types import SimpleNamespace
+
 import torch
 
 from . import _lib, vae as V
-from .vae import _area_windows, _gpt, _nch, _p, _slab_sum, _stream
+from .vae import _area_windows, _cp, _gpt, _nch, _p, _slab_sum, _stream
 
 _SLAB_BYTES = 64 << 20          # the most memory one launch's partial slabs may take
 _area_cache = {}
@@ -23,6 +29,16 @@ def _nslab(work, size):
     """Partial slabs of `size` floats for `work` work items: one per item up to 1024, fewer when the slabs are large."""
     return int(max(1, min(work, 1024, max(64, _SLAB_BYTES // (4 * size)))))
 
+
+def _cached(pk, key, make):
+    v = pk.get(key)
+    if v is None:
+        v = pk[key] = make()
+    return v
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the 1x1 stages
 
 def _area(K, N, device):
     """The channel-area residual (F.interpolate mode='area' over the channel axis, vae.py:136-141) as a matrix [N][K]."""
@@ -56,199 +72,6 @@ def _lin_dx(dy, vy, wc, vx, grid):
     return dx
 
 
-class Down(torch.autograd.Function):
-    """oniris_vae_down: x, a channels-last view (B, T tc, H sc, W sc, Cin) with any strides -> (B, T, H, W, Cout)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, bk):
-        B, T, H, W = x.shape[0], x.shape[1] // bk["tc"], x.shape[2] // bk["sc"], x.shape[3] // bk["sc"]
-        y = V.down(x, x.stride(), (B, T, H, W), False, bk, _stream())
-        ctx.save_for_backward(x, weight)
-        ctx.bk, ctx.grid = bk, (B, T, H, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        bk, dy = ctx.bk, dy.contiguous()
-        vx, vy = (bk["Cin"], bk["tc"], bk["sc"]), (bk["C"], 1, 1)
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _lin_dw(x.contiguous(), vx, dy, vy, ctx.grid)
-            dw = dw.reshape(weight.shape)
-        if ctx.needs_input_grad[0]:
-            N, K = bk["C"], bk["Cin"] * bk["tc"] * bk["sc"] ** 2
-            dx = _lin_dx(dy, vy, weight.detach().float().reshape(N, K) + _area(K, N, dy.device), vx, ctx.grid)
-        return dx, dw, db, None
-
-
-class Up(torch.autograd.Function):
-    """oniris_vae_up: x, a channels-last view (B, T, H, W, C) with any strides -> (B, T tc, H sc, W sc, C)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, bk):
-        B, T, H, W, C = x.shape
-        up = V.up(x, x.stride(), (B, T, H, W), bk, _stream())
-        ctx.save_for_backward(x, weight)
-        ctx.bk, ctx.grid = bk, (B, T, H, W)
-        return up
-
-    @staticmethod
-    def backward(ctx, dup):
-        x, weight = ctx.saved_tensors
-        bk, dup = ctx.bk, dup.contiguous()
-        C = bk["C"]
-        vx, vy = (C, 1, 1), (C, bk["tc"], bk["sc"])
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _lin_dw(x.contiguous(), vx, dup, vy, ctx.grid)
-            dw = dw.reshape(weight.shape)
-        if ctx.needs_input_grad[0]:
-            dx = _lin_dx(dup, vy, weight.detach().float().reshape(-1, C), vx, ctx.grid)
-        return dx, dw, db, None
-
-
-class Out(torch.autograd.Function):
-    """oniris_vae_out: x (B, T, H, W, C) -> (B, T, H, W, Cout) or, with logvar_multiplier (the last block), (mean, logvar), each
-    (B, Cout / 2, T, H, W)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, lvm, bk, lvm32):
-        ctx.bk, ctx.grid, ctx.last = bk, tuple(x.shape[:4]), lvm is not None
-        if lvm is None:
-            y = V.out(x, bk, _stream())
-            ctx.save_for_backward(x, weight)
-            return y
-        mean, logvar = V.out(x, bk, _stream(), lvm32, "moments")
-        ctx.save_for_backward(x, weight, lvm, logvar)
-        return mean, logvar
-
-    @staticmethod
-    def backward(ctx, *douts):
-        bk = ctx.bk
-        C, Cout = bk["C"], bk["Cout"]
-        dlvm = None
-        if ctx.last:
-            x, weight, lvm, logvar = ctx.saved_tensors
-            dm, dl = douts
-            if ctx.needs_input_grad[3]:
-                dlvm = (dl * logvar).sum().to(lvm.dtype).reshape(lvm.shape)          # logvar = raw exp(lvm)
-            dy = torch.cat((dm, dl * torch.exp(lvm.detach().float())), dim=1).permute(0, 2, 3, 4, 1).contiguous()
-        else:
-            x, weight = ctx.saved_tensors
-            dy = douts[0].contiguous()
-        vx, vy = (C, 1, 1), (Cout, 1, 1)
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _lin_dw(x, vx, dy, vy, ctx.grid)
-            dw = dw.reshape(weight.shape)
-        if ctx.needs_input_grad[0]:
-            dx = _lin_dx(dy, vy, weight.detach().float().reshape(Cout, C) + _area(C, Cout, dy.device), vx, ctx.grid)
-        return dx, dw, db, dlvm, None, None
-
-
-def _pack_dgrad(wa, wb, C, g):
-    """The data-gradient layouts of the two conv weights (include/oniris.h: oniris_vae_res_a_bwd / oniris_vae_res_b_bwd)."""
-    nch, gpt = _nch(C), _gpt(C, g)
-    f32 = dict(dtype=torch.float32, device=wa.device)
-    w = wa.detach().float().reshape(C, g, C, 2 * g, 3, 3).flip(4, 5).permute(3, 1, 4, 5, 0, 2)     # kt, gl, ky, kx, c, ci
-    w = torch.cat((w[g:], w[:g]), dim=1)                                  # r, j: j < g -> (gl j, kt g + r); j >= g -> (gl j - g, kt r)
-    w = w.reshape(g // gpt, gpt, 2 * g, 3, 3, C, C).permute(0, 2, 3, 4, 5, 6, 1)                   # gq, j, ky, kx, c, ci, rl
-    wda = torch.zeros(g // gpt, 2 * g, 3, 3, C, nch, gpt, **f32)
-    wda[..., :C, :] = w
-    wdb = torch.zeros(3, 3, C, nch, **f32)
-    wdb[..., :C] = wb.detach().float()[:, :, 0].flip(2, 3).permute(2, 3, 0, 1)                     # ky, kx, co, ci
-    return wda.contiguous(), wdb.contiguous()
-
-
-class Res(torch.autograd.Function):
-    """A ResBlock (vae.py:56-93) in training mode without a cache: x (B, T, H, W, C), emb (B, 2C) or None -> x + conv B(u)."""
-
-    @staticmethod
-    def forward(ctx, x, emb, wa, ba, wb, bb, bk, pk):
-        B, T, H, W, C = x.shape
-        g, nch, gpt = bk["g"], bk["nch"], bk["gpt"]
-        s = _stream()
-        x = x.contiguous()
-        emb = None if emb is None else emb.detach().float().contiguous()
-        a = torch.empty_like(x)
-        _lib.check(_lib.lib.oniris_vae_train_res_a(_p(x), _p(emb), _p(pk["wa"]), _p(pk["ba"]), B, T, H, W, C, g, nch, gpt, _p(a), s),
-                   "vae_train_res_a")
-        out = torch.empty_like(x)
-        _lib.check(_lib.lib.oniris_vae_train_res_b(_p(a), _p(x), _p(pk["wb"]), _p(pk["bb"]), B, T, H, W, C, nch, _p(out), s),
-                   "vae_train_res_b")
-        ctx.save_for_backward(x, a, wa, wb, *(() if emb is None else (emb,)))
-        ctx.bk = bk
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, a, wa, wb = ctx.saved_tensors[:4]
-        emb = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        bk, dout = ctx.bk, dout.contiguous()
-        B, T, H, W, C = x.shape
-        g, nch, gpt = bk["g"], bk["nch"], bk["gpt"]
-        s = _stream()
-        dev = x.device
-        wda, wdb = _pack_dgrad(wa, wb, C, g)
-        tiles = -(-H // 16) * -(-W // 16)
-        da = torch.empty_like(x)
-        _lib.check(_lib.lib.oniris_vae_res_b_bwd(_p(dout), _p(a), _p(wdb), B, T, H, W, C, nch, _p(da), s), "vae_res_b_bwd")
-        dwa = dba = dwb = dbb = demb = None
-        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
-            n = 9 * C * C + C
-            nslab = _nslab(B * T * tiles, n)
-            slab = torch.zeros(nslab, n, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.oniris_vae_conv3_wgrad_bwd(_p(a), None, _p(dout), B, T, H, W, C, 1, 0, _p(slab), nslab, s),
-                       "vae_conv3_wgrad_bwd")
-            r = _slab_sum(slab, n)
-            dwb = r[:9 * C * C].view(3, 3, C, C).permute(3, 2, 0, 1).reshape(wb.shape)            # ky, kx, ci, c -> c, ci, 1, ky, kx
-            dbb = r[9 * C * C:].clone()
-        want_emb = emb is not None and ctx.needs_input_grad[1]
-        part = torch.empty(tiles * (T // gpt), B, 2 * C, dtype=torch.float32, device=dev) if want_emb else None
-        dx = torch.empty_like(x)
-        _lib.check(_lib.lib.oniris_vae_res_a_bwd(_p(da), _p(x), _p(emb), _p(dout), _p(wda), B, T, H, W, C, g, nch, gpt, _p(dx),
-                                                 _p(part), s), "vae_res_a_bwd")
-        if want_emb:
-            demb = _slab_sum(part, B * 2 * C).view(B, 2 * C)
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            nw = 2 * g * g * 9 * C * C
-            n = nw + g * C
-            nslab = _nslab(B * (T // g) * tiles, n)
-            slab = torch.zeros(nslab, n, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.oniris_vae_conv3_wgrad_bwd(_p(x), _p(emb), _p(da), B, T, H, W, C, g, 1, _p(slab), nslab, s),
-                       "vae_conv3_wgrad_bwd")
-            r = _slab_sum(slab, n)
-            dwa = r[:nw].view(2 * g, g, 3, 3, C, C).permute(5, 1, 4, 0, 2, 3).reshape(wa.shape)   # kt, gl, ky, kx, ci, c -> (c gl), ci, kt, ky, kx
-            dba = r[nw:].view(g, C).t().reshape(-1)
-        return dx, demb, dwa, dba, dwb, dbb, None, None
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# Blocks wider than vae.MAX_NARROW (and an encoder `down` that compresses more than vae.MAX_DOWN_K channels): the backward on the
-# fp32 MFMA kernels of csrc/vae_wide_train.hip (include/oniris.h: oniris_vae_wide_*_bwd).  The forward is the inference launch
-# sequence of csrc/vae_wide.hip without a cache.  The data-gradient layouts are packed once per parameter version: they live in the
-# packed block / ResBlock of VAE._pack / VAE._pack_encoder, which are rebuilt when a parameter changes.
-
-def _cp(c):
-    return -(-c // 32) * 32
-
-
-def _pack_dgrad_wide(wa, wb, C, g):
-    """The data-gradient layouts of a wide ResBlock's conv weights: conv A's for oniris_vae_wide_conv_a on D = [da ++ g zero
-    frames] (tap j < g: (gl, kt) = (j, g + r); j >= g: (j - g, r), r the output frame in its group), conv B's for
-    oniris_vae_wide_conv_b_bwd; both flipped in space and transposed."""
-    CP, CinP = _cp(C), C + (C & 1)
-    f32 = dict(dtype=torch.float32, device=wa.device)
-    w = wa.detach().float().reshape(C, g, C, 2 * g, 3, 3).flip(4, 5).permute(3, 1, 4, 5, 0, 2)     # kt, gl, ky, kx, c, ci
-    w = torch.cat((w[g:], w[:g]), dim=1)                                                           # r, j, ky, kx, c, ci
-    wda = torch.zeros(2 * g, 3, 3, CinP, g, CP, **f32)
-    wda[:, :, :, :C, :, :C] = w.permute(1, 2, 3, 4, 0, 5)                                          # j, ky, kx, c, r, ci
-    wdb = torch.zeros(3, 3, CinP, CP, **f32)
-    wdb[:, :, :C, :C] = wb.detach().float()[:, :, 0].flip(2, 3).permute(2, 3, 0, 1)                # ky, kx, co, ci
-    return wda.contiguous(), wdb.contiguous(), torch.zeros(g, CP, **f32)
-
-
 def _pack_down_dgrad(weight, Cin, Cout, tc, sc):
     """The adjoint of `down` (tc = sc = 1: of `out`) for oniris_vae_wide_down_bwd: (W + the area matrix)^T as an `up` weight."""
     npos = tc * sc * sc
@@ -262,13 +85,6 @@ def _pack_up_dgrad(weight, C, tc, sc):
     """The adjoint of `up` for oniris_vae_wide_up_bwd: W^T as a `down` weight."""
     f32 = dict(dtype=torch.float32, device=weight.device)
     return V._pack_down_wide(weight.detach().float().reshape(-1, C).t(), torch.zeros(C, **f32), C, C, tc * sc * sc, f32)
-
-
-def _cached(pk, key, make):
-    v = pk.get(key)
-    if v is None:
-        v = pk[key] = make()
-    return v
 
 
 def _wide_lin_dw(x, vx, dy, vy, grid, nslab=None):
@@ -294,8 +110,37 @@ def _wide_down_dx(dy, pack, grid, Cy, Cx, tc, sc):
     return dx
 
 
-class WideDown(torch.autograd.Function):
-    """Down where the block's `down` is oniris_vae_wide_down (bk["wide_down"])."""
+def _lin_bwd(need, x, dy, weight, vx, vy, grid, bk, wide, area, key):
+    """The backward of a 1x1 stage: vx / vy = (C, tc, sc) views of x / dy over the coarse grid, area: whether the stage adds the
+    channel-area residual (`down` and `out` do, and only `up` has the compression on dy's side), need: its needs_input_grad ->
+    (dx in the layout of vx, dw, db in the parameters' shapes).  wide: on the MFMA kernels, with x in any strides and the
+    data-gradient pack kept in bk under `key`; otherwise x is made contiguous and the weight is composed per call."""
+    K, N = vx[0] * vx[1] * vx[2] ** 2, vy[0] * vy[1] * vy[2] ** 2
+    dx = dw = db = None
+    if need[1] or need[2]:
+        if wide:
+            dw, db = _wide_lin_dw(x, vx, dy, vy, grid)
+            dw, db = dw.permute(1, 3, 0, 2), db.reshape(-1)                            # px, py, cx, cy -> (py cy), (px cx)
+        else:
+            dw, db = _lin_dw(x.contiguous(), vx, dy, vy, grid)
+        dw = dw.reshape(weight.shape)
+    if need[0] and not wide:
+        wc = weight.detach().float().reshape(N, K)
+        dx = _lin_dx(dy, vy, wc + _area(K, N, dy.device) if area else wc, vx, grid)
+    elif need[0] and area:
+        pack = _cached(bk, key, lambda: _pack_down_dgrad(weight, vx[0], vy[0], vx[1], vx[2]))
+        dx = _wide_down_dx(dy, pack, grid, vy[0], vx[0], vx[1], vx[2])
+    elif need[0]:
+        pack = _cached(bk, key, lambda: _pack_up_dgrad(weight, vx[0], vy[1], vy[2]))
+        dx = torch.empty_like(x)
+        _lib.check(_lib.lib.oniris_vae_wide_up_bwd(_p(dy), _p(pack[0]), _p(pack[1]), _p(dx), *grid, vx[0], vy[1], vy[2], _stream()),
+                   "vae_wide_up_bwd")
+    return dx, dw, db
+
+
+class Down(torch.autograd.Function):
+    """oniris_vae_down, or oniris_vae_wide_down where bk["wide_down"]: x, a channels-last view (B, T tc, H sc, W sc, Cin) with any
+    strides -> (B, T, H, W, Cout)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, bk):
@@ -308,56 +153,43 @@ class WideDown(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        bk, dy = ctx.bk, dy.contiguous()
-        Cin, C, tc, sc = bk["Cin"], bk["C"], bk["tc"], bk["sc"]
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _wide_lin_dw(x, (Cin, tc, sc), dy, (C, 1, 1), ctx.grid)
-            dw = dw[:, 0].permute(2, 0, 1).reshape(weight.shape)                       # pos, ci, co -> co, (pos ci)
-            db = db.reshape(-1)
-        if ctx.needs_input_grad[0]:
-            pack = _cached(bk, "wd_dgrad", lambda: _pack_down_dgrad(weight, Cin, C, tc, sc))
-            dx = _wide_down_dx(dy, pack, ctx.grid, C, Cin, tc, sc)
-        return dx, dw, db, None
+        bk = ctx.bk
+        vx, vy = (bk["Cin"], bk["tc"], bk["sc"]), (bk["C"], 1, 1)
+        return *_lin_bwd(ctx.needs_input_grad, x, dy.contiguous(), weight, vx, vy, ctx.grid, bk, bk.get("wide_down"), True,
+                         "wd_dgrad"), None
 
 
-class WideUp(torch.autograd.Function):
-    """Up of a wide block: oniris_vae_wide_up."""
+class Up(torch.autograd.Function):
+    """oniris_vae_up: x, a channels-last view (B, T, H, W, C) with any strides -> (B, T tc, H sc, W sc, C); oniris_vae_wide_up
+    where bk["wide"], which reads a contiguous x."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, bk):
-        x = x.contiguous()
-        up = V.wide_up(x, bk, _stream())
+        if bk.get("wide"):
+            x = x.contiguous()
+        ctx.bk, ctx.grid = bk, tuple(x.shape[:4])
+        up = V.up(x, x.stride(), ctx.grid, bk, _stream())
         ctx.save_for_backward(x, weight)
-        ctx.bk = bk
         return up
 
     @staticmethod
     def backward(ctx, dup):
         x, weight = ctx.saved_tensors
-        bk, dup = ctx.bk, dup.contiguous()
-        B, T, H, W, C = x.shape
-        tc, sc = bk["tc"], bk["sc"]
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _wide_lin_dw(x, (C, 1, 1), dup, (C, tc, sc), (B, T, H, W))
-            dw = dw[0].permute(0, 2, 1).reshape(weight.shape)                          # sub, ci, co -> (sub co), ci
-            db = db.reshape(-1)
-        if ctx.needs_input_grad[0]:
-            pack = _cached(bk, "wu_dgrad", lambda: _pack_up_dgrad(weight, C, tc, sc))
-            dx = torch.empty_like(x)
-            _lib.check(_lib.lib.oniris_vae_wide_up_bwd(_p(dup), _p(pack[0]), _p(pack[1]), _p(dx), B, T, H, W, C, tc, sc, _stream()),
-                       "vae_wide_up_bwd")
-        return dx, dw, db, None
+        bk = ctx.bk
+        vx, vy = (bk["C"], 1, 1), (bk["C"], bk["tc"], bk["sc"])
+        return *_lin_bwd(ctx.needs_input_grad, x, dup.contiguous(), weight, vx, vy, ctx.grid, bk, bk.get("wide"), False,
+                         "wu_dgrad"), None
 
 
-class WideOut(torch.autograd.Function):
-    """Out of a wide block: oniris_vae_wide_out."""
+class Out(torch.autograd.Function):
+    """oniris_vae_out, or oniris_vae_wide_out where bk["wide"]: x (B, T, H, W, C) -> (B, T, H, W, Cout) or, with
+    logvar_multiplier (the last block), (mean, logvar), each (B, Cout / 2, T, H, W)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, lvm, bk, lvm32):
-        x = x.contiguous()
-        ctx.bk, ctx.last = bk, lvm is not None
+        if bk.get("wide"):
+            x = x.contiguous()
+        ctx.bk, ctx.grid, ctx.last = bk, tuple(x.shape[:4]), lvm is not None
         if lvm is None:
             y = V.out(x, bk, _stream())
             ctx.save_for_backward(x, weight)
@@ -369,7 +201,6 @@ class WideOut(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *douts):
         bk = ctx.bk
-        C, Cout = bk["C"], bk["Cout"]
         dlvm = None
         if ctx.last:
             x, weight, lvm, logvar = ctx.saved_tensors
@@ -380,16 +211,100 @@ class WideOut(torch.autograd.Function):
         else:
             x, weight = ctx.saved_tensors
             dy = douts[0].contiguous()
-        grid = tuple(x.shape[:4])
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = _wide_lin_dw(x, (C, 1, 1), dy, (Cout, 1, 1), grid)
-            dw = dw[0, 0].t().reshape(weight.shape)
-            db = db.reshape(-1)
-        if ctx.needs_input_grad[0]:
-            pack = _cached(bk, "wo_dgrad", lambda: _pack_down_dgrad(weight, C, Cout, 1, 1))
-            dx = _wide_down_dx(dy, pack, grid, Cout, C, 1, 1)
+        vx, vy = (bk["C"], 1, 1), (bk["Cout"], 1, 1)
+        dx, dw, db = _lin_bwd(ctx.needs_input_grad, x, dy, weight, vx, vy, ctx.grid, bk, bk.get("wide"), True, "wo_dgrad")
         return dx, dw, db, dlvm, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the ResBlock: per width one launch sequence, as five functions with the same shape (and one that packs the data-gradient
+# weights); Res holds what the widths share
+#   fwd(x, emb, bk, pk) -> (a, out)                              a: conv A's output, kept for backward
+#   dwb(a, dout) -> (conv B's weight gradient, flat; its bias gradient, flat)
+#   pack(wa, wb, C, g, pk) -> the data-gradient layouts of the two conv weights, for da and dx
+#   da(dout, a, packs, bk) -> da, in whatever form dwa and dx read it
+#   dwa(x, emb, da, g) -> (conv A's weight gradient, flat; its bias gradient, flat)
+#   dx(da, x, emb, dout, packs, bk, want_emb) -> (dx, the partial sums of d emb or None)
+
+def _pack_dgrad(wa, wb, C, g):
+    """The data-gradient layouts of the two conv weights (include/oniris.h: oniris_vae_res_a_bwd / oniris_vae_res_b_bwd)."""
+    nch, gpt = _nch(C), _gpt(C, g)
+    f32 = dict(dtype=torch.float32, device=wa.device)
+    w = wa.detach().float().reshape(C, g, C, 2 * g, 3, 3).flip(4, 5).permute(3, 1, 4, 5, 0, 2)     # kt, gl, ky, kx, c, ci
+    w = torch.cat((w[g:], w[:g]), dim=1)                                  # r, j: j < g -> (gl j, kt g + r); j >= g -> (gl j - g, kt r)
+    w = w.reshape(g // gpt, gpt, 2 * g, 3, 3, C, C).permute(0, 2, 3, 4, 5, 6, 1)                   # gq, j, ky, kx, c, ci, rl
+    wda = torch.zeros(g // gpt, 2 * g, 3, 3, C, nch, gpt, **f32)
+    wda[..., :C, :] = w
+    wdb = torch.zeros(3, 3, C, nch, **f32)
+    wdb[..., :C] = wb.detach().float()[:, :, 0].flip(2, 3).permute(2, 3, 0, 1)                     # ky, kx, co, ci
+    return wda.contiguous(), wdb.contiguous()
+
+
+def _conv3_dw(xin, emb, dA, g, causal):
+    """The summed slab of oniris_vae_conv3_wgrad_bwd -> (the weights, flat; the biases, flat)."""
+    B, T, H, W, C = xin.shape
+    nw = (2 * g * g if causal else 1) * 9 * C * C
+    n = nw + g * C
+    nslab = _nslab(B * (T // g) * -(-H // 16) * -(-W // 16), n)
+    slab = torch.zeros(nslab, n, dtype=torch.float32, device=xin.device)
+    _lib.check(_lib.lib.oniris_vae_conv3_wgrad_bwd(_p(xin), _p(emb), _p(dA), B, T, H, W, C, g, int(causal), _p(slab), nslab, _stream()),
+               "vae_conv3_wgrad_bwd")
+    r = _slab_sum(slab, n)
+    return r[:nw], r[nw:]
+
+
+def _res_fwd(x, emb, bk, pk):
+    B, T, H, W, C = x.shape
+    g, nch, gpt, s = bk["g"], bk["nch"], bk["gpt"], _stream()
+    a = torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_train_res_a(_p(x), _p(emb), _p(pk["wa"]), _p(pk["ba"]), B, T, H, W, C, g, nch, gpt, _p(a), s),
+               "vae_train_res_a")
+    out = torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_train_res_b(_p(a), _p(x), _p(pk["wb"]), _p(pk["bb"]), B, T, H, W, C, nch, _p(out), s),
+               "vae_train_res_b")
+    return a, out
+
+
+def _res_dwb(a, dout):
+    w, b = _conv3_dw(a, None, dout, 1, False)
+    return w, b.clone()
+
+
+def _res_da(dout, a, packs, bk):
+    B, T, H, W, C = a.shape
+    da = torch.empty_like(a)
+    _lib.check(_lib.lib.oniris_vae_res_b_bwd(_p(dout), _p(a), _p(packs[1]), B, T, H, W, C, bk["nch"], _p(da), _stream()), "vae_res_b_bwd")
+    return da
+
+
+def _res_dx(da, x, emb, dout, packs, bk, want_emb):
+    B, T, H, W, C = x.shape
+    g, nch, gpt = bk["g"], bk["nch"], bk["gpt"]
+    tiles = -(-H // 16) * -(-W // 16)
+    part = torch.empty(tiles * (T // gpt), B, 2 * C, dtype=torch.float32, device=x.device) if want_emb else None
+    dx = torch.empty_like(x)
+    _lib.check(_lib.lib.oniris_vae_res_a_bwd(_p(da), _p(x), _p(emb), _p(dout), _p(packs[0]), B, T, H, W, C, g, nch, gpt, _p(dx),
+                                             _p(part), _stream()), "vae_res_a_bwd")
+    return dx, part
+
+
+_NARROW_RES = SimpleNamespace(fwd=_res_fwd, dwb=_res_dwb, pack=lambda wa, wb, C, g, pk: _pack_dgrad(wa, wb, C, g), da=_res_da,
+                              dwa=lambda x, emb, da, g: _conv3_dw(x, emb, da, g, True), dx=_res_dx)
+
+
+def _pack_dgrad_wide(wa, wb, C, g):
+    """The data-gradient layouts of a wide ResBlock's conv weights: conv A's for oniris_vae_wide_conv_a on D = [da ++ g zero
+    frames] (tap j < g: (gl, kt) = (j, g + r); j >= g: (j - g, r), r the output frame in its group), conv B's for
+    oniris_vae_wide_conv_b_bwd; both flipped in space and transposed."""
+    CP, CinP = _cp(C), C + (C & 1)
+    f32 = dict(dtype=torch.float32, device=wa.device)
+    w = wa.detach().float().reshape(C, g, C, 2 * g, 3, 3).flip(4, 5).permute(3, 1, 4, 5, 0, 2)     # kt, gl, ky, kx, c, ci
+    w = torch.cat((w[g:], w[:g]), dim=1)                                                           # r, j, ky, kx, c, ci
+    wda = torch.zeros(2 * g, 3, 3, CinP, g, CP, **f32)
+    wda[:, :, :, :C, :, :C] = w.permute(1, 2, 3, 4, 0, 5)                                          # j, ky, kx, c, r, ci
+    wdb = torch.zeros(3, 3, CinP, CP, **f32)
+    wdb[:, :, :C, :C] = wb.detach().float()[:, :, 0].flip(2, 3).permute(2, 3, 0, 1)                # ky, kx, co, ci
+    return wda.contiguous(), wdb.contiguous(), torch.zeros(g, CP, **f32)
 
 
 def _wide_act_bwd(x, emb, dy, add, dx, part):
@@ -410,61 +325,90 @@ def _wide_conv3_dw(xin, dA, B, T, H, W, C, g, causal, nslab=None):
     return r[:nw], r[nw:]
 
 
-class WideRes(torch.autograd.Function):
-    """Res at a width above MAX_NARROW: the forward is act, conv A, act, conv B of csrc/vae_wide.hip (VAE._res_blocks without a
-    cache); x and a are kept, S and u are formed again in backward.  nslab (tests): the slab count of the two weight gradients."""
+# the wide sequence keeps x and a only: u and S are formed again in backward, each inside the function that reads it, so that u is
+# freed before du is allocated, du before S and S before the last stage
+
+def _wide_res_fwd(x, emb, bk, pk):
+    """act, conv A, act, conv B of csrc/vae_wide.hip (vae.res without a cache)."""
+    g, s = bk["g"], _stream()
+    seq, _ = V.wide_act(x, s, _p(emb), None, g)
+    a = V.wide_conv_a(seq, pk, g, s)
+    u, _ = V.wide_act(a, s, out=seq.view(-1)[:x.numel()].view(x.shape))
+    return a, V.wide_conv_b(u, x, pk, s)
+
+
+def _wide_res_dwb(a, dout):
+    u, _ = V.wide_act(a, _stream())
+    return _wide_conv3_dw(u, dout, *a.shape, 1, False)
+
+
+def _wide_res_da(dout, a, packs, bk):
+    B, T, H, W, C = a.shape
+    du = torch.empty_like(a)
+    _lib.check(_lib.lib.oniris_vae_wide_conv_b_bwd(_p(dout), _p(packs[1]), _p(du), B, T, H, W, C, _stream()), "vae_wide_conv_b_bwd")
+    D = torch.empty(B, T + bk["g"], H, W, C, dtype=torch.float32, device=a.device)      # [da ++ g zero frames]
+    D[:, T:].zero_()
+    _wide_act_bwd(a, None, du, None, D, None)
+    return D
+
+
+def _wide_res_dwa(x, emb, D, g):
+    S, _ = V.wide_act(x, _stream(), _p(emb), None, g)
+    return _wide_conv3_dw(S, D, *x.shape, g, True)
+
+
+def _wide_res_dx(D, x, emb, dout, packs, bk, want_emb):
+    B, T, H, W, C = x.shape
+    dy = V.wide_conv_a(D, dict(wa=packs[0], ba=packs[2]), bk["g"], _stream())
+    part = torch.empty(-(-T * H * W // 256), B, 2 * C, dtype=torch.float32, device=x.device) if want_emb else None
+    dx = torch.empty_like(x)
+    _wide_act_bwd(x, emb, dy, dout, dx, part)
+    return dx, part
+
+
+_WIDE_RES = SimpleNamespace(fwd=_wide_res_fwd, dwb=_wide_res_dwb, da=_wide_res_da, dwa=_wide_res_dwa, dx=_wide_res_dx,
+                            pack=lambda wa, wb, C, g, pk: _cached(pk, "dgrad", lambda: _pack_dgrad_wide(wa, wb, C, g)))
+
+
+class Res(torch.autograd.Function):
+    """A ResBlock (vae.py:56-93) in training mode without a cache: x (B, T, H, W, C), emb (B, 2C) or None -> x + conv B(u), on
+    the launch sequence of the block's width (bk["wide"]).  Backward forms only what was asked for, conv B's weight gradient
+    first: a block of which only conv B trains stops there."""
 
     @staticmethod
-    def forward(ctx, x, emb, wa, ba, wb, bb, bk, pk, nslab=None):
-        g, s = bk["g"], _stream()
+    def forward(ctx, x, emb, wa, ba, wb, bb, bk, pk):
+        k = _WIDE_RES if bk.get("wide") else _NARROW_RES
         x = x.contiguous()
         emb = None if emb is None else emb.detach().float().contiguous()
-        seq, _ = V.wide_act(x, s, _p(emb), None, g)
-        a = V.wide_conv_a(seq, pk, g, s)
-        u, _ = V.wide_act(a, s, out=seq.view(-1)[:x.numel()].view(x.shape))
-        out = V.wide_conv_b(u, x, pk, s)
+        a, out = k.fwd(x, emb, bk, pk)
         ctx.save_for_backward(x, a, wa, wb, *(() if emb is None else (emb,)))
-        ctx.bk, ctx.pk, ctx.nslab = bk, pk, nslab
+        ctx.bk, ctx.pk, ctx.k = bk, pk, k
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, a, wa, wb = ctx.saved_tensors[:4]
         emb = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        bk, pk, dout = ctx.bk, ctx.pk, dout.contiguous()
-        B, T, H, W, C = x.shape
-        g, s = bk["g"], _stream()
-        wda, wdb, zb = _cached(pk, "dgrad", lambda: _pack_dgrad_wide(wa, wb, C, g))
-        need = ctx.needs_input_grad
+        bk, k, need, dout = ctx.bk, ctx.k, ctx.needs_input_grad, dout.contiguous()
+        B, C, g = x.shape[0], x.shape[4], bk["g"]
         want_emb = emb is not None and need[1]
-        dwa = dba = dwb = dbb = demb = dx = None
+        dx = demb = dwa = dba = dwb = dbb = None
         if need[4] or need[5]:
-            u, _ = V.wide_act(a, s)
-            r, dbb = _wide_conv3_dw(u, dout, B, T, H, W, C, 1, False, ctx.nslab)
+            r, dbb = k.dwb(a, dout)
             dwb = r.view(3, 3, C, C).permute(3, 2, 0, 1).reshape(wb.shape)            # ky, kx, ci, c -> c, ci, 1, ky, kx
-            del u
         if not (need[0] or want_emb or need[2] or need[3]):
-            return None, None, None, None, dwb, dbb, None, None, None
-        du = torch.empty_like(x)
-        _lib.check(_lib.lib.oniris_vae_wide_conv_b_bwd(_p(dout), _p(wdb), _p(du), B, T, H, W, C, s), "vae_wide_conv_b_bwd")
-        D = torch.empty(B, T + g, H, W, C, dtype=torch.float32, device=x.device)      # [da ++ g zero frames]
-        D[:, T:].zero_()
-        _wide_act_bwd(a, None, du, None, D, None)
-        del du
+            return None, None, None, None, dwb, dbb, None, None
+        packs = k.pack(wa, wb, C, g, ctx.pk)
+        da = k.da(dout, a, packs, bk)
         if need[2] or need[3]:
-            S, _ = V.wide_act(x, s, _p(emb), None, g)
-            r, dba = _wide_conv3_dw(S, D, B, T, H, W, C, g, True, ctx.nslab)
+            r, dba = k.dwa(x, emb, da, g)
             dwa = r.view(2 * g, g, 3, 3, C, C).permute(5, 1, 4, 0, 2, 3).reshape(wa.shape)   # kt, gl, ky, kx, ci, c -> (c gl), ci, kt, ky, kx
             dba = dba.view(g, C).t().reshape(-1)
-            del S
         if need[0] or want_emb:
-            dy = V.wide_conv_a(D, dict(wa=wda, ba=zb), g, s)
-            part = torch.empty(-(-T * H * W // 256), B, 2 * C, dtype=torch.float32, device=x.device) if want_emb else None
-            dx = torch.empty_like(x)
-            _wide_act_bwd(x, emb, dy, dout, dx, part)
+            dx, part = k.dx(da, x, emb, dout, packs, bk, want_emb)
             if want_emb:
                 demb = _slab_sum(part, B * 2 * C).view(B, 2 * C)
-        return dx, demb, dwa, dba, dwb, dbb, None, None, None
+        return dx, demb, dwa, dba, dwb, dbb, None, None
 
 
 class _EmbValues(torch.autograd.Function):
@@ -479,10 +423,8 @@ class _EmbValues(torch.autograd.Function):
         return g, None
 
 
-def _res(wide, y, emb, rb, bk, pk):
-    """One ResBlock on the kernels of its width."""
-    w = (rb.conv3d0.conv3d.weight, rb.conv3d0.conv3d.bias, rb.conv3d1.weight, rb.conv3d1.bias)
-    return WideRes.apply(y, emb, *w, bk, pk, None) if wide else Res.apply(y, emb, *w, bk, pk)
+def _convs(rb):
+    return rb.conv3d0.conv3d.weight, rb.conv3d0.conv3d.bias, rb.conv3d1.weight, rb.conv3d1.bias
 
 
 def run(vae, x, t_b, noise):
@@ -493,9 +435,9 @@ def run(vae, x, t_b, noise):
     epk, dpk = vae._pack_encoder(dev), vae._pack(dev)
     y = x.float().permute(0, 2, 3, 4, 1)
     for blk, bk in zip(vae.encoder.encoder_blocks, epk["blocks"]):
-        y = (WideDown if bk.get("wide_down") else Down).apply(y, blk.compression_block.weight, blk.compression_block.bias, bk)
+        y = Down.apply(y, blk.compression_block.weight, blk.compression_block.bias, bk)
         for rb, pk in zip(blk.res_blocks, bk["res"]):
-            y = _res(bk.get("wide"), y, None, rb, bk, pk)
+            y = Res.apply(y, None, *_convs(rb), bk, pk)
     mean = y.permute(0, 4, 1, 2, 3).contiguous()
     if noise is None:
         noise = torch.randn_like(mean)
@@ -504,18 +446,16 @@ def run(vae, x, t_b, noise):
     nblk, B = len(dpk["blocks"]), x.shape[0]
     # a model with a wide block: the values of every FiLM scale | shift are those of the inference launch (oniris_vae_wide_temb), so
     # that the decoder's forward is bit for bit the eval-mode one; the gradient still flows through the torch expression
-    embk = V.wide_temb(dpk, vae._wide, t_b.contiguous(), _stream()) if vae._wide else None
+    embk = V.temb(dpk, vae._wide, t_b.contiguous(), _stream()) if vae._wide else None
     for i, (blk, bk) in enumerate(zip(vae.decoder.encoder_blocks, dpk["blocks"])):
-        wide = bk["wide"]
-        y = (WideUp if wide else Up).apply(y, blk.decompression_block.weight, blk.decompression_block.bias, bk)
+        y = Up.apply(y, blk.decompression_block.weight, blk.decompression_block.bias, bk)
         for rb, pk in zip(blk.res_blocks, bk["res"]):
             emb = rb.t_cond(rb.fourier_cond(t_b))
             if embk is not None:
                 emb = _EmbValues.apply(emb, embk[B * pk["emb_off"]:B * (pk["emb_off"] + 2 * bk["C"])].view(B, 2 * bk["C"]))
-            y = _res(wide, y, emb, rb, bk, pk)
-        out = WideOut if wide else Out
+            y = Res.apply(y, emb, *_convs(rb), bk, pk)
         if i < nblk - 1:
-            y = out.apply(y, blk.final_conv.weight, blk.final_conv.bias, None, bk, None)
+            y = Out.apply(y, blk.final_conv.weight, blk.final_conv.bias, None, bk, None)
         else:
-            r_mean, r_logvar = out.apply(y, blk.final_conv.weight, blk.final_conv.bias, vae.decoder.logvar_multiplier, bk, dpk["lvm"])
+            r_mean, r_logvar = Out.apply(y, blk.final_conv.weight, blk.final_conv.bias, vae.decoder.logvar_multiplier, bk, dpk["lvm"])
     return r_mean, r_logvar, mean

@@ -1,5 +1,5 @@
 """Wide VAE training on the GPU (csrc/vae_wide_train.hip, csrc/vae_wide_train.h; autoregressive_diffusion_amd/vae_train.py:
-WideRes, WideDown, WideUp, WideOut; VAE.wide_training()) against tests/vae_train_cpu_restatement.py in float64.
+Res, Down, Up, Out on a wide packed block; VAE.wide_training()) against tests/vae_train_cpu_restatement.py in float64.
 
 Stages, through the autograd Functions with operands packed by vae.py's own pack functions, on Gaussian operands: outputs, input
 gradient, parameter gradients and d emb under the two metrics and bounds of tests/vae_stage_oracle.py (5 x the distance of the
@@ -92,13 +92,48 @@ def test_res_stage(case):
     pk = V._pack_res_wide(rb, C, g, F32)
     xd = _cl(x).requires_grad_()
     embd = None if emb is None else emb.to(DEV).requires_grad_()
-    out = vae_train.WideRes.apply(xd, embd, *w, dict(g=g), pk, None)
+    out = vae_train.Res.apply(xd, embd, *w, dict(g=g, wide=True), pk)
     assert out.grad_fn is not None
     out.backward(_cl(dout))
     grads = dict(dx=_cf(xd.grad), dwa=w[0].grad.cpu(), dba=w[1].grad.cpu(), dwb=w[2].grad.cpu(), dbb=w[3].grad.cpu())
     if with_emb:
         grads["demb"] = embd.grad.cpu()
     _judge(f"res {_IDS(case)}", (dict(out=_cf(out)), grads), ref64, ref32)
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide"])
+def test_res_where_only_conv_b_trains(wide):
+    """Res with only conv B's weight and bias requiring grad: backward ends after conv B's weight gradient.  dwb and dbb are the
+    bits of the all-trainable run on the same operands, and every other .grad stays None.  Narrow: the smallest case of
+    S.RES_CASES; wide: (C, g, H, W) = (72, 2, 5, 7) with B = 2, T = 2g."""
+    from autoregressive_diffusion_amd import vae as V, vae_train
+    gen = torch.Generator().manual_seed(2550)
+    if wide:
+        (C, g, H, W), B = (72, 2, 5, 7), 2
+        T = 2 * g
+        rb, x, emb = _res_block(C, g, gen), torch.randn(B, C, T, H, W, generator=gen), None
+        pk, bk = V._pack_res_wide(rb.to(DEV), C, g, F32), dict(g=g, wide=True)
+    else:
+        case = min((c for c, _ in S.RES_CASES.values()), key=lambda c: c[0] * c[1] * c[2] * c[3] * c[4])
+        B, T, H, W, C, g, _ = case
+        rb, x, emb = S.res_operands(case)
+        pk, bk = V._pack_res(rb.to(DEV), C, g, F32), dict(g=g, nch=V._nch(C), gpt=V._gpt(C, g))
+    w = [rb.conv3d0.conv3d.weight, rb.conv3d0.conv3d.bias, rb.conv3d1.weight, rb.conv3d1.bias]
+    xd, doutd = _cl(x), _cl(torch.randn(B, C, T, H, W, generator=gen))
+
+    def run(everything):
+        for p in w:
+            p.grad = None
+        w[0].requires_grad_(everything), w[1].requires_grad_(everything)
+        xg = xd.clone().requires_grad_(everything)
+        eg = None if emb is None else emb.to(DEV).requires_grad_(everything)
+        vae_train.Res.apply(xg, eg, *w, bk, pk).backward(doutd)
+        return [p.grad for p in w], [xg.grad, None if eg is None else eg.grad]
+    full, full_in = run(True)
+    only, only_in = run(False)
+    assert all(v is not None for v in full) and full_in[0] is not None
+    assert torch.equal(only[2], full[2]) and torch.equal(only[3], full[3])
+    assert only[0] is None and only[1] is None and only_in == [None, None]
 
 
 def _lin_module(cin, cout, gen):
@@ -123,7 +158,7 @@ def test_down_stage(case):
     wd, bd = V._pack_down_wide(conv.weight, conv.bias, Cin, C, npos, F32)
     bk = dict(Cin=Cin, C=C, tc=tc, sc=sc, wd=wd, bd=bd, wide_down=True)
     xd = (x.to(DEV).permute(0, 2, 3, 4, 1) if case == DOWN_CASES[0] else _cl(x)).requires_grad_()
-    y = vae_train.WideDown.apply(xd, conv.weight, conv.bias, bk)
+    y = vae_train.Down.apply(xd, conv.weight, conv.bias, bk)
     y.backward(_cl(dy))
     _judge(f"down {_IDS(case)}", (dict(y=_cf(y)), dict(dx=_cf(xd.grad), dw=conv.weight.grad.cpu(), db=conv.bias.grad.cpu())), ref64, ref32)
 
@@ -140,7 +175,7 @@ def test_up_stage(case):
     conv = conv.to(DEV)
     wu, bu = V._pack_lin_wide(conv.weight, conv.bias, C, C, npos, F32)
     xd = _cl(x).requires_grad_()
-    y = vae_train.WideUp.apply(xd, conv.weight, conv.bias, dict(C=C, tc=tc, sc=sc, wu=wu, bu=bu, wide=True))
+    y = vae_train.Up.apply(xd, conv.weight, conv.bias, dict(C=C, tc=tc, sc=sc, wu=wu, bu=bu, wide=True))
     y.backward(_cl(dup))
     _judge(f"up {_IDS(case)}", (dict(y=_cf(y)), dict(dx=_cf(xd.grad), dw=conv.weight.grad.cpu(), db=conv.bias.grad.cpu())), ref64, ref32)
 
@@ -163,11 +198,11 @@ def test_out_stage(case):
     grads = lambda: dict(dx=_cf(xd.grad), dw=conv.weight.grad.cpu(), db=conv.bias.grad.cpu())
     if split:
         lvmd = torch.nn.Parameter(lvm.detach().to(DEV))
-        mean, logvar = vae_train.WideOut.apply(xd, conv.weight, conv.bias, lvmd, bk, lvmd.detach().float().reshape(1).contiguous())
+        mean, logvar = vae_train.Out.apply(xd, conv.weight, conv.bias, lvmd, bk, lvmd.detach().float().reshape(1).contiguous())
         torch.autograd.backward((mean, logvar), [d.to(DEV) for d in douts])
         got = (dict(mean=mean.detach().cpu(), logvar=logvar.detach().cpu()), dict(grads(), dlvm=lvmd.grad.cpu()))
     else:
-        y = vae_train.WideOut.apply(xd, conv.weight, conv.bias, None, bk, None)
+        y = vae_train.Out.apply(xd, conv.weight, conv.bias, None, bk, None)
         y.backward(_cl(douts[0]))
         got = (dict(y=_cf(y)), grads())
     _judge(f"out {_IDS(case)}", got, ref64, ref32)
@@ -376,7 +411,8 @@ def test_frozen_encoder():
 
 
 def test_narrow_model_is_untouched():
-    """channels=[3,8,8,8] trained with the switch off and on: the same output and gradient bits (it never meets a wide Function)."""
+    """channels=[3,8,8,8] trained with the switch off and on: the same output and gradient bits (none of its packed blocks is
+    wide, so every Function takes the narrow kernels either way)."""
     from autoregressive_diffusion_amd.vae import VAE
     gen = torch.Generator().manual_seed(3200)
     vae = O.seed_params(VAE(channels=[3, 8, 8, 8], n_res_blocks=1), 3201).to(DEV).train()

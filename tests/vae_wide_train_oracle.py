@@ -1,5 +1,5 @@
-"""Float64 references for the backward of the wide VAE stages (autoregressive_diffusion_amd/vae_train.py: WideRes, WideDown,
-WideUp, WideOut): Python restatements of the indexing of the kernels that run the data gradients on repacked weights, so that a
+"""Float64 references for the backward of the wide VAE stages (autoregressive_diffusion_amd/vae_train.py: Res, Down, Up, Out
+on a wide packed block): Python restatements of the indexing of the kernels that run the data gradients on repacked weights, so that a
 packing layout can be judged on the CPU, and the stages of tests/vae_train_cpu_restatement.py under autograd in float64 (the
 reference) and float32 (whose distance from float64 sets the bounds).  Nothing here launches a kernel."""
 import torch
