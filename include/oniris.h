@@ -87,7 +87,9 @@ typedef struct OnirisWeightDesc {
   void* dwp;       /* bf16 split-K slabs [nsplit_cap][CoutP][taps][CinP]: oniris_conv_wgrad workgroup column s   *
                     * overwrites slab s with plain stores (its fp32 partial sum rounded once); oniris_weight_bwd  *
                     * adds the first *nsplit slabs in fp32                                                         */
-  float* dws;      /* fp32 [CoutP][taps][CinP]: the sum of the slabs (scratch of oniris_weight_bwd)               */
+  float* dws;      /* fp32, CoutP*taps*CinP elements: scratch of oniris_weight_bwd (the row sums of the slabs between   *
+                    * its two passes).  The layout is private to the kernel: parameter order (co*fan + ci*taps +   *
+                    * tap) in the transposing form, slab order [CoutP][taps][CinP] in the four-chain form           */
   int32_t cout, cin, taps, kt;     /* taps = kt*kh*kw (1, 9 or 18); kt = temporal taps (1 or 2)                  */
   int32_t CoutP, CinP;             /* CoutP = roundup(cout,32), CinP = roundup(cin,64)                           */
   int32_t CoutPb, CinPb;           /* CoutPb = roundup(cin,32), CinPb = roundup(cout,64)                         */

@@ -1,6 +1,7 @@
-"""What the element-by-element GPU tests (test_glue_stages_gpu.py, test_step_edge_gpu.py) share  --  TEST INFRASTRUCTURE:
-NaN-prefilled output buffers and the three ways a kernel's output is held to a float64 restatement.  The bounds themselves
-(bound_bf16, bound_f32, U_F32_64) live in glue_oracle.py.  Every figure is printed as `<tag> <case> <tensor> <worst error / bound>`."""
+"""What the element-by-element GPU tests (test_glue_stages_gpu.py, test_step_edge_gpu.py, test_weight_stages_gpu.py) share  --
+TEST INFRASTRUCTURE: NaN-prefilled output buffers and the ways a kernel's output is held to a float64 restatement (bf16 outputs,
+fp32 reductions, fp32 elementwise results, exact results).  The bounds themselves (bound_bf16, bound_f32, U_F32_64) live in
+glue_oracle.py.  Every figure is printed as `<tag> <case> <tensor> <worst error / bound>` (tags: GLUE, EDGE, WEIGHT)."""
 import torch
 
 import glue_oracle as GO
