@@ -615,7 +615,11 @@ static int attn_prepare(const OnirisAttnArgs* args, AttnDev& d, const char* who)
   if (a.mask_mode != 0) {
     d.pshift = ilog2_exact(a.P);
     if (d.pshift < 0) { oniris_set_error("%s: P=%d must be a power of two", who, a.P); return ONIRIS_EUNSUPPORTED; }
-    if (a.mask_mode == 1) d.qf_off = (a.Lk - a.Lq) / a.P;
+    if (a.mask_mode == 1) {                          // frames appended behind cached ones: the queries are the LAST Lq / P frames
+      ONIRIS_CHECK_ARG(a.Lk >= a.Lq && (a.Lk - a.Lq) % a.P == 0,
+                       "%s: the frame-causal mask needs Lk >= Lq and whole frames between them (Lq %d, Lk %d, P %d)", who, a.Lq, a.Lk, a.P);
+      d.qf_off = (a.Lk - a.Lq) / a.P;
+    }
     if (a.mask_mode == 2 && (a.Lq != a.Lk || a.Lq != 2 * a.T * a.P || (a.T * a.P) % 128 != 0)) {
       oniris_set_error("%s: training mask needs Lq == Lk == 2*T*P and T*P %% 128 == 0", who); return ONIRIS_EINVAL;
     }

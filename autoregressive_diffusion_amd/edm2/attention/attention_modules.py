@@ -56,6 +56,7 @@ class VideoAttention(_AttentionBase):
             return
         self.rope = RotaryEmbedding(channels // num_heads)
         self.train_mask = None
+        self.context_window = None           # frames the cache keeps (UNet.set_context_window); None: all of them
 
     def _cl(self, x, batch_size, cache=None, update_cache=False, just_2d=False, clip=0.0, pair=False):
         """x (B*t, H, W, C) bf16 -> (mp_sum(x, attention(x)) [clipped], cache).  pair (guided pair evaluation, eval): x is
@@ -68,14 +69,15 @@ class VideoAttention(_AttentionBase):
         P = H * W
         self.__dict__["_tokens_per_frame"] = P               # (UNet.prewarm_eval sizes the next RoPE table from it)
         rope_bufs = (self.rope.inv_freq, self.rope.scale)
+        window = self.__dict__.get("context_window")
         if pair:
             assert not self.training and not torch.is_grad_enabled() and x.is_cuda
             o, cache = ops.attention_eval_x_pair(x, self.attn_qkv.weight.pw, batch_size, self.num_heads, rope_bufs, cache,
-                                                 update_cache, P)
+                                                 update_cache, P, window)
             return self._proj(x, o.reshape(N, H, W, C), clip), cache
         if not self.training and not torch.is_grad_enabled() and x.is_cuda:
             o, cache = ops.attention_eval_x(x, self.attn_qkv.weight.pw, batch_size, self.num_heads, rope_bufs, cache,
-                                            update_cache, P)
+                                            update_cache, P, window)
             return self._proj(x, o.reshape(N, H, W, C), clip), cache
         slot = self._slot(x)
         qkv = self.attn_qkv._cl(x, in_slot=slot).reshape(N, P, 3 * C)
@@ -83,14 +85,14 @@ class VideoAttention(_AttentionBase):
             T = N // (2 * batch_size)
             o = ops.attention_train(qkv, "video", batch_size, T, self.num_heads, rope_bufs)
         else:
-            o, cache = ops.attention_eval(qkv, batch_size, self.num_heads, rope_bufs, cache, update_cache, P)
+            o, cache = ops.attention_eval(qkv, batch_size, self.num_heads, rope_bufs, cache, update_cache, P, window)
         return self._proj(x, o.reshape(N, H, W, C), clip, slot), cache
 
     def forward(self, x, batch_size, cache=None, update_cache=False, just_2d=False):
         if self.num_heads == 0:
             return x, None
         if _fp32.active():
-            return _fp32.video_attention(self, x, batch_size, cache, update_cache, just_2d)
+            return _fp32.video_attention(self, x, batch_size, cache, update_cache, just_2d, self.__dict__.get("context_window"))
         with weights_ready(self):
             y, cache = self._cl(to_cl(x), batch_size, cache, update_cache, just_2d)
             return from_cl(y, x.dtype), cache

@@ -194,6 +194,7 @@ class UNet(BetterModule):
         frame = inspect.currentframe()
         args, _, _, values = inspect.getargvalues(frame)
         self.kwargs = {arg: values[arg] for arg in args if arg != "self"}
+        self.context_window = None          # set_context_window: frames every VideoAttention cache keeps (None: all)
 
     _oniris_cl_io = True        # forward(..., _cl_io=(B, tt)) takes / returns channels-last bf16 (edm2/loss.py fast path)
 
@@ -303,6 +304,20 @@ class UNet(BetterModule):
             out = from_cl(xcl[..., :self.img_channels], torch.float32)
             out = out.reshape(B, tt, *out.shape[1:]) * self.out_gain
             return out, cache
+
+    def set_context_window(self, frames=None):
+        """Bound the evaluation cache: every VideoAttention layer keeps the keys and values of the last `frames` frames (None, the
+        default: of all).  The window bounds what a call LEAVES, not what it sees: a call attends to all cached frames plus its
+        own, and with update_cache=True the cache afterwards holds the last min(frames, cached + new) -- the reference on a cache
+        whose every (K, V) pair was sliced to [:, -frames*P:] after the previous call, without dropping the KV rings.  The conv
+        caches and the gates' frame counters are untouched.  A plain attribute: copy.deepcopy keeps it, state_dict and kwargs
+        do not hold it.  Returns self."""
+        frames = ops._check_window(frames)
+        self.context_window = frames
+        for m in self.modules():
+            if isinstance(m, VideoAttention):
+                m.context_window = frames
+        return self
 
     def pair_ok(self):
         """Does the guided pair evaluation (_forward(_pair=True)) serve this net?  The bf16 path with every VideoAttention layer on
@@ -421,7 +436,7 @@ class UNet(BetterModule):
                 nk = kv[0].shape[1] // P + 1
                 ops.rope_tables(att.rope.inv_freq, att.rope.scale, nk, dev)
                 # room for the next frame in the layer's KV ring (grown here, never inside a capture)
-                ring = ops.KVRing.of(kv, kv[0].shape[0], P, kv[0].shape[2], 1, dev)
+                ring = ops.KVRing.of(kv, kv[0].shape[0], P, kv[0].shape[2], 1, dev, window=att.__dict__.get("context_window"))
                 if ring is not getattr(kv[0], "_oniris_ring", None):
                     cache[(side, name)]["attn"] = ring.views()
                 # the committed keys rotated ONCE for the next frame count (every evaluation of the frame reads them)
@@ -500,6 +515,11 @@ class Precond(BetterModule):
         super().__init__()
         self.unet, self.use_fp16, self.sigma_data = unet, use_fp16, sigma_data
         self.noise_weight = MultiNoiseLoss()
+
+    def set_context_window(self, frames=None):
+        """UNet.set_context_window of the wrapped net.  Returns self."""
+        unwrap_ddp(self.unet).set_context_window(frames)
+        return self
 
     def _ddp_fused_parameters(self):
         core = getattr(self.unet, "module", self.unet)

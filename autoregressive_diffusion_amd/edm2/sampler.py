@@ -80,13 +80,19 @@ class _GraphedDenoiser:
 
     def finish_cache(self):
         """The updated cache after the frame's last replay: every gated conv's (old pair, input of the last evaluation)
-        becomes the shifted pair (reference conv.py:83-86), as fresh tensors outside the graph's memory."""
+        becomes the shifted pair (reference conv.py:83-86), as fresh tensors outside the graph's memory; every windowed KV ring
+        makes room for the next frame (ops.settle_cache)."""
+        from .. import ops
+
         def walk(c):
             if not isinstance(c, dict):
                 return
             fr = c.pop("_pending_frame", None)
             if fr is not None:
                 c["activations"] = torch.cat([c["activations"][:, 1:], fr], dim=1)
+            kv = c.get("attn")
+            if isinstance(kv, tuple):              # a full windowed KV ring moves its live frames to the front (never in a capture)
+                c["attn"] = ops.settle_cache(kv)
             for v in c.values():
                 walk(v)
         walk(self.new_cache)

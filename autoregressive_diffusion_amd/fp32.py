@@ -206,7 +206,15 @@ def wide_heads_train(qkv, kind, B, T, heads, rope_bufs):
 
 
 @torch.no_grad()
-def wide_heads_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
+def _kept(k, v, window):
+    """The (k, v) (b, m, frames, P, d) a call leaves as its cache: everything, or the last `window` frames (the window bounds what
+    is kept, not what the call saw)."""
+    if window is None or k.shape[2] <= window:
+        return k, v
+    return k[:, :, -window:], v[:, :, -window:]
+
+
+def wide_heads_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window=None):
     """Eval-mode VideoAttention core for wide heads (attention_modules.py:51-77): the cache is the reference's -- normalised,
     UN-rotated k and v (b, m, frames, P, d), here fp32 --, every call rotates all keys for the grown key count."""
     u = _utils()
@@ -218,7 +226,8 @@ def wide_heads_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
     q, k, v = (u.normalize(x[:, :, s], dim=-1).reshape(B, t, P, heads, d).permute(0, 3, 1, 2, 4) for s in range(3))
     if kv_cache is not None:
         k, v = torch.cat((kv_cache[0], k), dim=2), torch.cat((kv_cache[1], v), dim=2)
-    new_cache = (k, v) if update_cache else kv_cache
+    from . import ops as _ops
+    new_cache = _kept(k, v, _ops._check_window(window)) if update_cache else kv_cache
     qr, kr = rope(q, k, rope_bufs[0], rope_bufs[1], False)
     vf = v.reshape(B, heads, -1, d)
     if t == 1:
@@ -340,7 +349,7 @@ def frame_attention(mod, x):
     return u.mp_sum(x.float(), mpconv(mod.attn_proj, o), t=mod.attn_balance)
 
 
-def video_attention(mod, x, batch_size, cache=None, update_cache=False, just_2d=False):
+def video_attention(mod, x, batch_size, cache=None, update_cache=False, just_2d=False, window=None):
     """VideoAttention.forward (attention_modules.py:30-82): rotary embedding over the frame index (RoPe.py), the DART training
     mask / causal prefill / one new frame against the cache.  The cache holds normalised UN-rotated k and v (:51-57)."""
     u = _utils()
@@ -358,7 +367,8 @@ def video_attention(mod, x, batch_size, cache=None, update_cache=False, just_2d=
         if cache is not None:
             k, v = torch.cat((cache[0], k), dim=2), torch.cat((cache[1], v), dim=2)
         if update_cache:
-            cache = (k, v)
+            from . import ops as _ops
+            cache = _kept(k, v, _ops._check_window(window))
     rope = mod.rope
     was = rope.training
     rope.train(mod.training)                                           # (the rotary module reads ITS OWN flag for the clean | noised layout)
@@ -396,7 +406,8 @@ def block(mod, x, emb, batch_size, c_noise, cache=None, update_cache=False, just
     x = u.mp_sum(x, y, t=mod.res_balance)
     from .edm2.attention import VideoAttention
     if isinstance(mod.attn, VideoAttention):
-        x, cache["attn"] = video_attention(mod.attn, x, batch_size, cache.get("attn"), update_cache, just_2d)
+        x, cache["attn"] = video_attention(mod.attn, x, batch_size, cache.get("attn"), update_cache, just_2d,
+                                           mod.attn.__dict__.get("context_window"))
     else:
         x, cache["attn"] = frame_attention(mod.attn, x), None
     if mod.clip_act is not None:

@@ -112,6 +112,47 @@ def frame_tables(n_frames, image_size, device):
     return _table_cache[key]
 
 
+APPEND_TABLE_MAX_COLS = 64         # listed blocks per row the grid kernels keep in one VGPR (block_list, csrc/attention_parts.h)
+
+
+def append_mask_table(n_cached, t_new, image_size):
+    """Rectangular kv table of t_new frames appended to n_cached cached ones (query frame i of the call sees key frame j of the
+    n_cached + t_new keys iff j <= n_cached + i): (kv_num (rows,), kv_idx (rows, cols), block_size) int32 numpy arrays, one row per
+    query table block OF THE CALL listing, ascending, every key block with an allowed pair for some row of the query block -- a
+    prefix of the key blocks.  Block size as oniris_infer_mask chooses it (P when P >= 128, else 128); None in its fall-back cases
+    (t*P < 128; t*P % 128 != 0 at P < 128) and where a row would list more than APPEND_TABLE_MAX_COLS blocks: the kernel then
+    walks all key blocks and its per-tile classification prunes.  A query block may straddle key-block boundaries (n*P no
+    multiple of the block): the table is a superset per block, the per-element mask decides."""
+    n, t, P = int(n_cached), int(t_new), int(image_size)
+    if n < 0 or t <= 0 or P <= 0:
+        raise ValueError("append_mask_table: bad sizes")
+    Lq, Lk = t * P, (n + t) * P
+    if Lq < 128 or (P < 128 and Lq % 128 != 0):
+        return None
+    blk = P if P >= 128 else 128
+    rows, nkb = Lq // blk, -(-Lk // blk)
+    q_last = (np.arange(rows, dtype=np.int64) + 1) * blk - 1              # last query token of every row
+    k_last = (n + q_last // P + 1) * P - 1                                # last key token it may see
+    num = np.minimum(nkb, k_last // blk + 1).astype(np.int32)
+    cols = int(num.max())
+    if cols > APPEND_TABLE_MAX_COLS:
+        return None
+    idx = np.zeros((rows, cols), dtype=np.int32)
+    for r in range(rows):
+        idx[r, :num[r]] = np.arange(num[r], dtype=np.int32)
+    return num, idx, blk
+
+
+def append_tables(n_cached, t_new, image_size, device):
+    """Device copy of append_mask_table (kv side only: nothing on the cached path has a backward), cached per (n, t, P, device)."""
+    key = ("append", int(n_cached), int(t_new), int(image_size), str(device))
+    if key not in _table_cache:
+        tab = append_mask_table(n_cached, t_new, image_size)
+        _table_cache[key] = None if tab is None else (torch.from_numpy(tab[0]).to(device), torch.from_numpy(tab[1]).to(device),
+                                                      None, None, tab[2])
+    return _table_cache[key]
+
+
 _sched_cache = {}
 _cu_count = {}
 ATTN_PERSISTENT = int(__import__("os").environ.get("ONIRIS_ATTN_PERSISTENT", "1"))   # 0: grid kernels (A/B knob)
@@ -1809,7 +1850,7 @@ def _attn_args(q, k, v, qt, kt, vt, out, lse, tabs, B, heads, Lq, Lk, C, mask_mo
     if tabs is not None:
         num, idx, qn, qi, a.tab_block = tabs
         a.kv_num, a.kv_idx, a.q_num, a.q_idx = _p(num), _p(idx), _p(qn), _p(qi)
-        a.tab_cols, a.qtab_cols = idx.shape[1], qi.shape[1]
+        a.tab_cols, a.qtab_cols = idx.shape[1], (qi.shape[1] if qi is not None else 0)     # (append_tables: kv side only)
     a.B, a.heads, a.Lq, a.Lk, a.C = B, heads, Lq, Lk, C
     a.mask_mode, a.P, a.T = mask_mode, P, T
     a.frame_kernel = (0 if FRAME_KERNEL else 1) | (0 if DECODE_STREAMS else 2) | (0 if FRAME_FWD_HALVES else 4)
@@ -2164,25 +2205,45 @@ def attention_train(qkv, kind, B, T, heads, rope_bufs=None):
     return fn.apply(qkv, kind, B, T, heads, rope_bufs, torch.is_grad_enabled())
 
 
+def _check_window(window):
+    """A context window is None (unbounded) or a whole number of frames >= 1."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"context window: None or a whole number of frames >= 1 (got {window!r})")
+    return window
+
+
 class KVRing:
     """Preallocated K / V storage of one VideoAttention layer during a rollout: [B][cap frames * P][C]
-    bf16 each, `n` committed frames.  The cache entry the modules hand around stays the reference's (K, V) pair of
-    (B, n*P, C) tensors -- they are VIEWS of the ring (`K._oniris_ring`), so nothing is concatenated or copied per
-    evaluation: the qkv kernel writes the new frames' k, v straight behind the committed ones (an evaluation with
+    bf16 each, `n` committed frames from frame `start` on.  The cache entry the modules hand around stays the reference's
+    (K, V) pair of (B, n*P, C) tensors -- they are VIEWS of the ring (`K._oniris_ring`), so nothing is concatenated or copied
+    per evaluation: the qkv kernel writes the new frames' k, v straight behind the committed ones (an evaluation with
     update_cache=False leaves them uncommitted: the next one overwrites them), RoPE reads the ring through a batch
     stride, the decode kernel reads V in place.  Appending in place is only done for the cache that owns the ring's
-    latest state; a continuation from an older (K, V) pair -- two futures from one cache -- gets a ring of its own."""
+    latest state; a continuation from an older (K, V) pair -- two futures from one cache -- gets a ring of its own.
+    `window` (frames, None: unbounded): a commit keeps the last `window` frames -- `start` moves on, the pair stays one
+    contiguous view; when no further frame fits behind them the live frames are copied to the front (make_room, outside
+    any graph capture), so a full window rolls on in the same storage for ever.  That copy overwrites what OLDER pairs of
+    this ring view: continuing from one of those afterwards is refused (KVRing.of)."""
 
-    def __init__(self, B, P, C, cap, device):
+    def __init__(self, B, P, C, cap, device, window=None):
         self.B, self.P, self.C, self.cap, self.n = B, P, C, cap, 0
+        self.start, self.window = 0, window
+        self.ver, self.moves = 0, 0                 # commits / copies to the front so far (KVRing.of: is a pair the latest state?)
         self.K = torch.empty((B, cap * P, C), dtype=BF16, device=device)
         self.V = torch.empty((B, cap * P, C), dtype=BF16, device=device)
         # ROTATED image of K for ONE key count (RoPe.py:55-57 re-rotates every key whenever the count changes): the
         # committed frames are rotated once per generated frame (rotate_committed, from UNet.prewarm_eval), the new frame's
         # key is added by the fused qkv kernel of each of the frame's 31 evaluations -- instead of one pass over the whole
-        # ring per evaluation.  kr_state = (committed frames, key count) the image is valid for.
+        # ring per evaluation.  kr_state = (committed frames, key count) the image is valid for; a commit or a copy to the
+        # front ends it.
         self.KR = torch.empty((B, cap * P, C), dtype=BF16, device=device)
         self.kr_state = None
+
+    def live(self, buf):
+        """`buf` (K, V or KR) from the first live frame on: the base the kernels address with the ring's batch stride."""
+        return buf[:, self.start * self.P:] if self.start else buf
 
     @torch.no_grad()
     def rotate_committed(self, rope_bufs):
@@ -2192,27 +2253,64 @@ class KVRing:
         if n > 0:
             tabs_r = rope_tables(rope_bufs[0], rope_bufs[1], nk, self.K.device)
             bstride = self.cap * self.P * self.C
-            _rope(self.K, self.KR, None, tabs_r, 2, self.B, n, self.P, self.C, 0, nk, x_bstride=bstride, xr_bstride=bstride)
+            _rope(self.live(self.K), self.live(self.KR), None, tabs_r, 2, self.B, n, self.P, self.C, 0, nk, x_bstride=bstride,
+                  xr_bstride=bstride)
         self.kr_state = (n, nk)
 
     def views(self):
-        k, v = self.K[:, :self.n * self.P], self.V[:, :self.n * self.P]
+        lo = self.start * self.P
+        k, v = self.K[:, lo:lo + self.n * self.P], self.V[:, lo:lo + self.n * self.P]
         k._oniris_ring = self
         k._oniris_n = self.n
+        k._oniris_ver = (self.ver, self.moves)
         return k, v
 
+    def commit(self, t):
+        """The t frames written behind the committed ones now belong to the cache; a window keeps its last frames."""
+        self.n += t
+        if self.window is not None and self.n > self.window:
+            self.start += self.n - self.window
+            self.n = self.window
+        self.ver += 1
+        self.kr_state = None
+
+    @torch.no_grad()
+    def make_room(self, t_new=1):
+        """Windowed ring: when t_new more frames do not fit behind the live ones (but would from the front), copy the live frames
+        to the front -- plain copies on the current stream, never inside a graph capture.  -> True where the ring moved."""
+        if (self.window is None or self.start == 0 or self.start + self.n + t_new <= self.cap or self.n + t_new > self.cap
+                or (self.K.is_cuda and torch.cuda.is_current_stream_capturing())):
+            return False
+        lo, ln = self.start * self.P, self.n * self.P
+        for buf in (self.K, self.V):
+            src = buf[:, lo:lo + ln]
+            buf[:, :ln].copy_(src if lo >= ln else src.clone())          # (cap >= 2 * window: the halves do not overlap)
+        self.start, self.kr_state = 0, None
+        self.moves += 1
+        return True
+
+    def owns(self, kv_cache, B, P, C, window):
+        k = kv_cache[0]
+        return (getattr(k, "_oniris_ring", None) is self and self.n == k.shape[1] // P and getattr(k, "_oniris_n", -1) == self.n
+                and getattr(k, "_oniris_ver", (0, 0)) == (self.ver, self.moves) and self.B == B and self.P == P and self.C == C
+                and self.window == window)
+
     @staticmethod
-    def of(kv_cache, B, P, C, t_new, device, grow=True):
+    def of(kv_cache, B, P, C, t_new, device, grow=True, window=None):
         """The ring that holds kv_cache (None: empty) with room for t_new more frames -- the cache's own ring when it is
         its latest state and large enough, else a new one (the old frames are copied once)."""
         n = 0 if kv_cache is None else kv_cache[0].shape[1] // P
         ring = getattr(kv_cache[0], "_oniris_ring", None) if kv_cache is not None else None
-        if (ring is not None and ring.n == n and getattr(kv_cache[0], "_oniris_n", -1) == n and ring.cap >= n + t_new
-                and ring.B == B and ring.P == P and ring.C == C):
+        if ring is not None and ring.owns(kv_cache, B, P, C, window) and ring.start + n + t_new <= ring.cap:
             return ring
         if not grow:
             return None
-        new = KVRing(B, P, C, max(16, 2 * (n + t_new)), device)
+        if ring is not None and getattr(kv_cache[0], "_oniris_ver", (0, 0))[1] != ring.moves:
+            raise RuntimeError("this (K, V) pair is an older state of a windowed KV ring whose storage has been reused since "
+                               "(set_context_window): continue from the latest cache")
+        # a windowed ring never grows once the window is full: 2 * window frames, the live half moves to the front in place
+        cap = max(16, 2 * (n + t_new)) if window is None else max(2 * max(window, t_new), n + t_new)
+        new = KVRing(B, P, C, cap, device, window)
         if n:
             new.K[:, :n * P].copy_(kv_cache[0])
             new.V[:, :n * P].copy_(kv_cache[1])
@@ -2236,35 +2334,50 @@ def _decode_splits(a, B, heads, Lq, Lk, dev):
         a._keep = ws                                # (keeps the workspace alive until the launch is queued)
 
 
-def _ring_commit(ring, nk, kv_cache, update_cache):
-    """The cache after an evaluation that wrote its new frames behind the ring's committed ones: with them (nk frames) or as it was."""
+def _ring_commit(ring, t, kv_cache, update_cache):
+    """The cache after an evaluation that wrote its t new frames behind the ring's committed ones and has QUEUED every launch that
+    reads the ring: with them, or as it was.  A windowed ring that has no room left for one more frame moves its live frames to
+    the front here (eager commit) or, when this runs inside a graph capture, in settle_cache after the frame's last replay."""
     if not update_cache:
         return kv_cache
-    ring.n = nk
+    ring.commit(t)
+    ring.make_room(1)
     return ring.views()
+
+
+def settle_cache(kv_cache):
+    """The (K, V) pair a captured evaluation committed (sampler.finish_cache, outside the capture): the pair itself, or new views
+    of its windowed ring after the copy to the front that the capture could not make."""
+    ring = getattr(kv_cache[0], "_oniris_ring", None) if isinstance(kv_cache, tuple) else None
+    if ring is None or ring.window is None or not ring.owns(kv_cache, ring.B, ring.P, ring.C, ring.window):
+        return kv_cache
+    return ring.views() if ring.make_room(1) else kv_cache
 
 
 def _ring_decode(q, ring, nk, rows, B, heads, kv_cache, update_cache):
     """One new frame per sequence, q (B, P, C) rotated and its k | v already behind the committed frames of the ring (rotated image
-    ready for nk keys): commit it or not, dense attention straight over the ring.  -> (out (rows, P, C) with rows [0, B) written,
-    the cache after the call)"""
+    ready for nk keys): dense attention straight over the ring's live frames, the frame committed or not.  -> (out (rows, P, C)
+    with rows [0, B) written, the cache after the call)"""
     P, C, dev = ring.P, ring.C, q.device
-    new_cache = _ring_commit(ring, nk, kv_cache, update_cache)
     out = torch.empty((rows, P, C), dtype=BF16, device=dev)
-    a = _attn_args(q, ring.KR, ring.V, None, None, None, out[:B], None, None, B, heads, P, nk * P, C, 0, P, 0)
+    a = _attn_args(q, ring.live(ring.KR), ring.live(ring.V), None, None, None, out[:B], None, None, B, heads, P, nk * P, C, 0, P, 0)
     a.v_bstride = a.k_bstride = ring.cap * P * C
     _decode_splits(a, B, heads, P, nk * P, dev)
     check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
-    return out, new_cache
+    return out, _ring_commit(ring, 1, kv_cache, update_cache)
 
 
 def _infer_mask(t, Lq, Lk, P, dev):
-    """(mask_mode, block tables) of the inference mask for t new frames (attention_modules.py:69-75)"""
+    """(mask_mode, block tables) of the inference mask for t new frames (attention_modules.py:69-75).  t > 1 frames behind a
+    non-empty cache (Lk > Lq; a TODO of the reference, :76-77): the per-element mask with the queries' frame offset (Lk - Lq) / P,
+    with the rectangular table of append_mask_table where there is one."""
     if t == 1:
         return 0, None                                          # one new frame: dense SDPA over all keys (:69-70)
     if Lq == Lk:
         return 1, device_tables("infer", t, P, dev)             # causal prefill (:72-75)
-    raise NotImplementedError("The inference mask is not implemented for this case")
+    if Lk < Lq or (Lk - Lq) % P != 0 or Lq != t * P:
+        raise ValueError(f"inference mask: {Lq} queries of {t} frames of {P} tokens against {Lk} keys")
+    return 1, append_tables((Lk - Lq) // P, t, P, dev)
 
 
 FUSED_QKV_EVAL = int(_os.environ.get("ONIRIS_FUSED_QKV_EVAL", "1"))     # 0: conv + qkv_norm[_rope_eval] as separate launches (A/B aid)
@@ -2277,27 +2390,29 @@ def _qkv_eval(x, pw, q, k, v, kr, tabs, ntok, C, kv_tpb, kv_bstride, kv_off, pos
 
 
 @torch.no_grad()
-def attention_eval_x(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P):
+def attention_eval_x(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P, window=None):
     """attention_eval from the layer INPUT x (N, H, W, C) and the packed attn_qkv weight: for one new frame against a
     prepared KV ring the 1x1 convolution, the normalisation and the rotation are one launch (oniris_qkv_eval), 3 launches
     per VideoAttention layer and evaluation instead of 4; every other case runs the convolution and attention_eval."""
     N, C = x.shape[0], x.shape[-1]
     t = N // B
     dev = x.device
-    ring = KVRing.of(kv_cache, B, P, C, t, dev) if (FUSED_QKV_EVAL and t == 1 and C == 64 * heads and pw.cout == 3 * C) else None
+    window = _check_window(window)
+    ring = (KVRing.of(kv_cache, B, P, C, t, dev, window=window)
+            if (FUSED_QKV_EVAL and t == 1 and C == 64 * heads and pw.cout == 3 * C) else None)
     if ring is None or ring.kr_state != (ring.n, ring.n + 1):
         qkv = conv(x, pw).reshape(N, P, 3 * C)
-        return attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P)
+        return attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window)
     n, nk = ring.n, ring.n + 1
     bstride = ring.cap * P * C
     q = torch.empty((N, P, C), dtype=BF16, device=dev)
     _qkv_eval(x.contiguous(), pw, q, ring.K, ring.V, ring.KR, rope_tables(rope_bufs[0], rope_bufs[1], nk, dev), N * P, C, P,
-              bstride, n * P, n)
+              bstride, (ring.start + n) * P, n)
     return _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
 
 
 @torch.no_grad()
-def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P):
+def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P, window=None):
     """attention_eval_x of a guided pair evaluation: x (2B, H, W, C), rows [0, B) the cached 3-D evaluation of one new frame
     per sequence, rows [B, 2B) the 2-D evaluation of the same input (attention_modules.py:36-45: dense attention inside the
     frame on normalised q | k | v, no RoPE, no KV cache).  -> (out (2B, P, C), cache of the 3-D rows).  With a prepared KV ring:
@@ -2307,9 +2422,10 @@ def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P)
     N, C = x.shape[0], x.shape[-1]
     assert N == 2 * B, (N, B)
     dev = x.device
-    ring = KVRing.of(kv_cache, B, P, C, 1, dev) if (FUSED_QKV_EVAL and C == 64 * heads and pw.cout == 3 * C) else None
+    window = _check_window(window)
+    ring = KVRing.of(kv_cache, B, P, C, 1, dev, window=window) if (FUSED_QKV_EVAL and C == 64 * heads and pw.cout == 3 * C) else None
     if ring is None or ring.kr_state != (ring.n, ring.n + 1):
-        o3, new_cache = attention_eval_x(x[:B], pw, B, heads, rope_bufs, kv_cache, update_cache, P)
+        o3, new_cache = attention_eval_x(x[:B], pw, B, heads, rope_bufs, kv_cache, update_cache, P, window)
         o2 = frame_attention_eval(x[B:], pw, heads)
         return torch.cat([o3.reshape(B, P, C), o2.reshape(B, P, C)]), new_cache
     n, nk = ring.n, ring.n + 1
@@ -2319,7 +2435,8 @@ def attention_eval_x_pair(x, pw, B, heads, rope_bufs, kv_cache, update_cache, P)
     cs_, sn_, sc_ = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
     xc = x.contiguous()
     check(lib.oniris_qkv_eval_pair(_p(xc), _p(pw.wf), _p(q), _p(ring.K), _p(ring.V), _p(ring.KR), _p(cs_), _p(sn_), _p(sc_), N * P,
-                                   B * P, C, pw.CinP, P, bstride, n * P, n, _p(q2), _p(k2), _p(v2), _stream()), "qkv_eval_pair")
+                                   B * P, C, pw.CinP, P, bstride, (ring.start + n) * P, n, _p(q2), _p(k2), _p(v2), _stream()),
+          "qkv_eval_pair")
     out, new_cache = _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
     lse = torch.empty((B, heads, P), dtype=torch.float32, device=dev)
     a2 = _attn_args(q2, k2, v2, None, None, None, out[B:], lse, None, B, heads, P, P, C, 0, P, 1)
@@ -2347,7 +2464,7 @@ def frame_attention_eval(x, pw, heads):
 
 
 @torch.no_grad()
-def _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
+def _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window=None):
     """attention_eval for heads of 8 / 16 / 32 channels (zero-padded into the 64-channel kernels, csrc/attention_hd.hip).  The
     cache is the reference's: normalised, UN-rotated k and v of all frames so far -- here (B, frames*P, heads*64) padded --
     and every call re-rotates all keys for the grown key count (RoPe.py:55-57); no KV ring on this path."""
@@ -2371,7 +2488,9 @@ def _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
     else:
         K, V = knew, vnew
     K, V = K.contiguous(), V.contiguous()
-    new_cache = (K, V) if update_cache else kv_cache
+    window = _check_window(window)
+    keep = nk * P if window is None else min(nk, window) * P            # (the window bounds what is kept, not what this call sees)
+    new_cache = ((K, V) if keep == nk * P else (K[:, -keep:], V[:, -keep:])) if update_cache else kv_cache
     kr = torch.empty_like(K)
     check(lib.oniris_rope_hd(_p(K), _p(kr), _p(cs_), _p(sn_), _p(sc_), B * nk * P, heads, d, P, nk, 0, 2, nk, _stream()), "rope_hd")
     Lq, Lk = t * P, nk * P
@@ -2385,47 +2504,47 @@ def _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
 
 
 @torch.no_grad()
-def attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P):
+def attention_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window=None):
     """Eval-mode VideoAttention core (attention_modules.py:51-77): qkv (B*t, P, 3C) of the NEW frames.
     kv_cache: (K, V) normalised, un-rotated, (B, t_cached*P, C) or None.  Returns out (B*t,P,C), new cache."""
     if _head_dim(qkv.shape[-1] // 3, heads) > 64:
         from . import fp32 as _fp32
-        return _fp32.wide_heads_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P)
+        return _fp32.wide_heads_eval(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window)
     if _head_dim(qkv.shape[-1] // 3, heads) != 64:
-        return _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P)
+        return _attention_eval_hd(qkv, B, heads, rope_bufs, kv_cache, update_cache, P, window)
     N, P_, C3 = qkv.shape
     C = C3 // 3
     dev = qkv.device
     t = N // B
-    ring = KVRing.of(kv_cache, B, P, C, t, dev)
+    ring = KVRing.of(kv_cache, B, P, C, t, dev, window=_check_window(window))
     n = ring.n
     q = torch.empty((N, P, C), dtype=BF16, device=dev)
     bstride = ring.cap * P * C
     nk = n + t
+    w_off = (ring.start + n) * P                    # where the new frames' k | v go: behind the live frames
     if t == 1 and ring.kr_state == (n, nk):
         # one new frame, and the ring's rotated image is ready for this key count (UNet.prewarm_eval): normalisation + the
         # rotation of the new q / k in ONE launch, dense attention straight over the ring -- 4 launches per layer and
         # evaluation instead of 6, and no pass over all cached keys
         cs_, sn_, sc_ = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
         check(lib.oniris_qkv_norm_rope_eval(_p(qkv), _p(q), _p(ring.K), _p(ring.V), _p(ring.KR), _p(cs_), _p(sn_), _p(sc_),
-                                            N * P, C, P, bstride, n * P, n, _stream()), "qkv_norm_rope_eval")
+                                            N * P, C, P, bstride, w_off, n, _stream()), "qkv_norm_rope_eval")
         return _ring_decode(q, ring, nk, N, B, heads, kv_cache, update_cache)
-    check(lib.oniris_qkv_norm(_p(qkv), _p(q), _p(ring.K), _p(ring.V), N * P, C, t * P, bstride, n * P, _stream()), "qkv_norm")
-    new_cache = _ring_commit(ring, nk, kv_cache, update_cache)
+    check(lib.oniris_qkv_norm(_p(qkv), _p(q), _p(ring.K), _p(ring.V), N * P, C, t * P, bstride, w_off, _stream()), "qkv_norm")
     Lq, Lk = t * P, nk * P
     tabs_r = rope_tables(rope_bufs[0], rope_bufs[1], nk, dev)
     qr = torch.empty_like(q)
     kr = torch.empty((B, Lk, C), dtype=BF16, device=dev)
     _rope(q, qr, None, tabs_r, 1, B, t, P, C, nk - t, nk)
-    _rope(ring.K, kr, None, tabs_r, 2, B, nk, P, C, 0, nk, x_bstride=bstride)
+    _rope(ring.live(ring.K), kr, None, tabs_r, 2, B, nk, P, C, 0, nk, x_bstride=bstride)
     out = torch.empty((N, P, C), dtype=BF16, device=dev)
     mask_mode, tabs = _infer_mask(t, Lq, Lk, P, dev)
-    a = _attn_args(qr, kr, ring.V, None, None, None, out, None, tabs, B, heads, Lq, Lk, C, mask_mode, P, 0)
+    a = _attn_args(qr, kr, ring.live(ring.V), None, None, None, out, None, tabs, B, heads, Lq, Lk, C, mask_mode, P, 0)
     a.v_bstride = bstride
     if t == 1:
         _decode_splits(a, B, heads, Lq, Lk, dev)
     check(lib.oniris_attn_fwd(ctypes.byref(a), _stream()), "attn_fwd")
-    return out, new_cache
+    return out, _ring_commit(ring, t, kv_cache, update_cache)
 
 
 # ------------------------------------------------------------------------------------------------------------------
