@@ -259,6 +259,8 @@ def resample(x, f, mode):
     N, C, H, W = x.shape
     if mode == "down":
         xp = torch.nn.functional.pad(x, (pad, pad, pad, pad))
+        if H + 2 * pad < L or W + 2 * pad < L:
+            raise ValueError(f"resample: a {H} x {W} image is smaller than the {L}-tap filter (conv2d refuses it too)")
         Ho, Wo = (H + 2 * pad - L) // 2 + 1, (W + 2 * pad - L) // 2 + 1
         out = None
         for i, fi in enumerate(taps):
