@@ -159,6 +159,10 @@ _SIGS = {
                                           c_float, c_void_p]),
     "oniris_sampler_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float,
                                       c_void_p, c_int, c_float, c_void_p]),
+    "oniris_sampler_ws_blocks": (c_int, [c_size_t]),
+    "oniris_sampler_step": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float,
+                                    c_void_p, c_int, c_float, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "oniris_sampler_mse_finish": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
     "oniris_embed_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_int, c_void_p]),
     "oniris_gates": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -826,6 +826,109 @@ extern "C" int oniris_sampler_update(int mode, float* x_hat, const float* x_pred
   return ONIRIS_OK;
 }
 
+// The same update with the two side branches of the reference's loop folded into the launch (edm2/sampler.py:56-60, 78-83):
+//   mode 0 / 1:  x_next as in sampler_update_kernel;   mode 2 (inject only):  x_next = x_hat
+//   target:  part[0][block] = sum (x_pred - target)^2,  part[1][block] = sum (x_next - target)^2 over the block's elements
+//            (x_next BEFORE the injection; per-thread accumulation, block_sum, one store per block: no atomics)
+//   noise:   x_hat <- x_out <- x_next + coef * noise  (the churn of the NEXT step: product and sum rounded on their own)
+// Without noise the stores are those of sampler_update_kernel (mode 2: x_out <- x_hat when they are two buffers).
+// A grid-stride loop: the grid is capped at ONIRIS_SAMPLER_WS_BLOCKS, so that a step's partials have a bounded size.
+__global__ __launch_bounds__(256) void sampler_step_kernel(int mode, float* x_hat, const float* __restrict__ x_pred,
+                                                           float* __restrict__ d_io, const float* x_aux,     // (x_aux, x_out, x_hat
+                                                           float* x_out, size_t n, float t_a, float dt,       //  may be one buffer)
+                                                           float* __restrict__ sigma_buf, int nsig, float sigma_next,
+                                                           const float* __restrict__ noise, float coef,
+                                                           const float* __restrict__ target, float* __restrict__ part) {
+#pragma clang fp contract(off)     // every product and sum is rounded on its own, like the separate tensor operations
+  __shared__ float red[16];
+  float acc_p = 0.f, acc_x = 0.f;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    if (sigma_buf && i < (size_t)nsig) sigma_buf[i] = sigma_next;
+    const float xh = x_hat[i];
+    float xn = xh;
+    if (mode == 0) {
+      const float d = (xh - x_pred[i]) / t_a;
+      d_io[i] = d;
+      const float s_ = dt * d;
+      xn = xh + s_;
+    } else if (mode == 1) {
+      const float dp = (x_aux[i] - x_pred[i]) / t_a;
+      const float a_ = 0.5f * d_io[i], b_ = 0.5f * dp;
+      const float m_ = dt * (a_ + b_);
+      xn = xh + m_;
+    }
+    if (target) {
+      const float tg = target[i];
+      const float ep = x_pred[i] - tg, ex = xn - tg;
+      const float ep2 = ep * ep, ex2 = ex * ex;
+      acc_p += ep2;
+      acc_x += ex2;
+    }
+    if (noise) {
+      const float c_ = coef * noise[i];
+      const float xc = xn + c_;
+      x_hat[i] = xc;
+      if (x_out != x_hat) x_out[i] = xc;
+    } else if (mode == 1) {
+      x_hat[i] = xn;
+      if (x_out != x_hat) x_out[i] = xn;
+    } else if (mode == 0 || x_out != x_hat) {
+      x_out[i] = xn;
+    }
+  }
+  if (target) {                                       // (uniform over the launch: every thread reaches the barriers)
+    acc_p = block_sum(acc_p, red);
+    acc_x = block_sum(acc_x, red);
+    if (threadIdx.x == 0) {
+      part[blockIdx.x] = acc_p;
+      part[gridDim.x + blockIdx.x] = acc_x;
+    }
+  }
+}
+
+// mse[r] = (sum of row r's `blocks` partials, in index order per thread) / n, one workgroup per row r = step * 2 + {pred, next}
+__global__ __launch_bounds__(256) void sampler_mse_finish_kernel(const float* __restrict__ part, int blocks, float inv_n,
+                                                                 float* __restrict__ mse) {
+  __shared__ float red[16];
+  const float* row = part + (size_t)blockIdx.x * blocks;
+  float acc = 0.f;
+  for (int j = threadIdx.x; j < blocks; j += 256) acc += row[j];
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) mse[blockIdx.x] = acc * inv_n;
+}
+
+static inline unsigned sampler_blocks(size_t n) {
+  const size_t nb = (n + 255) / 256;
+  return (unsigned)(nb < ONIRIS_SAMPLER_WS_BLOCKS ? nb : ONIRIS_SAMPLER_WS_BLOCKS);
+}
+
+extern "C" int oniris_sampler_ws_blocks(size_t n) { return n ? (int)sampler_blocks(n) : 0; }
+
+extern "C" int oniris_sampler_step(int mode, float* x_hat, const float* x_pred, float* d_io, const float* x_aux, float* x_out,
+                                   size_t n, float t_a, float dt, float* sigma_buf, int nsig, float sigma_next, const float* noise,
+                                   float coef, const float* target, float* mse_ws, int step, oniris_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ONIRIS_CHECK_ARG(mode >= 0 && mode <= 2 && x_hat && x_out && n > 0 && (mode == 2 || (x_pred && d_io && t_a != 0.f)) &&
+                   (mode != 1 || x_aux) && nsig >= 0 && (size_t)nsig <= n && (!target || (x_pred && mse_ws && step >= 0)),
+                   "sampler_step: bad arguments");
+  const unsigned nb = sampler_blocks(n);
+  float* part = target ? mse_ws + (size_t)step * 2 * nb : nullptr;
+  ONIRIS_KLAUNCH(sampler_step_kernel, dim3(nb), dim3(256), 0, stream, mode, x_hat, x_pred, d_io, x_aux, x_out, n, t_a, dt,
+                 sigma_buf, nsig, sigma_next, noise, coef, target, part);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
+extern "C" int oniris_sampler_mse_finish(const float* mse_ws, int num_steps, size_t n, float* mse, oniris_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ONIRIS_CHECK_ARG(mse_ws && mse && num_steps > 0 && n > 0, "sampler_mse_finish: bad arguments");
+  ONIRIS_KLAUNCH(sampler_mse_finish_kernel, dim3(2 * (unsigned)num_steps), dim3(256), 0, stream, mse_ws, (int)sampler_blocks(n),
+                 1.f / (float)n, mse);
+  ONIRIS_LAUNCH_CHECK();
+  return ONIRIS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // All Gating modules of a net in one launch (edm2/conv.py:113-127, eval): for layer l and frame slot n
 //   g = lo + (1 - lo) * hi * sigmoid(c_noise[n] * mult0 + off0 + log1p(n % T + nctx[l]) * mult1 + off1),

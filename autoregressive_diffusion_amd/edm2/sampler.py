@@ -69,10 +69,14 @@ class _GraphedDenoiser:
     # replay (the frame's last Euler evaluation, the one the reference updates the cache on, sampler.py:63) the shadow IS
     # the updated cache: no separate eager evaluation (4.2 ms against 1.4 ms for a replay at B = 1).  The caller's cache
     # keeps the old tensors alive for as long as the graph reads them.
-    def prepare(self, x0, t0):
+    # update_cache=False (a frame probed against a target keeps no evaluation's cache update, reference sampler.py:66): the
+    # graph is captured on the caller's cache itself with update_cache=False, like the graph of __call__ -- no shadow, nothing
+    # written beside the evaluation's own output.
+    def prepare(self, x0, t0, update_cache=True):
         self.x = x0.clone()
         self.t.fill_(t0)
         self.new_cache = None
+        self.update_cache = update_cache
 
     @staticmethod
     def _shadow(c):
@@ -107,9 +111,10 @@ class _GraphedDenoiser:
             pool, side = _graph_pool
             side.wait_stream(cur)
             g = torch.cuda.CUDAGraph()
-            shadow = self._shadow(self.cache)
+            update = self.update_cache
+            shadow = self._shadow(self.cache) if update else self.cache
             from .conv import DEFER_CACHE_SHIFT
-            DEFER_CACHE_SHIFT[0] = True
+            DEFER_CACHE_SHIFT[0] = update
             # capture_begin / capture_end by hand: the `torch.cuda.graph` context manager opens with a device
             # synchronisation, a gc.collect() and an empty_cache() -- with the previous frame's 31 replays still queued that
             # is where the host waited for the GPU, and the GPU then idled through the ~4 ms of host work of this capture
@@ -117,7 +122,7 @@ class _GraphedDenoiser:
                 with torch.cuda.stream(side):
                     g.capture_begin(pool=pool)
                     try:
-                        self.out, self.new_cache = self.net(self.x, self.t, self.cond, cache=shadow, update_cache=True,
+                        self.out, self.new_cache = self.net(self.x, self.t, self.cond, cache=shadow, update_cache=update,
                                                             just_2d=False, **self.kw)
                     finally:
                         g.capture_end()
@@ -150,47 +155,83 @@ class _GraphedDenoiser:
 _t_steps_cache = {}
 
 
-def _t_steps(num_steps, sigma_min, sigma_max, rho, dtype, device):
-    """The rho-schedule (reference sampler.py:40-44), evaluated on the device as there; kept per argument set together with
-    its host copy (the fused frame loop passes the sigmas as kernel arguments: reading them back every frame would wait for
-    the previous frame's evaluations)."""
-    key = (num_steps, float(sigma_min), float(sigma_max), float(rho), dtype, str(device))
+def _t_steps(num_steps, sigma_min, sigma_max, rho, dtype, device, S_churn=0, S_min=0, S_max=float("inf"), S_noise=1):
+    """The rho-schedule (reference sampler.py:40-44) and the churn table of every step (:56-60: t_hat = t_cur + gamma * t_cur,
+    coef = sqrt(t_hat^2 - t_cur^2) * S_noise), evaluated on the device with the reference's own expressions; kept per argument
+    set together with their host copies (the fused frame loop passes sigmas and coefficients as kernel arguments: reading them
+    back every frame would wait for the previous frame's evaluations).  Whether step k is churned is the reference's test
+    S_min <= t_cur <= S_max on the host copy.  Returns (t_steps, t_steps host, t_hat host, coef host, churned)."""
+    key = (num_steps, float(sigma_min), float(sigma_max), float(rho), dtype, str(device), float(S_churn), float(S_min),
+           float(S_max), float(S_noise))
     hit = _t_steps_cache.get(key)
     if hit is None:
         i = torch.arange(num_steps, dtype=dtype, device=device)
         t = (sigma_max ** (1 / rho) + i / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
         t = torch.cat([t, torch.zeros_like(t[:1])])
+        t_cur = t[:-1]
+        gamma = min(S_churn / num_steps, np.sqrt(2) - 1)
+        t_hat = t_cur + gamma * t_cur
+        coef = (t_hat ** 2 - t_cur ** 2).sqrt() * S_noise
+        ts = t.tolist()
+        churned = [bool(S_churn > 0 and S_min <= tc <= S_max) for tc in ts[:-1]]
         if len(_t_steps_cache) > 16:
             _t_steps_cache.clear()
-        hit = _t_steps_cache[key] = (t, t.tolist())
-    return hit[0]
+        hit = _t_steps_cache[key] = (t, ts, t_hat.tolist(), coef.tolist(), churned)
+    return hit
 
 
-def _fused_frame(net, graphed, cache, conditioning, t_steps, x0, B, num_steps):
-    """The frame loop of edm_sampler_with_mse for the common case (no churn, no target, fp32, CUDA; guidance through the pair
-    evaluation): same
-    arithmetic in the same order (reference sampler.py:56-76), but every evaluation is a graph replay whose x / sigma inputs
-    were written in place by the previous update kernel -- per evaluation ONE replay + ONE small launch instead of ~10 torch
-    launches (fill, mul, copy, clone, sub, div, mul, add ... on a 128 KB tensor, each ~5 us of a 1.6 ms evaluation)."""
+def _fused_frame(graphed, cache, sched, x0, num_steps, target=None, churn_noise=None):
+    """The frame loop of edm_sampler_with_mse (fp32, CUDA; guidance through the pair evaluation; any S_churn, target or not):
+    same arithmetic in the same order (reference sampler.py:53-83), but every evaluation is a graph replay whose x / sigma
+    inputs were written in place by the previous update kernel -- per evaluation ONE replay + ONE small launch instead of ~10
+    torch launches (fill, mul, copy, clone, sub, div, mul, add ... on a 128 KB tensor, each ~5 us of a 1.6 ms evaluation).
+    Churn: the noise of every churned step is drawn before the loop (the generator sees the draws of the tensor-expression
+    loop, in its order); step k's injection rides in the launch that forms step k - 1's x_next (step 0's: a launch of its own),
+    which also leaves t_hat[k] in the graph's sigma input.  target: the same launches leave block partials of the two squared
+    errors of every step; one launch reduces them and ONE copy brings the 2 * num_steps means to the host after the last step
+    (no .item() in the loop); no evaluation's cache update is kept (reference: update_cache=(... and target is None)), so
+    the graph is captured on the caller's cache with update_cache=False and nothing the evaluations read is written."""
     from .. import ops
-    ts = next((h[1] for h in _t_steps_cache.values() if h[0] is t_steps), None) or t_steps.tolist()
+    _, ts, t_hats, coefs, churned = sched
+    draws = {k: (churn_noise[k] if churn_noise is not None else torch.randn_like(x0)) for k in range(num_steps) if churned[k]}
+    draws = {k: v.to(torch.float32).expand_as(x0).contiguous() for k, v in draws.items()}
+    th = [t_hats[k] if churned[k] else ts[k] for k in range(num_steps)]      # the sigma of step k's Euler evaluation
+    probe = target is not None
+    tgt = target.expand_as(x0).contiguous() if probe else None
+    ws = ops.sampler_mse_ws(num_steps, x0) if probe else None
     xh = x0.contiguous().clone()
     d = torch.empty_like(xh)
-    graphed.prepare(xh, ts[0])
+    if churned[0]:
+        ops.sampler_step(2, xh, None, None, None, xh, 1.0, 0.0, noise=draws[0], coef=coefs[0])
+    graphed.prepare(xh, th[0], update_cache=not probe)
+
+    def last_update(k, mode, x_aux, x_out, t_a, dt):
+        """The launch that forms step k's final x_next: the step's squared errors and the injection of step k + 1 ride in it;
+        a step with neither is the plain update kernel, as on an unchurned frame."""
+        nz = draws.get(k + 1)
+        if nz is None and not probe:
+            ops.sampler_update(mode, xh, x_pred, d, x_aux, x_out, t_a, dt)
+        else:
+            ops.sampler_step(mode, xh, x_pred, d, x_aux, x_out, t_a, dt, graphed.t if nz is not None else None,
+                             th[k + 1] if nz is not None else 0.0, noise=nz, coef=coefs[k + 1] if nz is not None else 0.0,
+                             target=tgt, mse_ws=ws, step=k)
+
     for k in range(num_steps):
-        t_hat, t_next = ts[k], ts[k + 1]
-        if k == num_steps - 1:             # the evaluation whose cache update is kept (see _GraphedDenoiser.prepare)
-            x_pred = graphed.run()
-            ops.sampler_update(0, xh, x_pred, d, None, xh, t_hat, t_next - t_hat)
-            new = graphed.finish_cache()
-            cache.clear()                  # like the reference, the caller's dict itself carries the update (the replays that
-            cache.update(new)              # read the old tensors are ordered before anything queued from here on)
-            break
+        t_hat, t_next = th[k], ts[k + 1]
         x_pred = graphed.run()
+        if k == num_steps - 1:             # the evaluation whose cache update is kept (see _GraphedDenoiser.prepare)
+            last_update(k, 0, None, xh, t_hat, t_next - t_hat)
+            break
         ops.sampler_update(0, xh, x_pred, d, None, graphed.x, t_hat, t_next - t_hat, graphed.t, t_next)
         x_pred = graphed.run()
-        ops.sampler_update(1, xh, x_pred, d, graphed.x, graphed.x, t_next, t_next - t_hat)
-    return xh, cache
+        last_update(k, 1, graphed.x, graphed.x, t_next, t_next - t_hat)
+    if probe:
+        mse = ops.sampler_mse_finish(ws, xh.numel()).tolist()
+        return xh, [m[1] for m in mse], [m[0] for m in mse], cache
+    new = graphed.finish_cache()
+    cache.clear()                          # like the reference, the caller's dict itself carries the update (the replays that
+    cache.update(new)                      # read the old tensors are ordered before anything queued from here on)
+    return xh, [], [], cache
 
 
 @torch.no_grad()
@@ -230,20 +271,21 @@ def edm_sampler_with_mse(net, cache, target=None, gnet=None, conditioning=None, 
         ref, _ = net(x, t, conditioning, just_2d=True)
         return ref.lerp(Dx, guidance), cache
 
-    t_steps = _t_steps(num_steps, sigma_min, sigma_max, rho, dtype, device)
+    sched = _t_steps(num_steps, sigma_min, sigma_max, rho, dtype, device, S_churn, S_min, S_max, S_noise)
+    t_steps = sched[0]
     if noise is None:
         noise = torch.randn(B, 1, C, H, W, device=device)
     x_next = noise * t_steps[0]
     mse_values, mse_pred_values = [], []
-    if (graphed is not None and FUSED_FRAME and S_churn == 0 and target is None and x_next.dtype == torch.float32
-            and hasattr(unet, "prewarm_eval")):
-        x_next, cache = _fused_frame(net, graphed, cache, conditioning, t_steps, x_next, B, num_steps)
-        if was_training:
-            net.train()
-        return x_next, mse_values, mse_pred_values, cache
     if target is not None:
         target = target.to(dtype)
         x_next = x_next + target
+    # the replay loop: any S_churn, target or not (ONIRIS_SAMPLER_FUSED=0: the tensor expressions below for every argument set)
+    if graphed is not None and FUSED_FRAME and x_next.dtype == torch.float32 and hasattr(unet, "prewarm_eval"):
+        x_next, mse_values, mse_pred_values, cache = _fused_frame(graphed, cache, sched, x_next, num_steps, target, churn_noise)
+        if was_training:
+            net.train()
+        return x_next, mse_values, mse_pred_values, cache
     for k, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
         x_cur = x_next
         if S_churn > 0 and S_min <= t_cur <= S_max:

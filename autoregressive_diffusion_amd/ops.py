@@ -1286,6 +1286,37 @@ def sampler_update(mode, x_hat, x_pred, d_io, x_aux, x_out, t_a, dt, sigma_buf=N
                                     float(sigma_next), _stream()), "sampler_update")
 
 
+def sampler_mse_ws(num_steps, like):
+    """The workspace of a probed frame (`target=`): num_steps x 2 x blocks block partials for sampler_step, reduced by
+    sampler_mse_finish.  Not initialised: every row that is read has been written by that step's last update."""
+    return torch.empty(num_steps, 2, lib.oniris_sampler_ws_blocks(like.numel()), dtype=torch.float32, device=like.device)
+
+
+def sampler_step(mode, x_hat, x_pred, d_io, x_aux, x_out, t_a, dt, sigma_buf=None, sigma_next=0.0, noise=None, coef=0.0,
+                 target=None, mse_ws=None, step=0):
+    """sampler_update with the churn of the step that follows and the MSE probe in the same launch (reference
+    edm2/sampler.py:56-60, 78-83).  mode 2: no update, only the injection (step 0's churn).  noise: x_hat = x_out = x_next +
+    coef * noise.  target: the block partials of mean((x_pred - target)^2) and mean((x_next - target)^2) -- x_next before the
+    injection -- go to mse_ws[step]."""
+    _need_gpu(x_hat)
+    for t in (x_hat, x_pred, d_io, x_out, x_aux, noise, target):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x_hat.numel())
+    if target is not None:
+        assert (mse_ws.dtype == torch.float32 and mse_ws.is_contiguous() and 0 <= step < mse_ws.shape[0]
+                and tuple(mse_ws.shape[1:]) == (2, lib.oniris_sampler_ws_blocks(x_hat.numel())))
+    check(lib.oniris_sampler_step(mode, _p(x_hat), _p(x_pred), _p(d_io), _p(x_aux), _p(x_out), x_hat.numel(), float(t_a),
+                                  float(dt), _p(sigma_buf), sigma_buf.numel() if sigma_buf is not None else 0,
+                                  float(sigma_next), _p(noise), float(coef), _p(target), _p(mse_ws), int(step), _stream()),
+          "sampler_step")
+
+
+def sampler_mse_finish(mse_ws, n):
+    """(num_steps, 2) fp32 on the device: [k][0] = mean((x_pred - target)^2), [k][1] = mean((x_next - target)^2) of step k."""
+    mse = torch.empty(mse_ws.shape[0], 2, dtype=torch.float32, device=mse_ws.device)
+    check(lib.oniris_sampler_mse_finish(_p(mse_ws), mse_ws.shape[0], n, _p(mse), _stream()), "sampler_mse_finish")
+    return mse
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # fused magnitude-preserving glue (HBM-bound single-pass kernels, csrc/elementwise.hip)
 

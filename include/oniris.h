@@ -26,7 +26,8 @@ typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
 int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*), the wide encoder's oniris_vae_wide_down among them; guided sampling: OnirisConvArgs.ctx_rows (appended field),
-                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
+                                 * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*); the sampler's churn and target-MSE
+                                 * step (oniris_sampler_step, oniris_sampler_mse_finish, oniris_sampler_ws_blocks; oniris_sampler_update unchanged).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
                                  * oniris_gconv_bwd_fused(+ clip_flag, coef_own_scaled), oniris_qkv_norm_hd / _hd_bwd / oniris_rope_hd       */
 /* Measurement aid: arm a pair of HIP events (hipEvent_t created with timing); the next MFMA conv / weight-gradient /
@@ -164,6 +165,26 @@ int oniris_precond_out_guided(const void* F, const float* x, const float* sigma,
  *   sigma_buf (nsig floats, may be NULL): filled with sigma_next (the sigma input of the evaluation that follows).      */
 int oniris_sampler_update(int mode, float* x_hat, const float* x_pred, float* d_io, const float* x_aux, float* x_out, size_t n,
                           float t_a, float dt, float* sigma_buf, int nsig, float sigma_next, oniris_stream_t stream);
+/* oniris_sampler_step: the same update (same arguments, same arithmetic) with the loop's two side branches in the launch
+ *   (reference edm2/sampler.py:56-60 churn, :78-83 MSE against a target), so that a churned or probed frame needs no launch
+ *   other than graph replays and this one:
+ *   mode 2 (inject only): x_next = x_hat; x_pred (unless target is given), d_io, x_aux, t_a, dt are not used
+ *   target (n floats, may be NULL): the block partial sums of (x_pred - target)^2 and of (x_next - target)^2 -- x_next before
+ *     any injection -- go to mse_ws[step][0][block] and mse_ws[step][1][block]; mse_ws holds num_steps * 2 * blocks floats,
+ *     blocks = oniris_sampler_ws_blocks of n = min(ceil(n / 256), ONIRIS_SAMPLER_WS_BLOCKS); plain stores in a fixed order,
+ *     no atomics; rows of other steps are not touched, and with target == NULL mse_ws is not touched at all
+ *   noise (n floats, may be NULL): the churn of the step that follows, x_hat <- x_out <- x_next + coef * noise, the product
+ *     and the sum each rounded on its own (coef = the fp32 value of sqrt(t_hat^2 - t_cur^2) * S_noise).  noise == NULL: the
+ *     stores of oniris_sampler_update (mode 2: x_out <- x_hat when they are two buffers).
+ * oniris_sampler_mse_finish: one launch at the end of a frame: mse[step][0] = mean (x_pred - target)^2, mse[step][1] = mean
+ *   (x_next - target)^2 for step < num_steps (each step's partials added in index order, times 1 / n); 2 * num_steps floats
+ *   that the host reads with one copy.                                                                                    */
+#define ONIRIS_SAMPLER_WS_BLOCKS 1024
+int oniris_sampler_ws_blocks(size_t n);
+int oniris_sampler_step(int mode, float* x_hat, const float* x_pred, float* d_io, const float* x_aux, float* x_out, size_t n,
+                        float t_a, float dt, float* sigma_buf, int nsig, float sigma_next, const float* noise, float coef,
+                        const float* target, float* mse_ws, int step, oniris_stream_t stream);
+int oniris_sampler_mse_finish(const float* mse_ws, int num_steps, size_t n, float* mse, oniris_stream_t stream);
  /* oniris_embed_eval: the UNet's noise / label embedding (networks_edm2.py:204-216) in one fp32 launch: emb [N][cemb] bf16
  *   = mp_silu(mp_sum(MPConv_noise(MPFourier(c_noise)), MPConv_label(onehot(labels) * sqrt(L)), 1/3)); w_noise [cemb][cnoise],
  *   w_label [cemb][L] are the RAW fp32 parameters (normalised per row inside); labels / w_label NULL: no label term.      */
