@@ -86,6 +86,7 @@ _SIGS = {
     "oniris_profile_disarm": (c_int, []),
     "oniris_set_cu_reserve": (c_int, [c_int]),
     "oniris_set_ew_nt_bytes": (c_int64, [c_int64]),
+    "oniris_vae_wide_set_nb_max": (c_int, [c_int]),
     "oniris_frame_attn_bwd": (c_int, [c_void_p, c_void_p]),
     "oniris_frame_attn_qkv_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "oniris_frame_attn_qkv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),

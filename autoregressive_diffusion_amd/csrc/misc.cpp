@@ -56,6 +56,16 @@ extern "C" long long oniris_set_ew_nt_bytes(long long bytes) {      // returns t
   return old;
 }
 
+// The most 32-channel blocks of output channels a workgroup of the wide VAE's conv A takes (csrc/vae_wide_conv.h:
+// vae_wide_nb_conv_a): 4 by default, 2 puts blocks wider than 256 channels back on the 64-channel tile.  Same bits either way.
+static int g_vae_wide_nb_max = 4;
+int oniris_vae_wide_nb_max(void) { return g_vae_wide_nb_max; }
+extern "C" int oniris_vae_wide_set_nb_max(int nb) {                 // returns the previous value; nb: 2 or 4
+  const int old = g_vae_wide_nb_max;
+  g_vae_wide_nb_max = nb >= 4 ? 4 : 2;
+  return old;
+}
+
 // ---- dispatch census (common.h): (kernel handle, tag) -> launches
 int oniris_census_on = 0;
 static std::mutex g_census_mu;

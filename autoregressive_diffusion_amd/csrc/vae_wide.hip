@@ -10,7 +10,8 @@
 // The encoder at those widths runs the same ResBlock launches with a null emb (it passes t = None) behind oniris_vae_wide_down, the
 // compression stage as a GEMM over the strided fp32 or uint8 input (vae_wide_down_kernel of csrc/vae_wide_conv.h).
 // The convs take operands that are already activated: the cache is a plain copy of frames of S, and a conv of integers is exact.
-// Nothing here bounds the width: MAX_WIDTH of autoregressive_diffusion_amd/vae.py is the one constant that does.
+// Nothing here bounds the width: VAE.max_width of autoregressive_diffusion_amd/vae.py does (256; VAE512: 512, where conv A of a
+// block wider than 256 channels takes the 128-channel tile of vae_wide_nb_conv_a, csrc/vae_wide_conv.h).
 #include "oniris.h"
 #include "common.h"
 #include "vae_conv3.h"

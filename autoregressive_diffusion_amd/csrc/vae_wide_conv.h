@@ -303,10 +303,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
 // ---- host side (csrc/vae_wide.hip, csrc/vae_wide_train.hip)
 static inline bool vae_wide_c_ok(int c) { return c > 0 && c <= 65536; }
 static inline int vae_wide_nb(int CP) { return CP % 64 == 0 ? 2 : 1; }
+// Conv A (and its data gradient, the same launch) of a block wider than 256 channels whose CP is a multiple of 128: 128 output
+// channels per workgroup (NB = 4: the halo is staged half as often, 112 KB of LDS, one workgroup per CU), unless
+// oniris_vae_wide_set_nb_max says 2.  The K loop is the same, so the bits are those of NB = 2.  No block of up to 256 channels gets here.
+int oniris_vae_wide_nb_max(void);                                // csrc/misc.cpp
+static inline int vae_wide_nb_conv_a(int C, int CP) {
+  return C > 256 && CP % 128 == 0 && oniris_vae_wide_nb_max() >= 4 ? 4 : vae_wide_nb(CP);
+}
 
 template <int NB, int MODE>
 static int vae_wide_launch(const char* what, const VaeWideParams& p, dim3 grid, hipStream_t stream) {
-  constexpr int WP = NB == 2 ? 96 : 32, TAPS = MODE == VW_CONV_A ? 9 : 1;
+  constexpr int WP = (NB & 1) ? 32 * NB : 32 * NB + 32, TAPS = MODE == VW_CONV_A ? 9 : 1;
   const size_t bytes = ((size_t)DISC_HALO * DISC_HALO * DISC_APITCH + (size_t)TAPS * DISC_KC * WP) * sizeof(float);
   if (int rc = disc_raise_lds(vae_wide_kernel<NB, MODE>, bytes, what)) return rc;
   ONIRIS_KLAUNCH((vae_wide_kernel<NB, MODE>), grid, dim3(256), bytes, stream, p);
@@ -320,11 +327,13 @@ static int vae_wide_dispatch(const char* what, VaeWideParams& p, long long plane
   p.CinP = roundup(p.Cin, 2);
   p.CP = roundup(p.Cout, 32);
   p.tiles_x = cdiv(p.W, DISC_TILE); p.tiles_y = cdiv(p.H, DISC_TILE);
-  const int nb = vae_wide_nb(p.CP);
+  const int nb = MODE == VW_CONV_A ? vae_wide_nb_conv_a(p.Cout, p.CP) : vae_wide_nb(p.CP);
   p.nblk = p.CP / (32 * nb);
   const long long wgs = planes * p.tiles_x * p.tiles_y;
   ONIRIS_CHECK_ARG(wgs <= 0x7fffffffLL && (long long)p.nsub * p.nblk <= 65535, "%s: %lld tiles", what, wgs);
   const dim3 grid((unsigned)wgs, p.nsub * p.nblk);
+  if constexpr (MODE == VW_CONV_A)
+    if (nb == 4) return vae_wide_launch<4, MODE>(what, p, grid, stream);
   return nb == 2 ? vae_wide_launch<2, MODE>(what, p, grid, stream) : vae_wide_launch<1, MODE>(what, p, grid, stream);
 }
 

@@ -18,20 +18,23 @@
 
 #define VWT_PIX 256                                              // pixels per workgroup of the activation adjoint
 #define VWT_NC 4                                                 // channels per lane there: widths up to 256
+#define VWT_NC_WIDE 8                                            // and of the instantiation for widths up to 512
 
 // y = SiLU(z), z = n (1 + scale) + shift, n = x / d, d = sqrt(mean_c x^2 + 1e-4) (emb NULL: z = n):
 //   dz = dy SiLU'(z), dn = dz (1 + scale), dx = (dn - n mean_c(dn n)) / d (+ add), d scale = sum_pixels dz n, d shift = sum_pixels dz.
 // x, dy, add [B][npix][C]; dx [B][out_npix][C] (pixels npix.. are the caller's); part [gridDim.x][B][2C] or NULL.
+// NC: the channels a lane holds (C <= 64 NC); a lane's sums do not depend on it, so both instantiations give the same bits.
+template <int NC>
 __global__ __launch_bounds__(256) void vae_wide_act_bwd_kernel(const float* __restrict__ x, const float* __restrict__ emb,
                                                                const float* __restrict__ dy, const float* __restrict__ add,
                                                                float* __restrict__ dx, float* __restrict__ part, long long npix,
                                                                long long out_npix, int C, int B) {
-  __shared__ float red[3][2 * VWT_NC * 64];
+  __shared__ float red[3][2 * NC * 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y;
   const float* sc = emb ? emb + (size_t)b * 2 * C : nullptr;
-  float ds[VWT_NC], dh[VWT_NC];
+  float ds[NC], dh[NC];
 #pragma unroll
-  for (int i = 0; i < VWT_NC; ++i) ds[i] = dh[i] = 0.f;
+  for (int i = 0; i < NC; ++i) ds[i] = dh[i] = 0.f;
   for (int k = wave; k < VWT_PIX; k += 4) {
     const long long pp = (long long)blockIdx.x * VWT_PIX + k;
     if (pp >= npix) break;
@@ -42,9 +45,9 @@ __global__ __launch_bounds__(256) void vae_wide_act_bwd_kernel(const float* __re
       ss = fmaf(v, v, ss);
     }
     const float d = vae_rms(wave_sum(ss), C);
-    float dn[VWT_NC], xn[VWT_NC], m = 0.f;
+    float dn[NC], xn[NC], m = 0.f;
 #pragma unroll
-    for (int i = 0; i < VWT_NC; ++i) {
+    for (int i = 0; i < NC; ++i) {
       const int c = lane + 64 * i;
       dn[i] = xn[i] = 0.f;
       if (c < C) {
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(256) void vae_wide_act_bwd_kernel(const float* __re
     m = wave_sum(m) / (float)C;
     const size_t oo = ((size_t)b * out_npix + pp) * C;
 #pragma unroll
-    for (int i = 0; i < VWT_NC; ++i) {
+    for (int i = 0; i < NC; ++i) {
       const int c = lane + 64 * i;
       if (c < C) {
         float v = (dn[i] - xn[i] * m) / d;
@@ -76,22 +79,22 @@ __global__ __launch_bounds__(256) void vae_wide_act_bwd_kernel(const float* __re
   if (!part) return;
   if (wave > 0) {
 #pragma unroll
-    for (int i = 0; i < VWT_NC; ++i) {
+    for (int i = 0; i < NC; ++i) {
       red[wave - 1][i * 64 + lane] = ds[i];
-      red[wave - 1][(VWT_NC + i) * 64 + lane] = dh[i];
+      red[wave - 1][(NC + i) * 64 + lane] = dh[i];
     }
   }
   __syncthreads();
   if (wave == 0) {
     float* o = part + ((size_t)blockIdx.x * B + b) * 2 * C;
 #pragma unroll
-    for (int i = 0; i < VWT_NC; ++i) {
+    for (int i = 0; i < NC; ++i) {
       const int c = lane + 64 * i;
       if (c < C) {
         float s = ds[i], h = dh[i];
         for (int w = 0; w < 3; ++w) {
           s += red[w][i * 64 + lane];
-          h += red[w][(VWT_NC + i) * 64 + lane];
+          h += red[w][(NC + i) * 64 + lane];
         }
         o[c] = s;
         o[C + c] = h;

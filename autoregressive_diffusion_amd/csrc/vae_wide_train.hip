@@ -21,13 +21,17 @@
 extern "C" int oniris_vae_wide_act_bwd(const float* x, const float* emb, const float* dy, const float* add, float* dx, float* part,
                                        int B, int T, int H, int W, int C, int out_T, oniris_stream_t stream) {
   ONIRIS_CHECK_ARG(x && dy && dx && dx != x && dx != dy, "vae_wide_act_bwd: null pointer or dx aliases an operand");
-  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && H > 0 && W > 0 && C > 0 && C <= 64 * VWT_NC && out_T >= T,
-                   "vae_wide_act_bwd: bad sizes (B %d T %d H %d W %d C %d out_T %d; C <= %d)", B, T, H, W, C, out_T, 64 * VWT_NC);
+  ONIRIS_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && H > 0 && W > 0 && C > 0 && C <= 64 * VWT_NC_WIDE && out_T >= T,
+                   "vae_wide_act_bwd: bad sizes (B %d T %d H %d W %d C %d out_T %d; C <= %d)", B, T, H, W, C, out_T, 64 * VWT_NC_WIDE);
   ONIRIS_CHECK_ARG(!part || emb, "vae_wide_act_bwd: partials of d scale | d shift without emb");
   const long long npix = (long long)T * H * W, P = (npix + VWT_PIX - 1) / VWT_PIX;
   ONIRIS_CHECK_ARG(P <= 0x7fffffffLL, "vae_wide_act_bwd: %lld pixels", npix);
-  ONIRIS_KLAUNCH(vae_wide_act_bwd_kernel, dim3((unsigned)P, B), dim3(256), 0, (hipStream_t)stream, x, emb, dy, add, dx, part, npix,
-                 (long long)out_T * H * W, C, B);
+  if (C <= 64 * VWT_NC)
+    ONIRIS_KLAUNCH(vae_wide_act_bwd_kernel<VWT_NC>, dim3((unsigned)P, B), dim3(256), 0, (hipStream_t)stream, x, emb, dy, add, dx, part,
+                   npix, (long long)out_T * H * W, C, B);
+  else
+    ONIRIS_KLAUNCH(vae_wide_act_bwd_kernel<VWT_NC_WIDE>, dim3((unsigned)P, B), dim3(256), 0, (hipStream_t)stream, x, emb, dy, add, dx,
+                   part, npix, (long long)out_T * H * W, C, B);
   ONIRIS_LAUNCH_CHECK();
   return ONIRIS_OK;
 }

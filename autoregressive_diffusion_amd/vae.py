@@ -10,12 +10,16 @@ whole sequence gives (bit-identical here: csrc/vae*.hip and csrc/vae_conv3.h sum
 Activations are channels-last fp32 [B][T][H][W][C].  Decoder: per block one `up` launch, two per ResBlock, one `out` launch,
 plus one t-embedding launch per decode.  Encoder: per block one `down` launch (uint8 frames are normalised on load) and two per
 ResBlock (the decoder's kernels with a zero FiLM buffer), plus one `latents` launch per encode (include/oniris.h: oniris_vae_*).
-Blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip, on
+Blocks wider than MAX_NARROW = 64 channels (up to MAX_WIDTH = 256; up to 512 in `VAE512`) run on the fp32 MFMA tile kernels of csrc/vae_wide.hip, on
 both sides: the `up`, `out` and `down` stages as GEMMs and four launches per ResBlock (activation, conv A, activation, conv B; the
 encoder passes a null FiLM pointer), with the same cache entries.  An encoder `down` also takes the GEMM when it compresses more
 than 512 channels, whatever its output width.  A model that has such a block runs for inference only by default: the training
 path of `forward` raises NotImplementedError until `VAE.wide_training()` switches it on for that model (include/oniris.h:
-oniris_vae_wide_*, oniris_vae_wide_*_bwd).
+oniris_vae_wide_*, oniris_vae_wide_*_bwd).  `VAE512` is the same model for block widths up to 512 -- the full-size Counter-Strike VAE,
+channels=[3, 32, 128, 512, 8] -- with the training path on as constructed; a model of up to 256 channels runs the same launches
+under either class.  Above 256 channels conv A takes 128 output channels per workgroup where the padded width is a multiple of 128
+(11.6 % faster at 512 channels than the 64-channel tile, same bits: profiles/vae_512.txt) and a weight-gradient launch keeps its partial slabs within 64 MiB, down to a
+single slab that is the result (vae_train._nslab).
 
 `forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
 enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
@@ -355,15 +359,19 @@ class VAE(BetterModule):
     NotImplementedError here.  Blocks of up to 64 channels run on the register-tile kernels (csrc/vae.hip, csrc/vae_encoder.hip),
     wider ones on the fp32 MFMA tile kernels (csrc/vae_wide.hip), encoder and decoder alike; a model may mix them.  A model
     with a width above 64 runs for inference only unless `wide_training()` was called on it: until then the training path of
-    `forward` raises NotImplementedError (512 channels, the full-size Counter-Strike VAE, are out of scope)."""
+    `forward` raises NotImplementedError.  512 channels, the full-size Counter-Strike VAE, are refused here and run through
+    `VAE512`, the same model with max_width = 512."""
+
+    max_width = MAX_WIDTH               # the widest block the constructor accepts (VAE512: 512)
+    _wide_training_default = False      # the training path of a model with a wide block, as constructed (VAE512: on)
 
     def __init__(self, channels, n_res_blocks, time_compressions=[1, 2, 2], spatial_compressions=[1, 2, 2], mean=None, std=None):
         super().__init__()
         if len(channels) - 1 != len(time_compressions) or len(channels) - 1 != len(spatial_compressions) or len(channels) < 2:
             raise ValueError("VAE: len(channels) - 1 must equal the number of time and spatial compressions")
         widths = list(channels[::-1][:-1])
-        if max(widths) > MAX_WIDTH or min(widths) < 1:
-            raise NotImplementedError(f"VAE decoder: block widths {widths}: the HIP kernels take 1..{MAX_WIDTH} channels")
+        if max(widths) > self.max_width or min(widths) < 1:
+            raise NotImplementedError(f"VAE decoder: block widths {widths}: the HIP kernels take 1..{self.max_width} channels")
         if any(int(c) not in (1, 2) for c in list(time_compressions) + list(spatial_compressions)):
             raise NotImplementedError(f"VAE decoder: compressions {list(time_compressions)} / {list(spatial_compressions)}: "
                                       "the HIP kernels take 1 or 2")
@@ -372,7 +380,7 @@ class VAE(BetterModule):
                                       f"on the narrow kernels, which take 1..{MAX_NARROW} channels")
         self.latent_channels = channels[-1]
         self._wide = max(widths) if max(widths) > MAX_NARROW else 0
-        self._wide_training = False
+        self._wide_training = self._wide_training_default
         self.encoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="encoder")
         self.decoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="decoder")
         self.time_compression = np.prod(time_compressions)
@@ -387,7 +395,7 @@ class VAE(BetterModule):
     def wide_training(self, enabled=True):
         """Switch the training path of `forward` on (or off again) for a model with a block wider than MAX_NARROW: the backward on
         the fp32 MFMA kernels of csrc/vae_wide_train.hip (vae_train.py).  Off by default, so that a wide model refuses to train as
-        it always has until asked: `VAE.from_pretrained(path).to("cuda").wide_training()`.  A plain attribute: copy.deepcopy keeps
+        it always has until asked: `VAE.from_pretrained(path).to("cuda").wide_training()` (VAE512 is constructed with it on).  A plain attribute: copy.deepcopy keeps
         it, state_dict and kwargs do not hold it.  A model without a wide block trains either way, on the same kernels.  Returns
         self."""
         self._wide_training = bool(enabled)
@@ -663,7 +671,7 @@ class VAE(BetterModule):
         s = _stream()
         zeros = pk["zeros"].get(B)
         if zeros is None:                                    # the FiLM scale | shift of a ResBlock without t: zero
-            zeros = pk["zeros"][B] = torch.zeros(B * 2 * MAX_WIDTH, dtype=torch.float32, device=dev)
+            zeros = pk["zeros"][B] = torch.zeros(B * 2 * max(MAX_WIDTH, self._wide), dtype=torch.float32, device=dev)
         cache = {} if cache is None else cache
         new_cache = {}
         for i, bk in enumerate(pk["blocks"]):
@@ -728,3 +736,20 @@ class VAE(BetterModule):
         formula cs_train.py:102 applies by hand and the inverse of the affine in latents_to_frames.  (The reference's own method,
         vae.py:264-284, does not run: it unpacks four values from encode, adds std and returns nothing.)"""
         return self.encode_frames(frames)[0]
+
+
+class VAE512(VAE):
+    """`VAE` for block widths up to 512 channels: the full-size Counter-Strike VAE, channels=[3, 32, 128, 512, 8] with
+    n_res_blocks=5, time_compressions=[1, 2, 2, 1] and spatial_compressions=[1, 2, 2, 2] (cs_vae_train.py:34-39).  The same
+    constructor, `kwargs`, state_dict keys, checkpoint format, cache keys, methods and ValueErrors: `from
+    autoregressive_diffusion_amd.vae import VAE512 as VAE` is the whole change on the user's side, and
+    `VAE512.from_pretrained(path)` loads what `VAE` or the reference wrote (and `VAE` what this class wrote, up to 256 channels).
+    Two differences: a width above 512 (not 256) raises NotImplementedError, and the training path of `forward` is on as
+    constructed; `wide_training(False)` still turns it off.  More than 64 latent channels and compressions other than 1 or 2 are
+    refused as in `VAE`.  A model whose widest block has at most 256 channels runs the launches of `VAE(...).wide_training()`,
+    bit for bit.  The kernels are those of csrc/vae_wide.hip and csrc/vae_wide_train.hip, which never bounded the width; what a
+    block above 256 channels changes is the weight-gradient workspace (vae_train._nslab) and the activation adjoint's
+    instantiation (csrc/vae_wide_train.h)."""
+
+    max_width = 512
+    _wide_training_default = True

@@ -25,9 +25,20 @@ _SLAB_BYTES = 64 << 20          # the most memory one launch's partial slabs may
 _area_cache = {}
 
 
-def _nslab(work, size):
-    """Partial slabs of `size` floats for `work` work items: one per item up to 1024, fewer when the slabs are large."""
+def _nslab(work, size, width=0):
+    """Partial slabs of `size` floats for `work` work items: one per item up to 1024, fewer when the slabs are large, and never
+    fewer than 64 for a stage of up to 256 channels (`width`: the stage's widest channel count).  Above 256 channels the floor
+    is dropped, as discriminator._nslab27 does: one launch's slabs stay within _SLAB_BYTES, or it is a single slab where even
+    one exceeds that (conv A at 512 channels and g = 4: 302 MB a slab).  Nothing is lost: a slab's grid alone, (time tap, frame,
+    32-channel block) pairs by 32-channel blocks, is 162 workgroups at 257 channels and g = 1 and 8192 at 512 and g = 4."""
+    if width > V.MAX_WIDTH:
+        return int(max(1, min(work, 1024, _SLAB_BYTES // (4 * size))))
     return int(max(1, min(work, 1024, max(64, _SLAB_BYTES // (4 * size)))))
+
+
+def _wide_slab_sum(slab, n, width):
+    """_slab_sum; above 256 channels a single slab is the result and no launch is issued."""
+    return slab[0] if slab.shape[0] == 1 and width > V.MAX_WIDTH else _slab_sum(slab, n)
 
 
 def _cached(pk, key, make):
@@ -94,11 +105,12 @@ def _wide_lin_dw(x, vx, dy, vy, grid, nslab=None):
     npx, npy = vx[1] * vx[2] ** 2, vy[1] * vy[2] ** 2
     nw = npx * npy * vx[0] * vy[0]
     n = nw + npy * vy[0]
-    nslab = _nslab(B * T * -(-H // 16) * -(-W // 16), n) if nslab is None else nslab
+    width = max(vx[0], vy[0])
+    nslab = _nslab(B * T * -(-H // 16) * -(-W // 16), n, width) if nslab is None else nslab
     slab = torch.empty(nslab, n, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib.oniris_vae_wide_lin_wgrad_bwd(_p(x), *x.stride(), *vx, _p(dy), *vy, B, T, H, W, _p(slab), nslab, _stream()),
                "vae_wide_lin_wgrad_bwd")
-    r = _slab_sum(slab, n)
+    r = _wide_slab_sum(slab, n, width)
     return r[:nw].view(npx, npy, vx[0], vy[0]), r[nw:].view(npy, vy[0])
 
 
@@ -317,11 +329,11 @@ def _wide_conv3_dw(xin, dA, B, T, H, W, C, g, causal, nslab=None):
     """The summed slab of oniris_vae_wide_conv3_wgrad_bwd -> (the weights, flat; the biases, flat)."""
     nw = (2 * g * g if causal else 1) * 9 * C * C
     n = nw + g * C
-    nslab = _nslab(B * (T // g) * -(-H // 16) * -(-W // 16), n) if nslab is None else nslab
+    nslab = _nslab(B * (T // g) * -(-H // 16) * -(-W // 16), n, C) if nslab is None else nslab
     slab = torch.empty(nslab, n, dtype=torch.float32, device=xin.device)
     _lib.check(_lib.lib.oniris_vae_wide_conv3_wgrad_bwd(_p(xin), xin.shape[1], _p(dA), dA.shape[1], B, T, H, W, C, g, int(causal), _p(slab),
                                                         nslab, _stream()), "vae_wide_conv3_wgrad_bwd")
-    r = _slab_sum(slab, n)
+    r = _wide_slab_sum(slab, n, C)
     return r[:nw], r[nw:]
 
 

@@ -47,6 +47,11 @@ int oniris_set_cu_reserve(int k);
  * launch; returns the previous threshold.  The results do not depend on it (same arithmetic, other cache policy): the test
  * suite sets 0 to put every non-temporal instantiation under the oracle on oracle-sized tensors.                       */
 long long oniris_set_ew_nt_bytes(long long bytes);
+/* The widest tile of output channels of the wide VAE's conv A (oniris_vae_wide_conv_a, and its data gradient, the same launch), in
+ * 32-channel blocks: 4 (the default) lets a block wider than 256 channels whose padded width is a multiple of 128 take 128 output
+ * channels per workgroup, 2 keeps it on the 64-channel tile of every other width.  Process-wide, host-side, takes effect at the
+ * next launch; returns the previous value.  The results do not depend on it: the K loop and so every sum's order are the same. */
+int oniris_vae_wide_set_nb_max(int nb);
 /* Dispatch census (diagnostic).  oniris_census(1) clears the list and starts noting every kernel launch of this library;
  * oniris_census(0) stops.  oniris_census_read writes one line per distinct launch kind, "<launches>\t<kernel instantiation>
  * [ [tag]]\n" (demangled name with its template arguments; the tag marks variants picked at run time inside one
