@@ -57,42 +57,12 @@ __device__ __forceinline__ void vae_wide_mfma_taps(f32x16 (&acc)[2][NB], const f
   }
 }
 
+// The store loops of VW_UP and VW_OUT for the accumulators of tile (y0, x0) of plane pl = n T + tau, sub-position `sub`, output
+// channels n0 .. n0 + 32 NB - 1: + bias, then `up`'s rearranged position, or `out`'s area residual (read from p.x), split and
+// frames.  Shared with the bf16-operand kernel of csrc/vae_wide_bf16.h, whose accumulators have the same layout.
 template <int NB, int MODE>
-__global__ __launch_bounds__(256) void vae_wide_kernel(VaeWideParams p) {
-  constexpr int TAPS = MODE == VW_CONV_A ? 9 : 1;
-  extern __shared__ __attribute__((aligned(16))) float disc_lds[];
-  float* hl = disc_lds;                                          // [324][17]
-  float* wl = disc_lds + DISC_HALO * DISC_HALO * DISC_APITCH;    // [TAPS][16][WP]
-  const int tiles = p.tiles_x * p.tiles_y;
-  const int tile = blockIdx.x % tiles, pl = blockIdx.x / tiles;  // conv A: pl = n (T / g) + tau; else pl = n T + t
-  const int y0 = (tile / p.tiles_x) * DISC_TILE, x0 = (tile % p.tiles_x) * DISC_TILE;
-  const int sub = blockIdx.y / p.nblk, n0 = (blockIdx.y % p.nblk) * 32 * NB;
-  const int CoutP = p.nsub * p.CP;
-  const int ntau = MODE == VW_CONV_A ? p.T / p.g : 1;
-  const int n = MODE == VW_CONV_A ? pl / ntau : pl / p.T;
-  const int tau = MODE == VW_CONV_A ? pl % ntau : pl % p.T;
-  const int KT = MODE == VW_CONV_A ? 2 * p.g : 1;
-  const int plane0 = MODE == VW_CONV_A ? n * (p.g + p.T) + tau * p.g : pl;
-
-  f32x16 acc[2][NB];
-  disc_zero(acc);
-  for (int kt = 0; kt < KT; ++kt) {
-    for (int c0 = 0; c0 < p.CinP; c0 += DISC_KC) {
-      const int kc = min(DISC_KC, p.CinP - c0);
-      __syncthreads();
-      if (p.Cin % 32 == 0) disc_stage_halo_vec<DISC_APITCH, DISC_KC>(hl, p.x, nullptr, nullptr, plane0 + kt, y0, x0, p.H, p.W, p.Cin, c0);
-      else disc_stage_halo<DISC_APITCH>(hl, p.x, nullptr, nullptr, plane0 + kt, y0, x0, p.H, p.W, p.Cin, c0, kc);
-      disc_stage_weights<NB>(wl, p.w, kt * TAPS, TAPS, p.CinP, CoutP, c0, kc, sub * p.CP + n0);
-      __syncthreads();
-      vae_wide_mfma_taps<NB, TAPS>(acc, hl, wl, kc);
-    }
-  }
-
-  if (MODE == VW_CONV_A) {
-    disc_epilogue<NB>(acc, disc_lds, n * p.T + tau * p.g + sub, p.H, p.W, y0, x0, n0, p.Cout, p.bias + sub * p.CP, nullptr, 1.f, p.out,
-                      nullptr);
-    return;
-  }
+__device__ __forceinline__ void vae_wide_store(const f32x16 (&acc)[2][NB], const VaeWideParams& p, int pl, int n, int tau, int sub,
+                                               int n0, int y0, int x0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31;
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -138,6 +108,45 @@ __global__ __launch_bounds__(256) void vae_wide_kernel(VaeWideParams p) {
         }
       }
   }
+}
+
+template <int NB, int MODE>
+__global__ __launch_bounds__(256) void vae_wide_kernel(VaeWideParams p) {
+  constexpr int TAPS = MODE == VW_CONV_A ? 9 : 1;
+  extern __shared__ __attribute__((aligned(16))) float disc_lds[];
+  float* hl = disc_lds;                                          // [324][17]
+  float* wl = disc_lds + DISC_HALO * DISC_HALO * DISC_APITCH;    // [TAPS][16][WP]
+  const int tiles = p.tiles_x * p.tiles_y;
+  const int tile = blockIdx.x % tiles, pl = blockIdx.x / tiles;  // conv A: pl = n (T / g) + tau; else pl = n T + t
+  const int y0 = (tile / p.tiles_x) * DISC_TILE, x0 = (tile % p.tiles_x) * DISC_TILE;
+  const int sub = blockIdx.y / p.nblk, n0 = (blockIdx.y % p.nblk) * 32 * NB;
+  const int CoutP = p.nsub * p.CP;
+  const int ntau = MODE == VW_CONV_A ? p.T / p.g : 1;
+  const int n = MODE == VW_CONV_A ? pl / ntau : pl / p.T;
+  const int tau = MODE == VW_CONV_A ? pl % ntau : pl % p.T;
+  const int KT = MODE == VW_CONV_A ? 2 * p.g : 1;
+  const int plane0 = MODE == VW_CONV_A ? n * (p.g + p.T) + tau * p.g : pl;
+
+  f32x16 acc[2][NB];
+  disc_zero(acc);
+  for (int kt = 0; kt < KT; ++kt) {
+    for (int c0 = 0; c0 < p.CinP; c0 += DISC_KC) {
+      const int kc = min(DISC_KC, p.CinP - c0);
+      __syncthreads();
+      if (p.Cin % 32 == 0) disc_stage_halo_vec<DISC_APITCH, DISC_KC>(hl, p.x, nullptr, nullptr, plane0 + kt, y0, x0, p.H, p.W, p.Cin, c0);
+      else disc_stage_halo<DISC_APITCH>(hl, p.x, nullptr, nullptr, plane0 + kt, y0, x0, p.H, p.W, p.Cin, c0, kc);
+      disc_stage_weights<NB>(wl, p.w, kt * TAPS, TAPS, p.CinP, CoutP, c0, kc, sub * p.CP + n0);
+      __syncthreads();
+      vae_wide_mfma_taps<NB, TAPS>(acc, hl, wl, kc);
+    }
+  }
+
+  if (MODE == VW_CONV_A) {
+    disc_epilogue<NB>(acc, disc_lds, n * p.T + tau * p.g + sub, p.H, p.W, y0, x0, n0, p.Cout, p.bias + sub * p.CP, nullptr, 1.f, p.out,
+                      nullptr);
+    return;
+  }
+  vae_wide_store<NB, MODE>(acc, p, pl, n, tau, sub, n0, y0, x0);
 }
 
 // ---- down (reference: edm2/vae/vae.py :109-122, :136-141, :157-161).  Output pixel (t, y, x) at sub-position pos = (tq sc + hq) sc +
@@ -235,6 +244,47 @@ __device__ __forceinline__ float vae_wide_area(const TIN* xp, int s0, int s1, co
   return area;
 }
 
+// The epilogue of `down` for the accumulators of tile (y0, x0) of output plane pl, output channels n0 .. n0 + 32 NB - 1 (xn: the
+// sample's input at plane t tc): + bias + the area residual.  lds: the workgroup's LDS, [16][256] floats of it, free after the
+// barrier this begins with.  Shared with the bf16-operand kernel of csrc/vae_wide_bf16.h.
+template <int NB, typename TIN, bool VEC, bool RES>
+__device__ __forceinline__ void vae_wide_down_store(const f32x16 (&acc)[2][NB], const VaeWideDownParams& p, float* lds, const TIN* xn,
+                                                    int pl, int n0, int y0, int x0, long long ysh, long long xsw) {
+  // the area residual: per lane the window of its output channel at its 32 pixels, each summed in ascending k; a rolled loop per
+  // 16 pixels leaves the sums in the lane's own slots of the (now free) stage, and the unrolled store loop picks them up
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31;
+  const long long K = (long long)(p.tc * p.scm * p.scm) * p.Cin;
+  float* al = lds;                                               // [16][256]
+  __syncthreads();
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    const int co = n0 + nb * 32 + j;
+    if (co >= p.Cout) continue;
+    const float bv = p.bias[co];
+    const int s0 = (int)((co * K) / p.Cout), s1 = (int)(((co + 1) * K + p.Cout - 1) / p.Cout);
+    const float len = (float)(s1 - s0);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll 1
+      for (int r = 0; r < 16; ++r) {
+        const int i = mfma_row(r, lane);
+        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
+        float area = 0.f;
+        if (RES && y < p.Ho && xx < p.Wo) area = vae_wide_area<TIN, VEC>(xn + y * ysh + xx * xsw, s0, s1, p);
+        al[r * 256 + threadIdx.x] = area;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = mfma_row(r, lane);
+        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
+        if (y >= p.Ho || xx >= p.Wo) continue;
+        const float v = acc[mb][nb][r] + bv;
+        p.out[(((size_t)pl * p.Ho + y) * p.Wo + xx) * p.Cout + co] = RES ? v + al[r * 256 + threadIdx.x] / len : v;
+      }
+    }
+  }
+}
+
 // RES = false: out = conv + bias alone, the adjoint of `up` (csrc/vae_wide_train.hip: the sub-positions of d up gathered through W^T).
 template <int NB, typename TIN, bool VEC, bool RES = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void vae_wide_down_kernel(VaeWideDownParams p) {
@@ -264,40 +314,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void v
       vae_wide_mfma_taps<NB, 1>(acc, hl, wl, kc);
     }
   }
-
-  // the area residual: per lane the window of its output channel at its 32 pixels, each summed in ascending k; a rolled loop per
-  // 16 pixels leaves the sums in the lane's own slots of the (now free) stage, and the unrolled store loop picks them up
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31;
-  const long long K = (long long)P * p.Cin;
-  float* al = disc_lds;                                          // [16][256]
-  __syncthreads();
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const int co = n0 + nb * 32 + j;
-    if (co >= p.Cout) continue;
-    const float bv = p.bias[co];
-    const int s0 = (int)((co * K) / p.Cout), s1 = (int)(((co + 1) * K + p.Cout - 1) / p.Cout);
-    const float len = (float)(s1 - s0);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll 1
-      for (int r = 0; r < 16; ++r) {
-        const int i = mfma_row(r, lane);
-        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
-        float area = 0.f;
-        if (RES && y < p.Ho && xx < p.Wo) area = vae_wide_area<TIN, VEC>(xn + y * ysh + xx * xsw, s0, s1, p);
-        al[r * 256 + threadIdx.x] = area;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = mfma_row(r, lane);
-        const int y = y0 + 4 * wave + 2 * mb + (i >> 4), xx = x0 + (i & 15);
-        if (y >= p.Ho || xx >= p.Wo) continue;
-        const float v = acc[mb][nb][r] + bv;
-        p.out[(((size_t)pl * p.Ho + y) * p.Wo + xx) * p.Cout + co] = RES ? v + al[r * 256 + threadIdx.x] / len : v;
-      }
-    }
-  }
+  vae_wide_down_store<NB, TIN, VEC, RES>(acc, p, disc_lds, xn, pl, n0, y0, x0, ysh, xsw);
 }
 
 // ---- host side (csrc/vae_wide.hip, csrc/vae_wide_train.hip)

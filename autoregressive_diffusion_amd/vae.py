@@ -21,6 +21,14 @@ under either class.  Above 256 channels conv A takes 128 output channels per wor
 (11.6 % faster at 512 channels than the 64-channel tile, same bits: profiles/vae_512.txt) and a weight-gradient launch keeps its partial slabs within 64 MiB, down to a
 single slab that is the result (vae_train._nslab).
 
+`VAE.bf16_inference()` switches the wide blocks of one model to bf16 MFMA operands for inference (csrc/vae_wide_bf16.hip,
+include/oniris.h: oniris_vae_wide_*_bf16): the weights are rounded to bf16 (nearest even) when packed and the activated input of
+conv A, conv B, `up`, `down` and `out` when a kernel stages it, each exactly once (every MFMA launch of the VAE: the GEMM `down` of a
+narrow block that compresses more than MAX_DOWN_K channels among them); accumulation, biases, residuals (read from the unrounded
+tensor), activations, caches and every tensor in HBM stay fp32, the register-tile kernels of the narrow blocks are untouched, and
+the training path ignores the switch.  Off as constructed: the fp32 path keeps its bits and is the verification path (what `Precond(use_fp16=False)`
+is for the UNet, with the default the other way round).
+
 `forward` (encode, mix with noise, decode: what the reference's VAE training loops call) trains: in training mode with grad
 enabled its outputs carry a grad_fn and `.backward()` fills `.grad` of every trainable parameter through the kernels of
 csrc/vae_train.hip (vae_train.py).  Nothing here has a CPU path: use the reference's `edm2.vae` for that.
@@ -103,37 +111,55 @@ def _pack_res(rb, C, g, f32):
     return dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
 
 
-def _pack_res_wide(rb, C, g, f32):
+def _cinp(c, bf16):
+    """c input channels padded as the packed weights hold them: to even for the fp32 kernels (csrc/vae_wide_conv.h), to a multiple
+    of 16, the K step of the MFMA, for the bf16 ones (csrc/vae_wide_bf16.h)."""
+    return -(-c // 16) * 16 if bf16 else c + (c & 1)
+
+
+def _wdtype(f32, bf16):
+    """The tensor options of a wide block's packed weights: f32, or the same device in bf16.  A copy into such a tensor rounds to
+    nearest even, as `weight.to(torch.bfloat16)` does -- the one rounding of the weights (csrc/vae_wide_bf16.h)."""
+    return dict(f32, dtype=torch.bfloat16) if bf16 else f32
+
+
+def _pack_res_wide(rb, C, g, f32, bf16=False):
     """The two convolutions of a ResBlock wider than MAX_NARROW in the layouts of csrc/vae_wide_conv.h: output channels
-    [sub][CP] (CP = C rounded up to a multiple of 32), input channels rounded up to even, zero where padded."""
-    CP, CinP = _cp(C), C + (C & 1)
+    [sub][CP] (CP = C rounded up to a multiple of 32), input channels rounded up to even, zero where padded.  bf16: the weights
+    as bf16 in the same layouts with the input channels rounded up to a multiple of 16 (csrc/vae_wide_bf16.h), the biases fp32,
+    and bf16=True in the dict, which is what makes wide_conv_a / wide_conv_b pick the bf16 entry points."""
+    CP, CinP, wt = _cp(C), _cinp(C, bf16), _wdtype(f32, bf16)
     w = rb.conv3d0.conv3d.weight.detach().to(**f32)                   # (C g, C, 2g, 3, 3), co = c g + gl
-    wa = torch.zeros(2 * g, 3, 3, CinP, g, CP, **f32)
+    wa = torch.zeros(2 * g, 3, 3, CinP, g, CP, **wt)
     wa[:, :, :, :C, :, :C] = w.reshape(C, g, C, 2 * g, 3, 3).permute(3, 4, 5, 2, 1, 0)   # kt, ky, kx, ci, gl, c
     ba = torch.zeros(g, CP, **f32)
     ba[:, :C] = rb.conv3d0.conv3d.bias.detach().to(**f32).reshape(C, g).t()
-    wb = torch.zeros(3, 3, CinP, CP, **f32)
+    wb = torch.zeros(3, 3, CinP, CP, **wt)
     wb[:, :, :C, :C] = rb.conv3d1.weight.detach().to(**f32)[:, :, 0].permute(2, 3, 1, 0)   # ky, kx, ci, co
     bb = torch.zeros(CP, **f32)
     bb[:C] = rb.conv3d1.bias.detach().to(**f32)
-    return dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
+    pk = dict(wa=wa.contiguous(), ba=ba.contiguous(), wb=wb.contiguous(), bb=bb)
+    if bf16:
+        pk["bf16"] = True
+    return pk
 
 
-def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32):
-    """A 1x1 conv Cin -> nsub Cout (conv channel sub Cout + c) as w [CinP][nsub CP], bias [nsub][CP] (csrc/vae_wide_conv.h)."""
-    CP, CinP = _cp(Cout), Cin + (Cin & 1)
-    w = torch.zeros(CinP, nsub, CP, **f32)
+def _pack_lin_wide(weight, bias, Cin, Cout, nsub, f32, bf16=False):
+    """A 1x1 conv Cin -> nsub Cout (conv channel sub Cout + c) as w [CinP][nsub CP], bias [nsub][CP] (csrc/vae_wide_conv.h);
+    bf16: w as bf16 with CinP a multiple of 16 (csrc/vae_wide_bf16.h)."""
+    CP, CinP = _cp(Cout), _cinp(Cin, bf16)
+    w = torch.zeros(CinP, nsub, CP, **_wdtype(f32, bf16))
     w[:Cin, :, :Cout] = weight.detach().to(**f32).reshape(nsub, Cout, Cin).permute(2, 0, 1)
     b = torch.zeros(nsub, CP, **f32)
     b[:, :Cout] = bias.detach().to(**f32).reshape(nsub, Cout)
     return w.contiguous(), b.contiguous()
 
 
-def _pack_down_wide(weight, bias, Cin, Cout, npos, f32):
+def _pack_down_wide(weight, bias, Cin, Cout, npos, f32, bf16=False):
     """The compression 1x1 conv npos Cin -> Cout (rearranged channel k = pos Cin + c) as w [npos][CinP][CP], bias [CP]
-    (vae_wide_down_kernel of csrc/vae_wide_conv.h)."""
-    CP, CinP = _cp(Cout), Cin + (Cin & 1)
-    w = torch.zeros(npos, CinP, CP, **f32)
+    (vae_wide_down_kernel of csrc/vae_wide_conv.h); bf16: w as bf16 with CinP a multiple of 16 (csrc/vae_wide_bf16.h)."""
+    CP, CinP = _cp(Cout), _cinp(Cin, bf16)
+    w = torch.zeros(npos, CinP, CP, **_wdtype(f32, bf16))
     w[:, :Cin, :Cout] = weight.detach().to(**f32).reshape(Cout, npos, Cin).permute(1, 2, 0)
     b = torch.zeros(CP, **f32)
     b[:Cout] = bias.detach().to(**f32)
@@ -142,7 +168,8 @@ def _pack_down_wide(weight, bias, Cin, Cout, npos, f32):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # launches: thin wrappers on channels-last fp32 tensors (B, T, H, W, C) of the GPU, one per stage (temb, up, res, out, down: each
-# picks the narrow or the wide entry point from the packed block it is given) and one per entry point of a ResBlock.  bk: a packed
+# picks the narrow or the wide entry point from the packed block it is given, and the wide one's bf16 form where the packed block
+# or ResBlock says bf16=True) and one per entry point of a ResBlock.  bk: a packed
 # block (VAE._pack, VAE._pack_encoder), rb: one of its packed ResBlocks, pk: the decoder's pack, dims: the coarse grid (B, T, H, W),
 # strides: element strides (b, t, h, w, c) of an operand in any layout, s: the stream.  Each allocates what it writes and returns it.
 
@@ -162,6 +189,13 @@ def temb(pk, width, t, s):
     return emb
 
 
+def _wide_entry(stage, pk):
+    """(entry point, its name for error messages) of a wide stage: oniris_vae_wide_<stage>, or oniris_vae_wide_<stage>_bf16 where
+    the packed block or ResBlock pk holds bf16 weights."""
+    what = f"vae_wide_{stage}_bf16" if pk.get("bf16") else f"vae_wide_{stage}"
+    return getattr(_lib.lib, "oniris_" + what), what
+
+
 def up(x, strides, dims, bk, s, scale=None, shift=None):
     """oniris_vae_up: x over `dims` by `strides` (times scale plus shift per channel) -> (B, T tc, H sc, W sc, C); or
     oniris_vae_wide_up where bk["wide"]: x is then contiguous (`strides` is not read) and scale / shift are not taken."""
@@ -170,7 +204,8 @@ def up(x, strides, dims, bk, s, scale=None, shift=None):
     y = _new(x, B, T * tc, H * sc, W * sc, C)
     if bk["wide"]:
         assert scale is None and shift is None and x.is_contiguous()
-        _lib.check(_lib.lib.oniris_vae_wide_up(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(y), B, T, H, W, C, tc, sc, s), "vae_wide_up")
+        entry, what = _wide_entry("up", bk)
+        _lib.check(entry(_p(x), _p(bk["wu"]), _p(bk["bu"]), _p(y), B, T, H, W, C, tc, sc, s), what)
     else:
         _lib.check(_lib.lib.oniris_vae_up(_p(x), *strides, B, T, H, W, C, _p(scale), _p(shift), _p(bk["wu"]), _p(bk["bu"]), tc, sc,
                                           _p(y), s), "vae_up")
@@ -205,18 +240,21 @@ def wide_act(x, s, emb=None, cin=None, g=0, out=None):
 
 
 def wide_conv_a(seq, rb, g, s):
-    """oniris_vae_wide_conv_a: the sequence (B, g + T, H, W, C) -> u (B, T, H, W, C)."""
+    """oniris_vae_wide_conv_a (oniris_vae_wide_conv_a_bf16 where rb holds bf16 weights): the sequence (B, g + T, H, W, C) -> u
+    (B, T, H, W, C)."""
     B, T, H, W, C = seq.shape[0], seq.shape[1] - g, *seq.shape[2:]
     u = _new(seq, B, T, H, W, C)
-    _lib.check(_lib.lib.oniris_vae_wide_conv_a(_p(seq), _p(rb["wa"]), _p(rb["ba"]), _p(u), B, T, H, W, C, g, s), "vae_wide_conv_a")
+    entry, what = _wide_entry("conv_a", rb)
+    _lib.check(entry(_p(seq), _p(rb["wa"]), _p(rb["ba"]), _p(u), B, T, H, W, C, g, s), what)
     return u
 
 
 def wide_conv_b(a, x, rb, s):
-    """oniris_vae_wide_conv_b: -> x + conv B(a)."""
+    """oniris_vae_wide_conv_b (or its _bf16 form): -> x + conv B(a)."""
     B, T, H, W, C = x.shape
     y = torch.empty_like(x)
-    _lib.check(_lib.lib.oniris_vae_wide_conv_b(_p(a), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(y), B, T, H, W, C, s), "vae_wide_conv_b")
+    entry, what = _wide_entry("conv_b", rb)
+    _lib.check(entry(_p(a), _p(x), _p(rb["wb"]), _p(rb["bb"]), _p(y), B, T, H, W, C, s), what)
     return y
 
 
@@ -251,7 +289,7 @@ def out(x, bk, s, lvm=None, want="next"):
         logvar = torch.empty_like(mean)
         sb, sc, st, sh, sw = mean.stride()
         strides = (sb, st, sh, sw, sc)
-    entry, what = (_lib.lib.oniris_vae_wide_out, "vae_wide_out") if bk["wide"] else (_lib.lib.oniris_vae_out, "vae_out")
+    entry, what = _wide_entry("out", bk) if bk["wide"] else (_lib.lib.oniris_vae_out, "vae_out")
     _lib.check(entry(_p(x), _p(bk["wo"]), _p(bk["bo"]), B, T, H, W, C, Cout, half, _p(lvm), _p(y if want == "next" else mean),
                      _p(logvar), *strides, _p(frames), s), what)
     return y if want == "next" else frames if want == "frames" else (mean, logvar)
@@ -262,7 +300,7 @@ def down(x, strides, dims, normalize, bk, s):
     x / 127.5 - 1 on load) -> (B, T, H, W, C) over `dims`."""
     B, T, H, W = dims
     y = _new(x, B, T, H, W, bk["C"])
-    entry, what = (_lib.lib.oniris_vae_wide_down, "vae_wide_down") if bk.get("wide_down") else (_lib.lib.oniris_vae_down, "vae_down")
+    entry, what = _wide_entry("down", bk) if bk.get("wide_down") else (_lib.lib.oniris_vae_down, "vae_down")
     _lib.check(entry(_p(x), int(x.dtype == torch.uint8), *strides, B, T, H, W, bk["Cin"], bk["tc"], bk["sc"], int(normalize),
                      _p(bk["wd"]), _p(bk["bd"]), bk["C"], _p(y), s), what)
     return y
@@ -381,6 +419,7 @@ class VAE(BetterModule):
         self.latent_channels = channels[-1]
         self._wide = max(widths) if max(widths) > MAX_NARROW else 0
         self._wide_training = self._wide_training_default
+        self._bf16_inference = False
         self.encoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="encoder")
         self.decoder = EncoderDecoder(channels, n_res_blocks, time_compressions, spatial_compressions, type="decoder")
         self.time_compression = np.prod(time_compressions)
@@ -399,6 +438,29 @@ class VAE(BetterModule):
         it, state_dict and kwargs do not hold it.  A model without a wide block trains either way, on the same kernels.  Returns
         self."""
         self._wide_training = bool(enabled)
+        return self
+
+    def bf16_inference(self, enabled=True):
+        """Switch the bf16-operand inference kernels (csrc/vae_wide_bf16.hip) on (or off again) for the blocks wider than MAX_NARROW:
+        `VAE512.from_pretrained(path).to("cuda").eval().bf16_inference()`.  Off as constructed, for `VAE` and `VAE512` alike.
+
+        The contract (csrc/vae_wide_bf16.h).  While it is on, in a wide block the two operands of every matrix product -- conv A,
+        conv B, `up`, `down`, `out`, and the GEMM `down` of a narrow block that compresses more than MAX_DOWN_K channels, the one other
+        MFMA launch of the VAE -- are rounded to bf16, round-to-nearest-even, exactly once: the weights when they are packed
+        (`weight.to(torch.bfloat16)`), the activated input while a kernel stages it.  Everything else stays fp32: the accumulation
+        (in an order fixed by (C, g, tc, sc, Cout) alone, so the bit identities of chunked decoding and encoding hold as before),
+        the bias, the residual x of conv B and the channel-area residuals of `out` and `down` (read from the unrounded tensor),
+        exp(logvar_multiplier), the uint8 conversion, the activation pass, the t-embedding, every tensor between launches and
+        every cache entry: a cache written in one mode is accepted in the other.  The register-tile kernels of the narrow blocks
+        (csrc/vae.hip, csrc/vae_conv3.h, csrc/vae_encoder.hip) are untouched.
+
+        It governs `encode`, `encode_long_sequence`, `encode_frames`, `frames_to_latents`, `decode`, `decode_frames`,
+        `latents_to_frames`, and `forward` in eval mode or under torch.no_grad().  The training path of `forward` ignores it: it stays
+        fp32 and keeps its bits (it packs fp32 weights of its own; a model that alternates training steps and bf16 inference
+        re-packs at every change of side).  The packs are rebuilt when the switch changes; with it on a wide block's pack holds the
+        bf16 weights and no fp32 copy of them.  A plain attribute like `wide_training`: copy.deepcopy keeps it, state_dict and
+        kwargs do not hold it.  On a model without a wide block it is accepted and changes nothing.  Returns self."""
+        self._bf16_inference = bool(enabled)
         return self
 
     # ---- encode + mix + decode (vae.py:228-237)
@@ -459,10 +521,13 @@ class VAE(BetterModule):
         return r_mean, r_logvar, mean, {"encoder": enc_cache, "decoder": dec_cache}
 
     # ---- packed device weights
-    def _pack(self, device):
-        """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip and vae_conv3.h, rebuilt when one changed."""
+    def _pack(self, device, bf16=None):
+        """fp32 device copies of the decoder's parameters in the layouts of csrc/vae.hip and vae_conv3.h, rebuilt when one changed.
+        bf16 (None: as `bf16_inference` set it; the training path passes False): the weights of the wide blocks as bf16
+        (csrc/vae_wide_bf16.h); part of the signature, so a change rebuilds the pack."""
+        bf16 = bool(self.__dict__.get("_bf16_inference", False) if bf16 is None else bf16)
         params = list(self.decoder.parameters()) + list(self.decoder.buffers())
-        sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        sig = (str(device), bf16) + tuple((p.data_ptr(), p._version) for p in params)
         pk = self.__dict__.get("_oniris_vae_pack")
         if pk is not None and pk["sig"] == sig:
             return pk
@@ -475,7 +540,7 @@ class VAE(BetterModule):
                 nch, gpt = (0, 0) if wide else (_nch(C), _gpt(C, g))
                 res = []
                 for rb in blk.res_blocks:
-                    res.append(dict((_pack_res_wide if wide else _pack_res)(rb, C, g, f32), emb_off=eoff))
+                    res.append(dict(_pack_res_wide(rb, C, g, f32, bf16) if wide else _pack_res(rb, C, g, f32), emb_off=eoff))
                     off = sum(x.numel() for x in tparams)
                     tparams += [rb.fourier_cond.freqs.detach().to(**f32), rb.fourier_cond.phases.detach().to(**f32),
                                 rb.t_cond.weight.detach().to(**f32).reshape(-1), rb.t_cond.bias.detach().to(**f32)]
@@ -488,8 +553,10 @@ class VAE(BetterModule):
                           bo=blk.final_conv.bias.detach().to(**f32).contiguous(), res=res)
                 if wide:                                             # the 1x1 stages as GEMMs (csrc/vae_wide_conv.h)
                     bk["wu"], bk["bu"] = _pack_lin_wide(blk.decompression_block.weight, blk.decompression_block.bias, C, C,
-                                                        blk.time_compression * blk.spatial_compression ** 2, f32)
-                    bk["wo"], bk["bo"] = _pack_lin_wide(blk.final_conv.weight, blk.final_conv.bias, C, Cout, 1, f32)
+                                                        blk.time_compression * blk.spatial_compression ** 2, f32, bf16)
+                    bk["wo"], bk["bo"] = _pack_lin_wide(blk.final_conv.weight, blk.final_conv.bias, C, Cout, 1, f32, bf16)
+                    if bf16:
+                        bk["bf16"] = True
                 blocks.append(bk)
             pk = dict(sig=sig, blocks=blocks, tparams=torch.cat(tparams).contiguous(),
                       table=torch.tensor(table, dtype=torch.int32, device=device), n_rb=len(table) // 3, emb_per_row=eoff,
@@ -578,14 +645,16 @@ class VAE(BetterModule):
         return frames.cpu().numpy().astype(int)
 
     # ---- the encoder
-    def _pack_encoder(self, device):
+    def _pack_encoder(self, device, bf16=None):
         """fp32 copies of the encoder's parameters on `device` in the layouts of csrc/vae_encoder.hip and csrc/vae_conv3.h, rebuilt
         when a parameter changed.  pk["params"] names every state_dict entry that went into it.  A block wider than MAX_NARROW
         carries wide=True and its ResBlocks the layouts of csrc/vae_wide_conv.h; its `down`, and that of any block compressing
         more than MAX_DOWN_K channels, carries wide_down=True and the GEMM layout (_pack_down_wide).  Every other block holds
-        exactly what it held before there were wide ones."""
+        exactly what it held before there were wide ones.  bf16: as in _pack; the ResBlocks of a wide block then hold bf16 weights
+        and bf16=True, and so does every block whose `down` is the GEMM (wide_down: an MFMA launch, whatever the block's width)."""
+        bf16 = bool(self.__dict__.get("_bf16_inference", False) if bf16 is None else bf16)
         params = list(self.encoder.parameters())
-        sig = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        sig = (str(device), bf16) + tuple((p.data_ptr(), p._version) for p in params)
         pk = self.__dict__.get("_oniris_vae_enc_pack")
         if pk is not None and pk["sig"] == sig:
             return pk
@@ -598,7 +667,7 @@ class VAE(BetterModule):
                 K = Cin * npos
                 wide, wide_down = C > MAX_NARROW, C > MAX_NARROW or K > MAX_DOWN_K
                 if wide_down:                                  # the GEMM of csrc/vae_wide_conv.h
-                    wd, bd = _pack_down_wide(blk.compression_block.weight, blk.compression_block.bias, Cin, C, npos, f32)
+                    wd, bd = _pack_down_wide(blk.compression_block.weight, blk.compression_block.bias, Cin, C, npos, f32, bf16)
                 else:
                     g4 = (C + 3) // 4 * 4
                     wd = torch.zeros(K, 2, g4, **f32)          # per k = ((tc hc) wc) c: the conv weights | the area windows
@@ -613,7 +682,7 @@ class VAE(BetterModule):
                 names += [pre + "compression_block.weight", pre + "compression_block.bias"]
                 res = []
                 for j, rb in enumerate(blk.res_blocks):
-                    res.append((_pack_res_wide if wide else _pack_res)(rb, C, g, f32))
+                    res.append(_pack_res_wide(rb, C, g, f32, bf16) if wide else _pack_res(rb, C, g, f32))
                     names += [pre + f"res_blocks.{j}.{n}" for n in ("conv3d0.conv3d.weight", "conv3d0.conv3d.bias", "conv3d1.weight",
                                                                    "conv3d1.bias")]
                 nch, gpt = (0, 0) if wide else (_nch(C), _gpt(C, g))
@@ -623,6 +692,8 @@ class VAE(BetterModule):
                     bk["wide"] = True
                 if wide_down:
                     bk["wide_down"] = True
+                    if bf16:                                   # read by `down` alone: a ResBlock's pack carries its own flag
+                        bk["bf16"] = True
                 blocks.append(bk)
             pk = dict(sig=sig, blocks=blocks, params=names, zeros={})
         self.__dict__["_oniris_vae_enc_pack"] = pk

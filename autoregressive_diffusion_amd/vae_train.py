@@ -444,7 +444,7 @@ def run(vae, x, t_b, noise):
     the encode, as in the reference) -> (r_mean, r_logvar, mean), attached to the autograd graph of the VAE's parameters."""
     from .edm2.utils import bmult
     dev = x.device
-    epk, dpk = vae._pack_encoder(dev), vae._pack(dev)
+    epk, dpk = vae._pack_encoder(dev, bf16=False), vae._pack(dev, bf16=False)    # VAE.bf16_inference() is for inference only
     y = x.float().permute(0, 2, 3, 4, 1)
     for blk, bk in zip(vae.encoder.encoder_blocks, epk["blocks"]):
         y = Down.apply(y, blk.compression_block.weight, blk.compression_block.bias, bk)

@@ -25,7 +25,7 @@ extern "C" {
 typedef void* oniris_stream_t;
 
 const char* oniris_last_error(void);
-int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*), the wide encoder's oniris_vae_wide_down among them; guided sampling: OnirisConvArgs.ctx_rows (appended field),
+int oniris_abi_version(void);   /* 14.  Added within 14 (nothing existing changed): ONIRIS_EPI_ACT_BWD with OnirisConvArgs.ab_* (appended fields); the VAE encoder (oniris_vae_down, oniris_vae_latents); the VAE decoder (oniris_vae_*) and its wide path (oniris_vae_wide_*), the wide encoder's oniris_vae_wide_down among them, and the bf16-operand inference stages oniris_vae_wide_{conv_a,conv_b,up,out,down}_bf16; guided sampling: OnirisConvArgs.ctx_rows (appended field),
                                  * oniris_qkv_eval_pair, oniris_dart_input_pair, oniris_precond_out_guided; the VAE losses (oniris_vae_loss_*); LPIPS (oniris_lpips_*); the sampler's churn and target-MSE
                                  * step (oniris_sampler_step, oniris_sampler_mse_finish, oniris_sampler_ws_blocks; oniris_sampler_update unchanged).  13 -> 14: oniris_set_ew_nt_bytes, oniris_census / oniris_census_read (diagnostics), the fp32 verification path (oniris_conv_f32 / wgrad_f32 / attn_f32_*); no signature changed; 12 -> 13: oniris_dart_input(+ cpad: the packed input is 32 channels wide in the product, so that the stem conv runs on the
                                  * streaming kernels of the 32-channel level); 11 -> 12: oniris_set_cu_reserve; 10 -> 11: OnirisConvArgs.ctx_prod / ctx_prod_mode (appended fields); 9 -> 10: OnirisConvArgs.clip_flag,
@@ -736,6 +736,27 @@ int oniris_vae_wide_out(const float* x, const float* w, const float* bias, int B
 int oniris_vae_wide_down(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B, int To, int Ho,
                          int Wo, int Cin, int tcomp, int scomp, int normalize, const float* w, const float* bias, int Cout,
                          float* out, oniris_stream_t stream);
+
+/* The five matrix stages above with bf16 MFMA operands (v_mfma_f32_32x32x16_bf16), for inference, added within ABI 14 (nothing
+ * above changed).  csrc/vae_wide_bf16.hip, csrc/vae_wide_bf16.h (which states the numerical contract).  Each has the arguments,
+ * the argument checks and the error codes of its fp32 sibling, except w: bf16 bit patterns (the fp32 weights rounded to nearest
+ * even) in the sibling's layout [tap][CinP][nsub CP] with CinP = the input width rounded up to a multiple of 16 (not to even: the
+ * K step of the MFMA), zero where padded, 4-byte aligned.  The input is rounded to bf16 (nearest even) as it is staged; products
+ * are exact and summed in fp32 in the order time tap (down: sub-position), 32-channel chunk, spatial tap, 16-channel K step, then
+ * the bias and the residual -- res of conv_b and the channel-area terms of out and down come from the unrounded fp32 tensors.
+ * Everything in HBM is fp32: an output, or a cache entry of oniris_vae_wide_act, serves either path.                             */
+int oniris_vae_wide_conv_a_bf16(const float* S, const uint16_t* w, const float* bias, float* out, int B, int T, int H, int W, int C,
+                                int g, oniris_stream_t stream);
+int oniris_vae_wide_conv_b_bf16(const float* u, const float* res, const uint16_t* w, const float* bias, float* out, int B, int T, int H,
+                                int W, int C, oniris_stream_t stream);
+int oniris_vae_wide_up_bf16(const float* x, const uint16_t* w, const float* bias, float* out, int B, int T, int H, int W, int C,
+                            int tcomp, int scomp, oniris_stream_t stream);
+int oniris_vae_wide_out_bf16(const float* x, const uint16_t* w, const float* bias, int B, int T, int H, int W, int Cin, int Cout,
+                             int split, const float* logvar_mult, float* out, float* out2, int64_t sb, int64_t st, int64_t sh,
+                             int64_t sw, int64_t sc, uint8_t* frames, oniris_stream_t stream);
+int oniris_vae_wide_down_bf16(const void* x, int x_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int B, int To,
+                              int Ho, int Wo, int Cin, int tcomp, int scomp, int normalize, const uint16_t* w, const float* bias,
+                              int Cout, float* out, oniris_stream_t stream);
 
 /* Backward of the wide VAE stages, added within ABI 14 (nothing above changed).  csrc/vae_wide_train.hip, csrc/vae_wide_train.h.
  * The training forward of a wide ResBlock is oniris_vae_wide_act (cache_in NULL: the prefix is the first g activated frames) /
