@@ -16,6 +16,9 @@ What the epilogues read (csrc/conv_parts.h, csrc/conv_kernels.h; the same in eve
                        conv_fwd takes the kernel's own `out` (out_bf16=..., itself held to its bound) for it
   EPI_MPSUM            out  = bf16(clip(ta * res + tb * v)) from the fp32 v;  out2 = bf16(v)
   ctx_out              bf16(acc_ctx), the un-gated context product of frame (b, t)
+  ctx_prod             the same product as the FP32 tensor the one-frame launches keep (mode 1 / 3) or read back (mode 2)
+  ctx_rows             rows b >= ctx_rows of a guided pair:  v = acc_own, epilogue on escale[b - ctx_rows] and res[b]
+  x2 / act_out         taps 1: x is [bf16(cat_w1 x) | bf16(cat_w2 x2)], act_out = bf16(silu(that) / 0.596)
   clip_flag            1 iff the STORED value of some element is not below the clip in magnitude
 
 Bounds (derived from the chain lengths, not fitted).  With round-to-nearest fp32 arithmetic a chain of n operations is off by at
@@ -30,6 +33,10 @@ most 2^-8 of the stored value (glue_oracle.U_BF16):
                   is rounded in fp32, which for z << 0 is a RELATIVE error of ~|z| 2^-24 in sigmoid(z)), with u = U_F32_64 of
                   glue_oracle for the ~20 fp32 operations and the ~1 ulp hardware exp2 / rcp, plus 2^-112 absolute for the fp32
                   underflow of sigmoid(z) at z < -87 (the probes reach |z| of a few hundred).
+  own-only rows   the same bound with K = 9 Cin: the frames that walk the own taps only (ctx_prod_mode 2, the 2-D rows of a pair)
+  fp32 ctx_prod   |got - ref| <= (18 Cin + 4) * 2^-24 * mag  (bound_ctx_prod): 18 Cin exact products summed in fp32 in any order,
+                  + 4 for the four partial tiles added in LDS; the store is fp32, so there is no 2^-8 term.
+  act_out         glue_oracle.bound_bf16 of (a, |a|), a = silu(xo) / 0.596 of the exact xo: the bound mp_silu has there.
   slab sums       |sum_s slab[s] - ref| <= (2^-8 [+ 2^-8 with scale] + chain * 2^-24) * mag
                   every slab is ONE bf16 rounding of its fp32 partial sum, so 2^-8 * mag covers all slabs together whatever the
                   split; `scale` adds the bf16 rounding wgrad_fold applies to scale[n] * dy; chain = the positions one slab sums
@@ -67,6 +74,12 @@ def bound_act(pair):
     """out2 of EPI_EMB_SILU (an elementwise function of the kernel's own bf16 `out`).  The constant is fp32 underflow: from z < -87
     on sigmoid(z) is below 2^-126 and flushes to zero, an absolute error of at most |z| 2^-126 / 0.596 < 2^-112 for |z| < 2^13."""
     return U_BF16 * pair[0].abs() + GO.U_F32_64 * pair[1] + 2.0 ** -112
+
+
+def bound_ctx_prod(pair, Cin):
+    """The FP32 context product a one-frame launch keeps (OnirisConvArgs.ctx_prod): a sum of 18 Cin exact bf16 x bf16 products in
+    fp32, in any order, + the four partial tiles added in LDS.  No 2^-8 term: the store is fp32."""
+    return (18 * Cin + 4) * U1 * pair[1]
 
 
 def wgrad_chain(positions, nsplit):
@@ -130,9 +143,17 @@ def _conv_frames(x, w, taps, dtype, drop=None):
     return val, mag
 
 
+def cat_input(x, x2, cat_w):
+    """The two-source input of a 1x1 launch (OnirisConvArgs.x2): xo = [bf16(cat_w1 * x) | bf16(cat_w2 * x2)], every product formed in
+    float32 from the float32 cat_w the launch is handed and rounded ONCE to bf16 -- the op's definition, reproduced exactly.
+    x (..., C1), x2 (..., C2) -> float32 (..., C1 + C2) holding bf16 values."""
+    f = lambda t, w: (t.detach().to("cpu", torch.float32) * torch.tensor(float(w), dtype=torch.float32)).to(torch.bfloat16).float()
+    return torch.cat([f(x, cat_w[0]), f(x2, cat_w[1])], -1)
+
+
 def conv_fwd(x, ctx, w_own, w_ctx, B, S, T, H, W, Cin, Cout, taps, coef_own=None, coef_ctx=None, ctx_bstride=0, ctx_T=0, coff=(0, 0),
              ctx_fill=0.0, epi=EPI_NONE, res=None, escale=None, ta=0.0, tb=0.0, clip=0.0, out_bf16=None, dtype=torch.float64,
-             _defect=None):
+             ctx_prod=None, ctx_prod_mode=0, ctx_rows=0, x2=None, x_split=0, cat_w=(1.0, 1.0), _defect=None):
     """oniris_conv_fwd:  v[n] = coef_own[n] * conv(x[n], w_own) + coef_ctx[n] * sum_j conv(ctxframe(b, t + coff[j]), w_ctx[j]),
     n = (b, s, t);  ctxframe(b, f) = ctx[b * ctx_bstride + f] if 0 <= f < ctx_T else a frame of ctx_fill (inside the image only:
     the spatial padding stays zero).  x (B*S*T, H, W, Cin); ctx (rows, H, W, Cin) or None; w_own [taps][CoutP][CinP], w_ctx
@@ -140,43 +161,94 @@ def conv_fwd(x, ctx, w_own, w_ctx, B, S, T, H, W, Cin, Cout, taps, coef_own=None
     columns, the row pitch is the launch's business.  out_bf16: the kernel's own `out` for EPI_EMB_SILU (None: this function's
     rounding).  Returns a dict of (value, mag) pairs: 'v', 'out', and where they exist 'out2', 'ctx_out'; 'clip_hit' (bool: some
     |bf16(out)| >= clip) and 'clip_margin' (min over elements of | |q| - clip |, the distance of the unclipped sum from the clip).
+
+    The evaluation-path options (include/oniris.h; all off by default):
+      ctx_prod_mode   0 / 1: as above, and the entry 'ctx_prod' = the un-gated context product (y3, m3) that the launch keeps as an
+                      FP32 tensor (mode 1; the same pair as 'ctx_out', which is its bf16 store);  3: that entry ALONE (x, coef_*, the
+                      epilogue are not read);  2: `ctx_prod` is an INPUT, v = coef_own * y2 + coef_ctx * ctx_prod with magnitude
+                      |coef_own| m2 + |coef_ctx| |ctx_prod| -- ctx and w_ctx are not read (None will do).
+      ctx_rows        R > 0 with B = 2 R, S = T = 1 (a guided pair): ctx, coef_*, escale and ctx_prod hold R rows; rows b >= R are
+                      v = y2 alone -- no coefficient, no context -- with the epilogue on escale[b - R] and res[b]; 'ctx_prod' (and
+                      'ctx_out') have R rows.
+      x2, x_split,    taps 1 without a context: the input is xo = cat_input(x (.., x_split), x2 (.., Cin - x_split), cat_w), the conv
+      cat_w           is taken of that xo in float64, and 'act_out' = (silu(xo) / 0.596, its magnitude): an elementwise function
+                      of the exact xo, the pair glue_oracle.act_fwd gives mp_silu.
     `_defect`: the deliberate defects of test_conv_oracle (None: the restatement)."""
     N = B * S * T
+    R = ctx_rows
+    assert R == 0 or (B == 2 * R and S == 1 and T == 1)
+    Bc = R if R else B                                # the sequences that have a context
+    Nc = Bc * S * T
     d = lambda t: None if t is None else t.detach().to("cpu", dtype)
+    r = {}
+    if x2 is not None:
+        assert taps == 1 and ctx is None and 0 < x_split < Cin
+        if _defect == "cat_swap":
+            cat_w = (cat_w[1], cat_w[0])
+        x2 = x2.reshape(N, H, W, Cin - x_split)
+        xo = cat_input(x.reshape(N, H, W, x_split), x2, cat_w)
+        if _defect == "split_off8":                   # the scale changes 8 channels late: x2's first 8 channels times cat_w1
+            xo[..., x_split:x_split + 8] = cat_input(x2[..., :8], x2[..., :0], cat_w)
+        x = xo
+        a = xo.double() * torch.sigmoid(xo.double()) / SILU_DIV
+        r["act_out"] = (a.to(dtype), a.abs().to(dtype))
+    has_ctx = ctx is not None or ctx_prod_mode == 2
+    y3 = m3 = None
+    if has_ctx:
+        if ctx_prod_mode == 2:
+            y3 = d(ctx_prod).reshape(Bc * T, H, W, Cout)
+            m3 = y3.abs()
+        else:
+            ctx = d(ctx).reshape(-1, H, W, Cin)
+            wc = d(w_ctx)[:, :Cout, :Cin]
+            if _defect == "coff_swap":
+                coff = (coff[1], coff[0])
+            if _defect == "append_bstride":
+                ctx_bstride = T
+            fill = 0.0 if _defect == "fill0" else ctx_fill
+            y3 = torch.zeros(Bc * T, H, W, Cout, dtype=dtype)
+            m3 = torch.zeros_like(y3)
+            for j in range(2):
+                fr = torch.full((Bc * T, H, W, Cin), fill, dtype=dtype)
+                for b in range(Bc):
+                    for t in range(T):
+                        f = t + coff[j]
+                        if 0 <= f < ctx_T:
+                            fr[b * T + t] = ctx[b * ctx_bstride + f]
+                        elif _defect == "cross_sequence" and coff[j] == -1 and b > 0:
+                            fr[b * T + t] = ctx[b * ctx_bstride + f]            # the frame in front of row b's first: row b - 1's
+                t_, m_ = _conv_frames(fr, wc[j * taps:(j + 1) * taps], taps, dtype)
+                y3 += t_
+                m3 += m_
+            r["ctx_out"] = (y3, m3)
+            r["ctx_prod"] = (GO.bf(y3), m3) if _defect == "ctx_prod_bf16" else (y3, m3)
+            if ctx_prod_mode == 3:
+                return {"ctx_prod": r["ctx_prod"]}
     x = d(x).reshape(N, H, W, Cin)
     wo = d(w_own)[:, :Cout, :Cin]
     drop = (1, 0, 4) if _defect == "tap_drop" else None
     y2, m2 = _conv_frames(x, wo, taps, dtype, drop)
-    co = torch.ones(N, dtype=dtype) if coef_own is None else d(coef_own).reshape(N)
+    co = torch.ones(N, dtype=dtype)                   # (rows b >= ctx_rows: no coefficient)
+    if coef_own is not None:
+        co[:Nc] = d(coef_own).reshape(Nc)
+    if _defect == "pair_twin_coef":
+        co[R:] = co[:R]
     v, mag = co.reshape(N, 1, 1, 1) * y2, co.abs().reshape(N, 1, 1, 1) * m2
-    r = {}
-    if ctx is not None:
-        ctx = d(ctx).reshape(-1, H, W, Cin)
-        wc = d(w_ctx)[:, :Cout, :Cin]
-        cc = torch.ones(N, dtype=dtype) if coef_ctx is None else d(coef_ctx).reshape(N).clone()
+    if has_ctx:
+        cc = torch.zeros(N, dtype=dtype)              # (rows b >= ctx_rows: no context)
+        cc[:Nc] = 1.0 if coef_ctx is None else d(coef_ctx).reshape(Nc)
         if _defect == "coef_neighbour":
             cc[1] = cc[2]
-        if _defect == "coff_swap":
-            coff = (coff[1], coff[0])
-        fill = 0.0 if _defect == "fill0" else ctx_fill
-        y3 = torch.zeros(B * T, H, W, Cout, dtype=dtype)
-        m3 = torch.zeros_like(y3)
-        for j in range(2):
-            fr = torch.full((B * T, H, W, Cin), fill, dtype=dtype)
-            for b in range(B):
-                for t in range(T):
-                    f = t + coff[j]
-                    if 0 <= f < ctx_T:
-                        fr[b * T + t] = ctx[b * ctx_bstride + f]
-                    elif _defect == "cross_sequence" and coff[j] == -1 and b > 0:
-                        fr[b * T + t] = ctx[b * ctx_bstride + f]            # the frame in front of row b's first: row b - 1's
-            t_, m_ = _conv_frames(fr, wc[j * taps:(j + 1) * taps], taps, dtype)
-            y3 += t_
-            m3 += m_
-        r["ctx_out"] = (y3, m3)
-        e3 = lambda t: t.reshape(B, 1, T, H, W, Cout).expand(B, S, T, H, W, Cout).reshape(N, H, W, Cout)
-        v = v + cc.reshape(N, 1, 1, 1) * e3(y3)
-        mag = mag + cc.abs().reshape(N, 1, 1, 1) * e3(m3)
+        if _defect == "pair_ctx_added":
+            cc[R:] = cc[:R]
+        if _defect == "mode2_scaled":
+            cc = cc * co
+        e3 = lambda t: t.reshape(Bc, 1, T, H, W, Cout).expand(Bc, S, T, H, W, Cout).reshape(Nc, H, W, Cout)
+        y3n, m3n = e3(y3), e3(m3)
+        if R:                                         # the twin's product, which only a defect's coefficient lets through
+            y3n, m3n = torch.cat([y3n, y3n]), torch.cat([m3n, m3n])
+        v = v + cc.reshape(N, 1, 1, 1) * y3n
+        mag = mag + cc.abs().reshape(N, 1, 1, 1) * m3n
     if _defect == "ragged_cout":
         # ONE 16-byte store -- the last 8-channel block of one pixel -- filled from the padded weight rows behind it
         lo = Cout - 8
@@ -190,7 +262,10 @@ def conv_fwd(x, ctx, w_own, w_ctx, B, S, T, H, W, Cin, Cout, taps, coef_own=None
     elif epi == EPI_EMB_SILU:
         r["out"] = (v, mag)
         vb = GO.bf(v) if out_bf16 is None else d(out_bf16).reshape(N, H, W, Cout)
-        z = vb * d(escale).reshape(N, 1, 1, Cout)
+        es = d(escale).reshape(Nc, 1, 1, Cout)
+        if R:                                         # a 2-D row reads the emb-scale row of its twin
+            es = torch.cat([es, es[:1].expand(R, 1, 1, Cout) if _defect == "pair_escale0" else es])
+        z = vb * es
         a = z * torch.sigmoid(z) / SILU_DIV
         r["out2"] = (a, (1 + z.abs()) * a.abs())
     else:

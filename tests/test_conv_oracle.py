@@ -2,10 +2,15 @@
 
   pinned         every restatement against float64 torch.nn.functional.conv2d + autograd assembled independently (the context
                  concatenation of test_ops_gpu._gated_conv_train_case, oracle.oniris_oracle.mp_sum / mp_silu): forward, data gradient
-                 through the flipped and transposed `wb` packing, weight gradient; 1e-12 relative
+                 through the flipped and transposed `wb` packing, weight gradient; 1e-12 relative.  The evaluation-path options
+                 likewise: the append against ONE F.conv3d over [cached pair | new frames], ctx_prod_mode 1 / 2 / 3, the rows of a
+                 guided pair (ctx_rows), the two-source 1x1 conv with its activation
   not too tight  the same formulas with bf16 operands, fp32 accumulation and one bf16 store fit every bound
   not too loose  deliberate defects injected into the restatement exceed the bound on at least one element -- while the starred ones
-                 change the tensor's relative L2 norm by less than the 5e-3 the aggregate tests (test_ops_gpu.py) allow
+                 change the tensor's relative L2 norm by less than the 5e-3 the aggregate tests (test_ops_gpu.py) allow.  For the
+                 evaluation path: a 2-D row of a pair with its twin's gate coefficient, with the context added, with emb-scale row 0;
+                 a kept product scaled by coef_own or stored through bf16; an append with the row stride of its frames alone; the
+                 cat weights swapped; the split 8 channels late
   exact probes   for every case of test_conv_stages_gpu.py: all values integers and mag <= 256 for every output element and every
                  weight-gradient element, the condition under which any summation order and any split is exact
 
@@ -109,6 +114,94 @@ def test_plain_and_1x1_are_pinned():
         close(r["out"][0], nhwc(F.conv2d(x, w, padding=k // 2)), f"plain taps={taps}")
 
 
+def _cached_problem(B, T, H, W, cin, cout, seed):
+    """A cached evaluation assembled with torch: T new frames per sequence behind a cached pair, the context product as ONE
+    F.conv3d over [pair | frames] (edm2/conv.py:84-86), NCHW float64."""
+    gen = _gen(seed)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=F64)
+    x, pair = r(B, T, cin, H, W), r(B, 2, cin, H, W)
+    w2, w3 = r(cout, cin, 3, 3) / math.sqrt(9 * cin), r(cout, cin, 2, 3, 3) / math.sqrt(18 * cin)
+    ca, cb = torch.rand(B * T, generator=gen, dtype=F64) + 0.2, torch.rand(B * T, generator=gen, dtype=F64) - 0.5
+    y2 = F.conv2d(x.reshape(B * T, cin, H, W), w2, padding=1)
+    m2 = F.conv2d(x.reshape(B * T, cin, H, W).abs(), w2.abs(), padding=1)
+    seq = torch.cat([pair, x], 1).permute(0, 2, 1, 3, 4)                                  # (B, cin, T + 2, H, W)
+    y3 = F.conv3d(seq, w3, padding=(0, 1, 1))[:, :, :T].permute(0, 2, 1, 3, 4).reshape(B * T, cout, H, W)
+    m3 = F.conv3d(seq.abs(), w3.abs(), padding=(0, 1, 1))[:, :, :T].permute(0, 2, 1, 3, 4).reshape(B * T, cout, H, W)
+    flat = lambda t: nhwc(t.reshape(-1, *t.shape[2:]))
+    return dict(x=x, pair=pair, xl=flat(x), pairl=flat(pair), ctxl=flat(torch.cat([pair, x], 1)), wf2=CO.pack_wf(w2.reshape(cout, cin, 9)),
+                wf3=CO.pack_wf(w3.reshape(cout, cin, 2, 9)), w2=w2, ca=ca, cb=cb, y2=y2, m2=m2, y3=y3, m3=m3, gen=gen)
+
+
+def test_append_is_pinned():
+    """S = 1, ctx = [cached pair | the T new frames] with row stride T + 2 and coff (0, 1)."""
+    B, T, H, W, cin, cout = 2, 3, 4, 6, 8, 16
+    p = _cached_problem(B, T, H, W, cin, cout, 21)
+    r = CO.conv_fwd(p["xl"], p["ctxl"], p["wf2"], p["wf3"], B, 1, T, H, W, cin, cout, 9, coef_own=p["ca"], coef_ctx=p["cb"],
+                    ctx_bstride=T + 2, ctx_T=T + 2, coff=(0, 1))
+    e = lambda c: c.reshape(-1, 1, 1, 1)
+    close(r["out"][0], nhwc(e(p["ca"]) * p["y2"] + e(p["cb"]) * p["y3"]), "append v")
+    close(r["out"][1], nhwc(e(p["ca"]).abs() * p["m2"] + e(p["cb"]).abs() * p["m3"]), "append mag")
+    close(r["ctx_prod"][0], nhwc(p["y3"]), "append y3")
+
+
+def test_ctx_prod_modes_and_ctx_rows_are_pinned():
+    """The one-frame forms: the kept product written (1), alone (3), read back (2); the guided pair with every epilogue."""
+    R, H, W, cin, cout = 3, 4, 6, 8, 16
+    p = _cached_problem(R, 1, H, W, cin, cout, 22)
+    gen = p["gen"]
+    e = lambda c: c.reshape(-1, 1, 1, 1)
+    v3 = e(p["ca"]) * p["y2"] + e(p["cb"]) * p["y3"]
+    geo = dict(B=R, S=1, T=1, H=H, W=W, Cin=cin, Cout=cout, taps=9)
+    one = dict(geo, ctx_bstride=2, ctx_T=2, coff=(0, 1), coef_own=p["ca"], coef_ctx=p["cb"])
+    for pm in (0, 1):
+        r = CO.conv_fwd(p["xl"], p["pairl"], p["wf2"], p["wf3"], ctx_prod_mode=pm, **one)
+        close(r["out"][0], nhwc(v3), f"mode {pm} v")
+        close(r["ctx_prod"][0], nhwc(p["y3"]), f"mode {pm} y3")
+        close(r["ctx_prod"][1], nhwc(p["m3"]), f"mode {pm} m3")
+    r = CO.conv_fwd(None, p["pairl"], p["wf2"], p["wf3"], ctx_prod_mode=3, **dict(one, coef_own=None, coef_ctx=None))
+    assert set(r) == {"ctx_prod"}
+    close(r["ctx_prod"][0], nhwc(p["y3"]), "mode 3 y3")
+    kept = torch.randn(R, cout, H, W, generator=gen, dtype=F64)
+    r = CO.conv_fwd(p["xl"], None, p["wf2"], None, ctx_prod=nhwc(kept), ctx_prod_mode=2, **one)
+    close(r["out"][0], nhwc(e(p["ca"]) * p["y2"] + e(p["cb"]) * kept), "mode 2 v")
+    close(r["out"][1], nhwc(e(p["ca"]).abs() * p["m2"] + e(p["cb"]).abs() * kept.abs()), "mode 2 mag")
+    assert "ctx_prod" not in r
+    # the pair: R more rows of x and res, y2 alone, the emb-scale row of the twin
+    x2d = torch.randn(R, cin, H, W, generator=gen, dtype=F64)
+    vp = torch.cat([v3, F.conv2d(x2d, p["w2"], padding=1)])
+    xp = torch.cat([p["xl"], nhwc(x2d)])
+    pk = dict(one, B=2 * R, ctx_rows=R)
+    c = 1 + 0.3 * torch.randn(R, cout, generator=gen, dtype=F64)
+    res = torch.randn(2 * R, cout, H, W, generator=gen, dtype=F64)
+    r = CO.conv_fwd(xp, p["pairl"], p["wf2"], p["wf3"], epi=CO.EPI_EMB_SILU, escale=c, out_bf16=nhwc(vp), ctx_prod_mode=1, **pk)
+    close(r["out"][0], nhwc(vp), "pair v")
+    close(r["out2"][0], nhwc(O.mp_silu(vp * torch.cat([c, c])[:, :, None, None])), "pair emb_silu")
+    close(r["ctx_prod"][0], nhwc(p["y3"]), "pair y3")
+    assert r["ctx_prod"][0].shape[0] == R
+    t = 0.3
+    nrm = math.sqrt((1 - t) ** 2 + t ** 2)
+    r = CO.conv_fwd(xp, p["pairl"], p["wf2"], p["wf3"], epi=CO.EPI_MPSUM, res=nhwc(res), ta=(1 - t) / nrm, tb=t / nrm, **pk)
+    close(r["out"][0], nhwc(O.mp_sum(res, vp, t)), "pair mpsum")
+    r = CO.conv_fwd(xp, None, p["wf2"], None, ctx_prod=nhwc(kept), ctx_prod_mode=2, **pk)
+    close(r["out"][0], nhwc(torch.cat([e(p["ca"]) * p["y2"] + e(p["cb"]) * kept, vp[R:]])), "pair mode 2")
+
+
+def test_two_source_1x1_is_pinned():
+    gen = _gen(23)
+    N, H, W, C1, C2, cout = 3, 5, 7, 24, 16, 40
+    bf = lambda t: t.to(torch.bfloat16)
+    x, skip = bf(torch.randn(N, C1, H, W, generator=gen)), bf(torch.randn(N, C2, H, W, generator=gen))
+    w = torch.randn(cout, C1 + C2, 1, 1, generator=gen, dtype=F64)
+    w1, w2 = 1.2345678, 0.7654321
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    xo = torch.cat([bf(x.float() * f32(w1)), bf(skip.float() * f32(w2))], 1).double()
+    r = CO.conv_fwd(nhwc(x), None, CO.pack_wf(w.reshape(cout, C1 + C2, 1)), None, 1, 1, N, H, W, C1 + C2, cout, 1, x2=nhwc(skip), x_split=C1,
+                    cat_w=(w1, w2))
+    close(r["out"][0], nhwc(F.conv2d(xo, w)), "two-source out")
+    close(r["out"][1], nhwc(F.conv2d(xo.abs(), w.abs())), "two-source mag")
+    close(r["act_out"][0], nhwc(O.mp_silu(xo)), "act_out")
+
+
 @pytest.mark.parametrize("B,T,H,W,cin,cout", [(2, 3, 4, 6, 8, 16), (2, 1, 3, 5, 16, 8)])
 def test_data_and_weight_gradient_are_pinned(B, T, H, W, cin, cout):
     p = _gated_problem(B, T, H, W, cin, cout, 6)
@@ -155,7 +248,9 @@ def _usage(what, got, ref, bound):
     assert use <= 1.0, (what, use)
 
 
-_TIGHT_FWD = [r for r in CS.FWD if r[0] in ("st_8x8", "st_2x2", "st_8x8_dgrad", "st_1x1_36", "g16_64_64", "g8_32_64", "s_alias", "few_2", "ev_8x8", "st_1x1_nt3")]
+_TIGHT_FWD = [r for r in CS.FWD if r[0] in ("st_8x8", "st_2x2", "st_8x8_dgrad", "st_1x1_36", "g16_64_64", "g8_32_64", "s_alias", "few_2", "ev_8x8", "st_1x1_nt3",
+                                                     "ap_8x8", "ap_ones", "e1_store", "e1_ctx_96", "e1_read_160", "pair_silu", "pair_read",
+                                                     "cat_few_ragged", "cat_few_512")]
 
 
 @pytest.mark.parametrize("row", _TIGHT_FWD, ids=lambda r: r[0])
@@ -163,16 +258,25 @@ def test_forward_bounds_are_not_too_tight(row):
     name, mode, B, T, H, W, Cin, Cout, taps, epi = row[:10]
     d = CS.fwd_inputs(row, False)
     d["clip"] = CS.pick_clip(d, epi, False)
-    kw = {k: d[k] for k in ("B", "S", "T", "H", "W", "Cin", "Cout", "taps", "coef_own", "coef_ctx", "ctx_bstride", "ctx_T", "coff",
-                            "ctx_fill", "epi", "res", "escale", "ta", "tb", "clip")}
+    kw = {k: d[k] for k in CS._FWD_KW + ("clip",)}
     ctx = d["x"] if isinstance(d["ctx"], str) else d["ctx"]
     lo = CO.conv_fwd(d["x"], ctx, d["w_own"], d["w_ctx"], dtype=torch.float32, **kw)
+    if d["ctx_prod_mode"] in (1, 3):                 # the kept product: fp32 sum, fp32 store
+        rp = CS.fwd_reference(d)["ctx_prod"]
+        _usage(f"{name} ctx_prod", lo["ctx_prod"][0], rp[0], CO.bound_ctx_prod(rp, d["Cin"]))
+        if d["ctx_prod_mode"] == 3:
+            return
     out = lo["out"][0].to(torch.bfloat16)
     r = CS.fwd_reference(d, out_bf16=out)
-    u = CO.u_fwd(taps * Cin * CS._ctx_phases(mode), 12)
+    u = CS.fwd_u(row)
     _usage(f"{name} out", out, r["out"][0], CO.bound_out(r["out"], u))
+    if "act_out" in r:
+        xo = CO.cat_input(d["x"], d["x2"], d["cat_w"])
+        a32 = xo * torch.sigmoid(xo) / torch.tensor(CO.SILU_DIV, dtype=torch.float32)
+        _usage(f"{name} act_out", a32.to(torch.bfloat16), r["act_out"][0], CS.GO.bound_bf16(*r["act_out"]))
     if "ctx_out" in r:
-        _usage(f"{name} ctx_out", lo["ctx_out"][0].to(torch.bfloat16), r["ctx_out"][0], CO.bound_out(r["ctx_out"], u))
+        u3 = CO.u_fwd(taps * d["Cin"] * CS._ctx_phases(mode), 12)
+        _usage(f"{name} ctx_out", lo["ctx_out"][0].to(torch.bfloat16), r["ctx_out"][0], CO.bound_out(r["ctx_out"], u3))
     if d["epi"] == CO.EPI_EMB_SILU:
         lo2 = CO.conv_fwd(d["x"], ctx, d["w_own"], d["w_ctx"], dtype=torch.float32, out_bf16=out, **kw)
         _usage(f"{name} out2", lo2["out2"][0].to(torch.bfloat16), r["out2"][0], CO.bound_act(r["out2"]))
@@ -231,9 +335,55 @@ def _defect(what, got, ref, bound, starred):
         assert l2 < 5e-3, (what, l2)
 
 
+def _eval_defect_problem(defect):
+    """The evaluation-path launch a defect is shown on: (positional arguments, keyword arguments, the tensor held, its bound as a
+    function of the good pair).  bf16 operands; the coefficients, emb-scales and cat weights differ from row to row as they do in
+    a rollout."""
+    gen = _gen(31)
+    bf = lambda *s, scale=1.0: (torch.randn(*s, generator=gen) * scale).to(torch.bfloat16)
+    H = W = 8
+    cin = cout = 8
+    if defect in ("cat_swap", "split_off8"):
+        C1, C2, N = 24, 16, 2
+        args = (bf(N, H, W, C1), None, CO.pack_wf(bf(cout, C1 + C2, 1, scale=(C1 + C2) ** -0.5)), None, 1, 1, N, H, W, C1 + C2, cout, 1)
+        kw = dict(x2=bf(N, H, W, C2), x_split=C1, cat_w=(1.29, 0.91))
+        return args, kw, "out", lambda good: CO.bound_out(good, CO.u_fwd(C1 + C2, 12))
+    w2, w3 = CO.pack_wf(bf(cout, cin, 9, scale=(27 * cin) ** -0.5)), CO.pack_wf(bf(cout, cin, 2, 9, scale=(27 * cin) ** -0.5))
+    if defect == "append_bstride":
+        B, T = 2, 3
+        x, pair = bf(B, T, H, W, cin), bf(B, 2, H, W, cin)
+        args = (x, torch.cat([pair, x], 1), w2, w3, B, 1, T, H, W, cin, cout, 9)
+        kw = dict(coef_own=0.9 - 0.05 * torch.arange(B * T), coef_ctx=0.3 + 0.05 * torch.arange(B * T), ctx_bstride=T + 2, ctx_T=T + 2, coff=(0, 1))
+        return args, kw, "out", lambda good: CO.bound_out(good, CO.u_fwd(27 * cin, 12))
+    R = 2
+    one = dict(coef_own=0.9 - 0.1 * torch.arange(R), coef_ctx=0.3 + 0.1 * torch.arange(R), ctx_bstride=2, ctx_T=2, coff=(0, 1))
+    if defect in ("mode2_scaled", "ctx_prod_bf16"):
+        pm = 2 if defect == "mode2_scaled" else 1
+        args = (bf(R, H, W, cin), bf(R * 2, H, W, cin), w2, w3, R, 1, 1, H, W, cin, cout, 9)
+        kw = dict(one, ctx_prod_mode=pm, ctx_prod=torch.randn(R, H, W, cout, generator=gen) if pm == 2 else None)
+        if pm == 1:
+            return args, kw, "ctx_prod", lambda good: CO.bound_ctx_prod(good, cin)
+        return args, kw, "out", lambda good: CO.bound_out(good, CO.u_fwd(9 * cin, 12))
+    assert defect in ("pair_twin_coef", "pair_ctx_added", "pair_escale0"), defect
+    args = (bf(2 * R, H, W, cin), bf(R * 2, H, W, cin), w2, w3, 2 * R, 1, 1, H, W, cin, cout, 9)
+    kw = dict(one, ctx_rows=R, epi=CO.EPI_EMB_SILU, escale=1 + 0.3 * torch.randn(R, cout, generator=gen))
+    if defect == "pair_escale0":
+        return args, kw, "out2", CO.bound_act
+    u = torch.tensor([CO.u_fwd(27 * cin, 12)] * R + [CO.u_fwd(9 * cin, 12)] * R, dtype=F64).reshape(2 * R, 1, 1, 1)
+    return args, kw, "out", lambda good: CO.bound_out(good, u)
+
+
+_EVAL_DEFECTS = ("pair_twin_coef", "pair_ctx_added", "pair_escale0", "mode2_scaled", "ctx_prod_bf16", "append_bstride", "cat_swap", "split_off8")
+
+
 @pytest.mark.parametrize("defect,starred", [("tap_drop", True), ("fill0", False), ("cross_sequence", False), ("coef_neighbour", True),
-                                            ("coff_swap", False), ("ragged_cout", True)])
+                                            ("coff_swap", False), ("ragged_cout", True)] + [(k, False) for k in _EVAL_DEFECTS])
 def test_forward_defects_stand_out(defect, starred):
+    if defect in _EVAL_DEFECTS:
+        args, kw, tensor, bound = _eval_defect_problem(defect)
+        good = CO.conv_fwd(*args, **kw)[tensor]
+        _defect(defect, CO.conv_fwd(*args, _defect=defect, **kw)[tensor][0], good[0], bound(good), starred)
+        return
     cout = 40 if defect == "ragged_cout" else 8
     x, w2, w3, kw = _wide(cout)
     good = CO.conv_fwd(x, x, w2, w3, **kw)["out"]
@@ -284,16 +434,19 @@ def _integers_below_256(case, name, pair):
     assert int((v != 0).sum()) * 100 >= v.numel(), (case, name, "the probe is all but empty")
 
 
-@pytest.mark.parametrize("row", CS.FWD, ids=lambda r: r[0])
+@pytest.mark.parametrize("row", CS.FWD + [CS.PAIR_FALLBACK], ids=lambda r: r[0])
 def test_forward_probes_are_exact(row):
     d = CS.fwd_inputs(row, True)
     d["clip"] = CS.pick_clip(d, row[9], True)
-    for k in ("x", "w_own", "w_ctx", "res", "coef_own", "coef_ctx"):
+    for k in ("x", "x2", "w_own", "w_ctx", "res", "coef_own", "coef_ctx", "ctx_prod"):
         if isinstance(d[k], torch.Tensor):
             assert bool((d[k].double() == d[k].double().round()).all()), (row[0], k)
     assert d["ta"] == round(d["ta"]) and d["tb"] == round(d["tb"]) and d["clip"] == round(d["clip"])
+    assert all(math.log2(w) == round(math.log2(w)) for w in d["cat_w"]), (row[0], "cat_w")
+    if row[0] == "ap_ones":
+        assert bool((d["ctx"].reshape(d["B"], d["T"] + 2, -1)[:, :2] == 1).all())
     r = CS.fwd_reference(d)
-    for name in ("v", "out", "ctx_out"):
+    for name in ("v", "out", "ctx_out", "ctx_prod"):
         if name in r:
             _integers_below_256(row[0], name, r[name])
     if row[9] == "mpsum_hit":
